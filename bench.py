@@ -14,12 +14,17 @@ masks on the device.  With N > 1 every rank runs its own replica 
 rank's time.  With --shard-T one video of that length is cut into N clip chunks (+ halo), two RCCL all-gathers per
 forward (cvpr2025-decafnet_amd/dist.py), strong scaling; rank 0 checks the result against the unsharded forward.
 
-Rank 0 prints ONE JSON line: the driver contract fields plus
+Rank 0 prints ONE JSON line: the driver contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of
+one timed step: exactly --steps steps are timed unless --min-timed-s asks for repeated blocks).  A plain run sets up, warms up,
+times the steps and prints that line; --full adds, after the timed steps (rank 0 of the replica mode)
   roofline     : dominant kernel family (dense-conv GEMM), live HIP-event timing of every launch
   parity       : max |delta| of logits / offsets of one timed video against the CPU oracle (the checker)
   cpu_baseline : the CPU oracle (a port of the reference algorithm) timed on this host's cores (N = 1 only)
   stages       : per-kernel-family time of one step (same event timing)
   post         : proposal decode + NMS latency and the NMS index match against the oracle
+  xattn_config2, mfma_sustained, nq8, one_forward_in_flight, one_video_per_call : the other configurations, each timed on its own
+--dump-outputs DIR writes what the last timed step returned to its caller (logits / offsets / masks of every video, float32 .npy;
+see dump_outputs); weights and inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import ctypes
@@ -57,8 +62,14 @@ def parse():
                          'holds --videos x --batch videos')
     ap.add_argument('--shard-T', type=int, default=0,
                     help='BASELINE configs[3]: one video of this many clips, clip-chunk sharded over the ranks (0 = replicas)')
-    ap.add_argument('--min-timed-s', type=float, default=2.0,
-                    help='repeat the timed block of --steps steps (each block barrier + synchronise bracketed) until this much time is covered')
+    ap.add_argument('--min-timed-s', type=float, default=0.0,
+                    help='repeat the timed block of --steps steps (each block barrier + synchronise bracketed) until this much time is covered '
+                         '(default 0: one block, exactly --steps timed steps)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure / check everything else: per-kernel roofline and stages, parity against the '
+                         'CPU oracle, CPU baseline, proposal decode + NMS, the other configurations (off: the headline figure only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)')
     ap.add_argument('--attn-mode', default='f16x3', choices=['f16x3', 'f16'],
                     help="attention products on the matrix cores: f16x3 (fp32 accurate, default) or f16 (one fp16 product: BASELINE configs[4]'s "
                          "'bf16 MFMA attention'; opt-in, the line's `parity` is its delta against the fp32 oracle)")
@@ -127,6 +138,33 @@ def max_deltas(got, want, nq, L):
     do = max(float((got[1][q][l].float().cpu() - want[1][q][l]).abs().max()) for q in range(nq) for l in range(L))
     mk = all(bool(torch.equal(got[2][q][l].cpu(), want[2][q][l])) for q in range(nq) for l in range(L))
     return dl, do, mk
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, videos):
+    """--dump-outputs: what the timed path handed its caller in the last timed step.  ``videos``: per video of the step, what
+    forward(..., eval=True) returns for it (logits, offsets, masks: per query, per level (1, n_l[, 2])).  Written as
+    logits (V, NQ, S), offsets (V, NQ, S, 2) and masks (V, NQ, S), float32, the levels concatenated along the point axis S.
+    Above 64 MB in all, the same fixed, seeded sample of the points is kept in every array and its indices go to points.npy."""
+    import numpy as np
+
+    def flat(part):
+        return torch.stack([torch.cat([x.reshape((-1,) + tuple(x.shape[2:])) for x in lv]) for lv in part]).float().cpu().numpy()
+
+    arrs = {name: np.stack([flat(v[i]) for v in videos]) for i, name in enumerate(('logits', 'offsets', 'masks'))}
+    S = arrs['logits'].shape[2]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES // (total // S + 8)
+        idx = np.sort(np.random.default_rng(0).choice(S, keep, replace=False))
+        arrs = {k: np.ascontiguousarray(a[:, :, idx]) for k, a in arrs.items()}
+        arrs['points'] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    return {'files': sorted(k + '.npy' for k in arrs), 'videos': len(videos), 'points': S, 'sampled_points': len(idx) if 'points' in arrs else None}
 
 
 class Marks:
@@ -215,6 +253,7 @@ def run_sharded(args, pkg, dist, rank, world, dev):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert model.numerics_status() & 1 == 0, 'f16x3 GEMM range overflow flagged'
+    dumped = dump_outputs(args.dump_outputs, [out]) if args.dump_outputs and rank == 0 else None
     for _ in range(min(args.steps, 5)):
         step(timed=True)
     torch.cuda.synchronize()
@@ -245,6 +284,8 @@ def run_sharded(args, pkg, dist, rank, world, dev):
                                        'tests/test_gpu_e2e.py::test_config4_unsharded_T65536_vs_oracle)',
                             'max_abs_logit': dl, 'max_abs_offset': do, 'masks_equal': mk}
         assert mk and dl < 2e-4 and do < 2e-4, f'sharded forward differs from the unsharded one: {dl} {do} {mk}'
+        if dumped:
+            result['dump_outputs'] = dumped
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.barrier()
@@ -379,10 +420,10 @@ def main():
     batch0 = [first] + lane_inputs(model, 2025 + 3 + rank)
 
     def step1():
-        """one forward on the current stream; returns the outputs of its FIRST video in forward()'s structure"""
+        """one forward on the current stream; returns, per video of the forward, what forward(..., eval=True) returns"""
         if args.batch > 1:
-            return model.forward_videos(batch0)[0]
-        return model(vid, shallow, vmask, texts, text_cls, tmasks, eval=True)
+            return model.forward_videos(batch0)
+        return [model(vid, shallow, vmask, texts, text_cls, tmasks, eval=True)]
 
     # A step = one batch of `--videos` x `--batch` different synthetic videos: `--videos` independent forwards (own model
     # instance = own workspace + HIP graph) on their own streams, each carrying `--batch` videos.
@@ -399,17 +440,18 @@ def main():
     torch.cuda.synchronize()
 
     def step():
+        """one step; returns the outputs of every video of the step, forward by forward (step1's structure)"""
         if not others:
             return step1()
         with torch.cuda.stream(stream0):
-            out0 = step1()
+            outs = step1()
         for mk, a, sk, bk in others:
             with torch.cuda.stream(sk):
                 if args.batch > 1:
-                    mk.forward_videos(bk)
+                    outs += mk.forward_videos(bk)
                 else:
-                    mk(*a, eval=True)
-        return out0
+                    outs.append(mk(*a, eval=True))
+        return outs
 
     # setup, not steps: the engine runs a new argument set eagerly once, captures its HIP graph on the second call and
     # replays from the third; a few more replays let the allocator and the clocks settle whatever --warmup is
@@ -452,7 +494,9 @@ def main():
     # the f16x3 GEMMs flag any accumulator that left the finite range (operands beyond the fp16 range): must be clean
     for mk in [model] + [o[0] for o in others]:
         assert mk.numerics_status() & 1 == 0, 'f16x3 GEMM range overflow flagged: the timed outputs are not valid'
-    timed_out = [[[x.clone() for x in lv] for lv in part] for part in out]      # first video of the LAST timed step (rank-local)
+    # outputs of the LAST timed step (rank-local), before anything else runs on the reused output buffers
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs and rank == 0 else None
+    timed_out = [[[x.clone() for x in lv] for lv in part] for part in out[0]] if args.full else None     # its first video
     n_lanes = 1 + len(others)
     n_videos = n_lanes * max(1, args.batch)
     clips_per_step = n_videos * vid_len * args.nq
@@ -481,7 +525,9 @@ def main():
                             if dist is not None else {'world_size': 1, 'backend': None})},
     }
 
-    if rank == 0:
+    if dumped:
+        result['dump_outputs'] = dumped
+    if rank == 0 and args.full:
         # ---- live per-kernel timing: the same steps again with every launch bracketed by HIP events
         lib.dcf_profile_enable(1)
         for _ in range(args.steps):
@@ -799,6 +845,7 @@ def main():
             chk['gpu_over_cpu'] = result['value'] / result['cpu_baseline']['value']
         if 'roofline' in result:
             result['roofline']['checks'] = chk
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.barrier()

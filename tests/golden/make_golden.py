@@ -11,7 +11,7 @@ Modules the reference imports at module level but never touches on the grounding
 replaced by inert stubs.
 
 Fixture families:  G1 ops.npz / ops64.npz, G2 gate.npz, G3 e2e_*.npz, G4 postproc.npz,
-G5 nms_kat.npz, G6 data_io.npz (feature files, annotations, text-CLS table through the reference's loaders),
+G5 nms_kat.npz (+ nms_kat_big.npz, nms_ref_random.npz: `make_golden.py nms_big` / `nms_random`), G6 data_io.npz (feature files, annotations, text-CLS table through the reference's loaders),
 G3 at bench scale: e2e_scale_c3.npz / e2e_scale_c4.npz (T = 16 384 / 65 536, outputs only; `make_golden.py scale`).
 """
 import importlib
@@ -802,6 +802,33 @@ def gen_nms_big(ext):
     save('nms_kat_big.npz', out)
 
 
+def gen_nms_random(ext):
+    """the extension's answers on the 40 random candidate sets test_nms_vs_compiled_reference_random draws (same generator, same
+    draws): NMS indices and, for soft-NMS methods 0 / 1 / 2, indices and dets"""
+    g = torch.Generator().manual_seed(99)
+    out, cases = {}, []
+    for trial in range(40):
+        n = int(torch.randint(1, 300, (1,), generator=g))
+        c = torch.rand(n, generator=g) * 100
+        ln = torch.rand(n, generator=g) * 30 + 0.1
+        segs = torch.stack((c - ln / 2, c + ln / 2), -1).contiguous()
+        scores = torch.rand(n, generator=g).contiguous()
+        if len(torch.unique(scores)) != n:
+            continue
+        thr = float(torch.rand(1, generator=g) * 0.8 + 0.05)
+        i = len(cases)
+        out[f'r{i}/segs'], out[f'r{i}/scores'] = segs, scores
+        out[f'r{i}/nms'] = ext.nms(segs, scores, iou_thresh=thr)
+        for method in (0, 1, 2):
+            dets = torch.zeros(n, 3)
+            idx = ext.softnms(segs, scores, dets, iou_thresh=thr, sigma=0.5, min_score=0.01, method=method)
+            out[f'r{i}/soft{method}/idx'] = idx
+            out[f'r{i}/soft{method}/dets'] = dets[:len(idx)]
+        cases.append(dict(trial=trial, n=n, iou_thresh=thr))
+    out['cases'] = cases
+    save('nms_ref_random.npz', out)
+
+
 # ------------------------------------------------------------------ G6: feature files / annotations / text-CLS table
 def write_data_tree(root, arrays):
     """materialise the synthetic dataset of data_io.npz under ``root`` (also used by tests/test_data_io.py)"""
@@ -917,5 +944,7 @@ if __name__ == '__main__':
         gen_nms(ext)
     if 'nms_big' in which:
         gen_nms_big(ext)
+    if 'nms_random' in which:
+        gen_nms_random(ext)
     if 'data_io' in which:
         gen_data_io()

@@ -302,31 +302,32 @@ def test_nms_known_answers_beyond_4096_candidates():
 
 
 def test_nms_vs_compiled_reference_random():
-    """When oracle/_ref holds the reference's own extension, fuzz the C oracle against it."""
+    """The C oracle against the reference's own extension on 40 random candidate sets: the extension's answers are stored in
+    tests/golden/nms_ref_random.npz (make_golden.py nms_random); when oracle/_ref holds the compiled extension, it is asked live too."""
     import importlib.util
     spec = importlib.util.spec_from_file_location('oracle_build_ref', os.path.join(ROOT, 'oracle', 'build_ref.py'))
     br = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(br)
     ext = br.load_module()
-    if ext is None:
-        pytest.skip('oracle/_ref not built')
-    g = torch.Generator().manual_seed(99)
-    for trial in range(40):
-        n = int(torch.randint(1, 300, (1,), generator=g))
-        c = torch.rand(n, generator=g) * 100
-        ln = torch.rand(n, generator=g) * 30 + 0.1
-        segs = torch.stack((c - ln / 2, c + ln / 2), -1).contiguous()
-        scores = torch.rand(n, generator=g).contiguous()
-        if len(torch.unique(scores)) != n:
-            continue
-        thr = float(torch.rand(1, generator=g) * 0.8 + 0.05)
-        assert torch.equal(nms_oracle.nms(segs, scores, thr), ext.nms(segs, scores, iou_thresh=thr))
+    g = Golden('nms_ref_random.npz')
+    cases = g.js('cases')
+    assert len(cases) >= 30
+    for i, c in enumerate(cases):
+        segs, scores, thr = g.t(f'r{i}/segs'), g.t(f'r{i}/scores'), c['iou_thresh']
+        keep = nms_oracle.nms(segs, scores, thr)
+        assert torch.equal(keep, g.t(f'r{i}/nms')), c
+        if ext is not None:
+            assert torch.equal(keep, ext.nms(segs, scores, iou_thresh=thr)), c
         for method in (0, 1, 2):
-            d1, d2 = torch.zeros(n, 3), torch.zeros(n, 3)
+            d1 = torch.zeros(len(segs), 3)
             i1 = nms_oracle.softnms(segs, scores, d1, thr, 0.5, 0.01, method)
-            i2 = ext.softnms(segs, scores, d2, iou_thresh=thr, sigma=0.5, min_score=0.01, method=method)
-            assert torch.equal(i1, i2)
-            assert torch.equal(d1[:len(i1)], d2[:len(i2)])
+            assert torch.equal(i1, g.t(f'r{i}/soft{method}/idx')), (c, method)
+            assert torch.equal(d1[:len(i1)], g.t(f'r{i}/soft{method}/dets')), (c, method)
+            if ext is not None:
+                d2 = torch.zeros(len(segs), 3)
+                i2 = ext.softnms(segs, scores, d2, iou_thresh=thr, sigma=0.5, min_score=0.01, method=method)
+                assert torch.equal(i1, i2)
+                assert torch.equal(d1[:len(i1)], d2[:len(i2)])
 
 
 @pytest.mark.parametrize('name', ['late', 'second', 'late_scat', 'early', 'early_single'])

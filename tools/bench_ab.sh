@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 V=${1:-base}; N=${2:-2}; shift; shift
 cd "$R" || exit 1
-mkdir -p gpurun_out
+OUT=$(mktemp -d)
 LIB="$R/cvpr2025-decafnet_amd/build/variants/$V/libdecafnet_hip.so"
 test -f "$LIB" || { echo "no variant $V"; exit 1; }
 show() {
@@ -25,6 +25,6 @@ print(f"{d['value'] / 1e6:7.3f} M clips/s  event ms {d.get('event_ms_per_step', 
 P
 }
 for i in $(seq "$N"); do
-  python3 bench.py --no-post --no-cpu-baseline > gpurun_out/ab_prod.json 2> gpurun_out/ab_prod.err; echo -n "product  "; show gpurun_out/ab_prod.json "$@"
-  DCF_LIB_PATH=$LIB python3 bench.py --no-post --no-cpu-baseline > gpurun_out/ab_var.json 2> gpurun_out/ab_var.err; echo -n "$V  "; show gpurun_out/ab_var.json "$@"
+  python3 bench.py --full --min-timed-s 2 --no-post --no-cpu-baseline > "$OUT/ab_prod.json" 2> "$OUT/ab_prod.err"; echo -n "product  "; show "$OUT/ab_prod.json" "$@"
+  DCF_LIB_PATH=$LIB python3 bench.py --full --min-timed-s 2 --no-post --no-cpu-baseline > "$OUT/ab_var.json" 2> "$OUT/ab_var.err"; echo -n "$V  "; show "$OUT/ab_var.json" "$@"
 done

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 VS=$1; N=${2:-2}; shift; shift
 cd "$R" || exit 1
-mkdir -p gpurun_out
+OUT=$(mktemp -d)
 show() {
 python3 - "$1" "${@:2}" <<'P'
 import json, sys
@@ -21,10 +21,10 @@ print(f"{d['value'] / 1e6:7.3f} M clips/s  event ms {d.get('event_ms_per_step', 
 P
 }
 for i in $(seq "$N"); do
-  python3 bench.py --no-post --no-cpu-baseline > gpurun_out/ab_prod.json 2> gpurun_out/ab_prod.err; echo -n "product  "; show gpurun_out/ab_prod.json "$@"
+  python3 bench.py --full --min-timed-s 2 --no-post --no-cpu-baseline > "$OUT/ab_prod.json" 2> "$OUT/ab_prod.err"; echo -n "product  "; show "$OUT/ab_prod.json" "$@"
   for V in $VS; do
     LIB="$R/cvpr2025-decafnet_amd/build/variants/$V/libdecafnet_hip.so"
     test -f "$LIB" || { echo "no variant $V"; continue; }
-    DCF_LIB_PATH=$LIB python3 bench.py --no-post --no-cpu-baseline > gpurun_out/ab_$V.json 2> gpurun_out/ab_$V.err; echo -n "$V  "; show gpurun_out/ab_$V.json "$@"
+    DCF_LIB_PATH=$LIB python3 bench.py --full --min-timed-s 2 --no-post --no-cpu-baseline > "$OUT/ab_$V.json" 2> "$OUT/ab_$V.err"; echo -n "$V  "; show "$OUT/ab_$V.json" "$@"
   done
 done

@@ -1,6 +1,7 @@
 #!/bin/bash
 # everything profiles/ holds for a round, on the GPU box (via gpurun): bash tools/round_profiles.sh <tag>
-# (writes gpurun_out/<tag>_*; copy what is to be kept into profiles/ afterwards)
+# (the bench JSON lines and the single-stream statistics go to profiles/<tag>_*, the other tools' results to their own output folder:
+# copy what is to be kept into profiles/ afterwards)
 tag=${1:-r03}
 R=$GRAFT_REPO_ROOT
 cd $R
@@ -11,9 +12,9 @@ echo "pmc traffic done"
 bash tools/run_trace.sh $tag --videos 1 --batch 1 --min-timed-s 0 && cp gpurun_out/step_$tag.txt gpurun_out/${tag}_step_timeline.txt
 [ -f gpurun_out/${tag}_dispatches.json ] && cp gpurun_out/${tag}_dispatches.json profiles/${tag}_dispatches.json
 echo "timeline done"
-python3 bench.py --steps 10 --warmup 3 > gpurun_out/${tag}_bench_n1.json 2> gpurun_out/${tag}_bench_n1.err
-python3 bench.py --steps 10 --warmup 3 --nq 8 --no-cpu-baseline > gpurun_out/${tag}_bench_n1_nq8.json 2>/dev/null
-python3 bench.py --steps 10 --warmup 3 --videos 1 --batch 1 --no-cpu-baseline > gpurun_out/${tag}_bench_n1_one_video.json 2>/dev/null
+python3 bench.py --full --min-timed-s 2 --steps 10 --warmup 3 > profiles/${tag}_bench_n1.json 2> /tmp/${tag}_bench_n1.err
+python3 bench.py --full --min-timed-s 2 --steps 10 --warmup 3 --nq 8 --no-cpu-baseline > profiles/${tag}_bench_n1_nq8.json 2>/dev/null
+python3 bench.py --full --min-timed-s 2 --steps 10 --warmup 3 --videos 1 --batch 1 --no-cpu-baseline > profiles/${tag}_bench_n1_one_video.json 2>/dev/null
 echo "bench done"
 # single-stream kernel statistics: reproduce roofline.achieved from rocprofv3 (tools/solo_check.py)
 bash tools/solo_stats.sh $tag
