@@ -49,6 +49,8 @@ SIGNATURES = {
     'dcf_forward_train_videos': (i32, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), i64, ctypes.POINTER(i32),
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(vp),
                                        c_f32p, c_f32p, c_f32p, c_u8p, vp]),
+    'dcf_model_set_dropout': (i32, [vp, f32, f32, f32, f32, f32, i64]),
+    'dcf_debug_dropout_keep': (i32, [i64, i32, i64, i64, f32, c_u8p, vp]),
     'dcf_sigmoid_focal_loss': (i32, [c_f32p, c_f32p, c_u8p, i64, f32, f32, i32, c_f32p, c_f32p, c_i32p, vp]),
     'dcf_ctr_iou_loss': (i32, [c_f32p, c_f32p, c_u8p, i64, i32, f32, c_f32p, c_f32p, c_i32p, vp]),
     'dcf_forward_eval_gated': (i32, [vp, c_f32p, c_f32p, c_u8p, i64, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),

@@ -27,6 +27,7 @@
 #include "attn.h"
 #include "common.h"
 #include "dec_chain.h"
+#include "dropout.h"
 #include "enc_chain.h"
 #include "ffn_chain.h"
 #include "gemm.h"
@@ -295,6 +296,16 @@ struct dcf_model {
   float* dbg_fused = nullptr;
   int64_t dbg_cap = 0;                        // capacity (floats) of the armed tap destinations
   bool keep_debug = false;
+  // dcf_model_set_dropout: the training forward's dropout / drop-path (dropout.h).  `drop` points at `drop_state` only while
+  // dcf_forward_train_videos runs with a rate above 0; every other entry point sees nullptr and its launch sequence of before.
+  struct DropState {
+    float p[5] = {0.f, 0.f, 0.f, 0.f, 0.f};     // vid proj, vid path, fusion proj, fusion path, refine (DROP_R_*)
+    float scale[5] = {1.f, 1.f, 1.f, 1.f, 1.f}; // 1.0f / (1.0f - p), fp32
+    uint64_t seed = 0;
+    bool active = false;
+    int b0 = 0;                                // first (video, query) row of the chunk being run
+  } drop_state;
+  DropState* drop = nullptr;
 };
 
 namespace dcf {
@@ -1326,6 +1337,108 @@ static int run_fusion(dcf_model* m, Buffers& b, float* X, int64_t ldx, int B, in
   return 0;
 }
 
+// ---- the training forward with dropout (dcf_model_set_dropout; contract in dropout.h / include/decafnet_hip.h).  Every site's
+// tensor is materialised: the unfused kernel sequence of run_encoder / run_fusion, the dropout kernels between them.
+enum { DROP_R_VPROJ = 0, DROP_R_VPATH, DROP_R_FPROJ, DROP_R_FPATH, DROP_R_REFINE };
+static DropSite drop_at(const dcf_model* m, int rate, uint32_t site) {
+  DropSite d;
+  d.site = site; d.p = m->drop->p[rate]; d.scale = m->drop->scale[rate];
+  return d;
+}
+
+// TransformerEncoder.forward (blocks.py:578-591) with proj_drop (sub 0), the FFN's two dropouts (1, 2) and both drop-paths (3, 4)
+// of site group / layer `site0`; arguments as run_encoder.  Dropout tensors are (B', E / 4E, T_in / stride).
+static int run_encoder_drop(dcf_model* m, const EncW& w, Buffers& b, const float* Xin, int64_t ldx, const uint8_t* mask_in,
+                            const uint8_t* mask_out, int B, int T_in, int stride, float* Xout, int64_t ldo, uint32_t site0,
+                            hipStream_t st) {
+  const dcf_config& c = m->cfg;
+  const int E = c.E, To = T_in / stride, rows = B * To;
+  const auto& d = *m->drop;
+  EncPreArgs ep{};
+  ep.X = Xin; ep.ldx = ldx; ep.mask_in = mask_in; ep.ln_w = w.ln_attn_w; ep.ln_b = w.ln_attn_b;
+  ep.dw_q = w.dw_q; ep.dw_k = w.dw_k; ep.dw_v = w.dw_v;
+  ep.qn_w = w.qn_w; ep.qn_b = w.qn_b; ep.kn_w = w.kn_w; ep.kn_b = w.kn_b; ep.vn_w = w.vn_w; ep.vn_b = w.vn_b;
+  ep.Qc = b.R[0]; ep.Kc = b.R[1]; ep.Vc = b.R[2]; ep.Skip = stride == 2 ? b.R[3] : nullptr;
+  ep.B = B; ep.T_in = T_in; ep.C = E;
+  TRY(launch_enc_pre(ep, stride, st));
+  GemmArgs g3[3] = {gemm(b.R[0], E, w.wq, w.bq, b.R[4], E, rows, E, E), gemm(b.R[1], E, w.wk, w.bk, b.R[5], E, rows, E, E),
+                    gemm(b.R[2], E, w.wv, w.bv, b.R[6], E, rows, E, E)};
+  TRY(run_gemm(m, g3, 3, A_ROWS, st));
+  if (c.win > 0) {
+    LocalAttnArgs la{b.R[4], b.R[5], b.R[6], mask_out, b.R[0], B, To, E, c.vid_heads, c.win};
+    TRY(launch_local_attn(la, st));
+  } else {
+    GlobalAttnArgs ga{b.R[4], b.R[5], b.R[6], mask_out, b.R[0], B, To, E, c.vid_heads};
+    TRY(launch_global_attn(ga, st));
+  }
+  // h = proj(ctx) -> R4;  x' = skip * mask + drop_path_attn(ls_attn * proj_drop(h))          (blocks.py:392, :586)
+  GemmArgs gp = gemm(b.R[0], E, w.wp, w.bp, b.R[4], E, rows, E, E);
+  TRY(run_gemm(m, &gp, 1, A_ROWS, st));
+  DropResArgs ra{};
+  ra.out = b.R[1]; ra.ldo = E;
+  if (stride == 2) { ra.R = b.R[3]; ra.ldr = E; } else { ra.R = Xin; ra.ldr = ldx; }
+  ra.H = b.R[4]; ra.ldh = E; ra.rowmask = mask_out; ra.res_mask = 1; ra.out_mask = 0; ra.ls = w.ls_attn;
+  ra.rows = rows; ra.C = E; ra.T = To; ra.b0 = d.b0; ra.seed = d.seed;
+  ra.drop = drop_at(m, DROP_R_VPROJ, site0 | DROP_PROJ); ra.path = drop_at(m, DROP_R_VPATH, site0 | DROP_PATH_ATTN);
+  TRY(launch_drop_residual(ra, st));
+  // FFN: dropout(gelu(fc(ln_ffn(x')))) -> proj -> R4;  out = x' + drop_path_ffn(ls_ffn * dropout(.) * mask)   (blocks.py:535-538, :589-590)
+  LnArgs ln{}; ln.X = b.R[1]; ln.ldx = E; ln.Y = b.R[2]; ln.ldy = E; ln.w = w.ln_ffn_w; ln.b = w.ln_ffn_b; ln.rows = rows; ln.C = E;
+  TRY(launch_ln(ln, st));
+  GemmArgs gf = gemm(b.R[2], E, w.fc_w, w.fc_b, b.HID, 4 * E, rows, 4 * E, E);
+  gf.flags = G_GELU;
+  TRY(run_gemm(m, &gf, 1, A_ROWS, st));
+  TRY(launch_dropout(b.HID, 4 * E, rows, 4 * E, To, d.b0, d.seed, drop_at(m, DROP_R_VPROJ, site0 | DROP_FFN_HID), st));
+  GemmArgs go = gemm(b.HID, 4 * E, w.pj_w, w.pj_b, b.R[4], E, rows, E, 4 * E);
+  TRY(run_gemm(m, &go, 1, A_ROWS, st));
+  ra.out = Xout; ra.ldo = ldo; ra.R = b.R[1]; ra.ldr = E; ra.res_mask = 0; ra.out_mask = 1; ra.ls = w.ls_ffn;
+  ra.drop = drop_at(m, DROP_R_VPROJ, site0 | DROP_FFN_OUT); ra.path = drop_at(m, DROP_R_VPATH, site0 | DROP_PATH_FFN);
+  return launch_drop_residual(ra, st);
+}
+
+// XAttNFusion._forward (fusion.py:56-66) on one level of B sequences of T rows with the decoders' proj_drop on the (B', 2E, T)
+// scale / shift tensor (sub 0), the FFN's two dropouts (1, 2) and drop_path_ffn (4); X updated in place, ln_out -> out
+static int run_fusion_drop(dcf_model* m, Buffers& b, float* X, int64_t ldx, int B, int T, const uint8_t* mask, const TextMeta* dm,
+                           int Lk, float* out, int64_t ld_out, hipStream_t st) {
+  const dcf_config& c = m->cfg;
+  const int E = c.E, rows = B * T;
+  const auto& d = *m->drop;
+  for (size_t li = 0; li < m->dec.size(); ++li) {
+    const DecW& w = m->dec[li];
+    const uint32_t site0 = drop_site(DROP_G_FUSION, (uint32_t)li, 0);
+    TextLnArgs tl{*dm, b.kvn, b.kvmask, w.ln_kv_w, w.ln_kv_b, Lk, c.TE};
+    TRY(launch_text_ln(tl, B, st));
+    GemmArgs gkv[2] = {gemm(b.kvn, c.TE, w.wk, w.bk, b.Kt, E, B * Lk, E, c.TE), gemm(b.kvn, c.TE, w.wv, w.bv, b.Vt, E, B * Lk, E, c.TE)};
+    TRY(run_gemm(m, gkv, 2, A_ROWS, st));
+    DecPreArgs dp{X, ldx, mask, w.ln_q_w, w.ln_q_b, w.dw, w.qn_w, w.qn_b, b.R[0], b.R[1], B, T, E};
+    dp.nbr = nullptr;
+    dp.affine = c.xattn_affine;
+    TRY(launch_dec_pre(dp, st));
+    GemmArgs gq = gemm(b.R[0], E, w.wq, w.bq, b.R[2], E, rows, E, E);
+    TRY(run_gemm(m, &gq, 1, A_ROWS, st));
+    XAttnArgs xa{b.R[2], b.Kt, b.Vt, b.kvmask, b.R[0], B, T, Lk, E, c.fusion_heads, m->status, c.attn_mode == 1};
+    TRY(launch_xattn(xa, st));
+    // (scale | shift) = proj_drop(proj(ctx)) -> H2;  q3 = adaln(q) * scale + shift -> R2, ln_ffn(q3) -> R0   (blocks.py:392, :643-646)
+    GemmArgs gh = gemm(b.R[0], E, w.wp, w.bp, b.H2, 2 * E, rows, 2 * E, E);
+    TRY(run_gemm(m, &gh, 1, A_ROWS, st));
+    TRY(launch_dropout(b.H2, 2 * E, rows, 2 * E, T, d.b0, d.seed, drop_at(m, DROP_R_FPROJ, site0 | DROP_PROJ), st));
+    TRY(launch_dec_mid(b.R[1], b.H2, w.ln_ffn_w, w.ln_ffn_b, b.R[2], b.R[0], rows, E, st));
+    GemmArgs gf = gemm(b.R[0], E, w.fc_w, w.fc_b, b.HID, 4 * E, rows, 4 * E, E);
+    gf.flags = G_GELU;
+    TRY(run_gemm(m, &gf, 1, A_ROWS, st));
+    TRY(launch_dropout(b.HID, 4 * E, rows, 4 * E, T, d.b0, d.seed, drop_at(m, DROP_R_FPROJ, site0 | DROP_FFN_HID), st));
+    GemmArgs go = gemm(b.HID, 4 * E, w.pj_w, w.pj_b, b.R[1], E, rows, E, 4 * E);
+    TRY(run_gemm(m, &go, 1, A_ROWS, st));
+    // q = q3 + drop_path_ffn(ls_ffn * dropout(proj(.)) * mask)                                              (blocks.py:648-649)
+    DropResArgs ra{};
+    ra.out = X; ra.ldo = ldx; ra.R = b.R[2]; ra.ldr = E; ra.H = b.R[1]; ra.ldh = E; ra.rowmask = mask; ra.res_mask = 0; ra.out_mask = 1;
+    ra.ls = w.ls_ffn; ra.rows = rows; ra.C = E; ra.T = T; ra.b0 = d.b0; ra.seed = d.seed;
+    ra.drop = drop_at(m, DROP_R_FPROJ, site0 | DROP_FFN_OUT); ra.path = drop_at(m, DROP_R_FPATH, site0 | DROP_PATH_FFN);
+    TRY(launch_drop_residual(ra, st));
+  }
+  LnArgs ln{}; ln.X = X; ln.ldx = ldx; ln.Y = out; ln.ldy = ld_out; ln.w = m->fus_out_w; ln.b = m->fus_out_b; ln.rows = rows; ln.C = E;
+  return launch_ln(ln, st);
+}
+
 // The videos of one forward: all padded to the same T, video v with nq[v] queries; the queries of all videos are one flat
 // list (text / outputs in video order).  One video is the reference's call (model.py:496 asserts bs == 1); several are
 // the throughput extension dcf_forward_eval_videos: after vid_map every kernel works on rows [query][t] and does not
@@ -1712,6 +1825,7 @@ static int forward(dcf_model* m, const VideoSet& vs, int T0, int nq,
     const LevelTable& lt = pl->lt;
     const int rows0 = B * T0, rowsP = B * Tp, rowsAll = B * S;
     uint8_t* mask_in = sv > 1 ? b.mask_pre : b.mask_all;      // validity of the T0 input clips (gate stage)
+    if (m->drop) m->drop->b0 = q0;
     unsigned long long vmap = 0;           // video of batch element i in nibble i (B <= 16 with several videos, <= 16 videos)
     for (int i = 0; i < B && i < 16; ++i) vmap |= (unsigned long long)video_of[q0 + i] << (4 * i);
 
@@ -1757,7 +1871,8 @@ static int forward(dcf_model* m, const VideoSet& vs, int T0, int nq,
     bool fused_as_stats = false;                  // fusion.ln_out carried into vid_net.embd_fc as row statistics
     if (c.model_kind != 1) {
       const bool tap = m->keep_debug && m->dbg_fused;    // the `fused` debug tap wants the normalised rows themselves
-      TRY(run_fusion(m, b, b.X, E, B, T0, nullptr, mask0, nullptr, dm, Lk, b.R[0], E, st, tap ? nullptr : &fused_as_stats));
+      if (m->drop) TRY(run_fusion_drop(m, b, b.X, E, B, T0, mask0, dm, Lk, b.R[0], E, st));
+      else TRY(run_fusion(m, b, b.X, E, B, T0, nullptr, mask0, nullptr, dm, Lk, b.R[0], E, st, tap ? nullptr : &fused_as_stats));
       if (tap) DCF_HIP(hipMemcpyAsync(m->dbg_fused, b.R[0], (size_t)rows0 * E * 4, hipMemcpyDeviceToDevice, st));
     }
 
@@ -1846,7 +1961,8 @@ static int forward(dcf_model* m, const VideoSet& vs, int T0, int nq,
       }
       for (size_t i = 0; i < m->stem.size(); ++i) {
         // stem layers work in place at level 0: out -> R[3] is free for stride 1, then copy back via swap of roles
-        TRY(run_encoder(m, m->stem[i], b, b.X, E, maskP, maskP, B, Tp, 1, b.R[3], E, st));
+        if (m->drop) TRY(run_encoder_drop(m, m->stem[i], b, b.X, E, maskP, maskP, B, Tp, 1, b.R[3], E, drop_site(DROP_G_STEM, (uint32_t)i, 0), st));
+        else TRY(run_encoder(m, m->stem[i], b, b.X, E, maskP, maskP, B, Tp, 1, b.R[3], E, st));
         DCF_HIP(hipMemcpyAsync(b.X, b.R[3], (size_t)rowsP * E * 4, hipMemcpyDeviceToDevice, st));
       }
       const int ldf = E + TCN_HID;
@@ -1858,6 +1974,8 @@ static int forward(dcf_model* m, const VideoSet& vs, int T0, int nq,
         const uint8_t* mo = b.mask_all + lt.start[l];
         float* xo = b.F + (int64_t)lt.start[l] * ldf;
         if (c.pool_only) TRY(launch_dwconv3(xin, ldx, mi, m->pool_w[l], xo, ldf, B, l > 0 ? lt.T[l - 1] : Tp, stride, E, st));   // video_net.py:107-109
+        else if (m->drop) TRY(run_encoder_drop(m, m->branch[l], b, xin, ldx, mi, mo, B, l > 0 ? lt.T[l - 1] : Tp, stride, xo, ldf,
+                                               drop_site(DROP_G_BRANCH, (uint32_t)l, 0), st));
         else TRY(run_encoder(m, m->branch[l], b, xin, ldx, mi, mo, B, l > 0 ? lt.T[l - 1] : Tp, stride, xo, ldf, st));
         xin = xo; ldx = ldf;
       }
@@ -1895,6 +2013,9 @@ static int forward(dcf_model* m, const VideoSet& vs, int T0, int nq,
       ra.bufA = b.tcnA; ra.bufB = b.tcnB; ra.F = b.F; ra.ldf = E + TCN_HID; ra.E = E;
       ra.B = B; ra.T0 = Tp; ra.n_levels = L; ra.n_layers = L;
       ra.f16 = m->gemm_terms == GEMM_F16X3; ra.status = m->status;
+      if (m->drop) {
+        ra.drop_seed = m->drop->seed; ra.drop_p = m->drop->p[DROP_R_REFINE]; ra.drop_scale = m->drop->scale[DROP_R_REFINE]; ra.drop_b0 = q0;
+      }
       TRY(launch_refine(ra, lt, st));
     }
     TRY(run_head_pair(m, m->cls2, m->reg, b, *pl, E + TCN_HID, 1, 0, logits_out + (int64_t)q0 * S, 2, 1,
@@ -1988,7 +2109,7 @@ static int text_encode(dcf_model* m, const float* tokens, const uint8_t* token_m
 extern "C" {
 
 const char* dcf_last_error(void) { return dcf::g_err.c_str(); }
-int dcf_abi_version(void) { return 10; }
+int dcf_abi_version(void) { return 11; }
 
 int dcf_model_create(const dcf_config* cfg, dcf_model** out) {
   DCF_CHECK(cfg && out, "dcf_model_create: null argument");
@@ -2107,7 +2228,8 @@ static int forward_maybe_graph(dcf_model* m, const VideoSet& vs, int T0, int nq,
   // jitter; ONE video per call (~100 launches of 5 - 40 us) is 5 % faster launched eagerly (1.75 vs 1.84 ms: a graph node
   // costs ~0.9 us more than an in-order launch, and the host needs ~0.5 ms to issue the forward the GPU takes 1.75 ms for).
   const bool want = m->graph_mode == 1 || (m->graph_mode == 0 && (long long)nq * T0 >= 65536);
-  const bool eligible = want && !no_graph && !g_prof_on && !m->keep_debug && nq > 0;
+  // (dropout: eager, the seed is a kernel argument that a captured graph would bake in)
+  const bool eligible = want && !no_graph && !g_prof_on && !m->keep_debug && nq > 0 && !m->drop;
   if (!eligible) {
     m->last_launch = 0;
     return forward(m, vs, T0, nq, text, text_mask, text_len, gate, lo, oo, mo, st);
@@ -2241,8 +2363,30 @@ int dcf_forward_train_videos(dcf_model* m, int32_t nvid, const float* const* vid
     vs.vid[v] = vid[v]; vs.shallow[v] = shallow_vid[v]; vs.mask[v] = vid_mask[v]; vs.text_cls[v] = text_cls[v]; vs.nq[v] = nq_per_video[v];
     nq += nq_per_video[v];
   }
-  return dcf::forward_maybe_graph(m, vs, (int)T, nq, text, text_mask, text_len, nullptr, logits2_out, offsets_out, masks_out,
-                                  (hipStream_t)stream);
+  if (m->drop_state.active) {
+    DCF_CHECK(!m->cfg.second_fusion, "dcf_forward_train_videos: dropout with the second fusion is not implemented");
+    m->drop = &m->drop_state;
+  }
+  const int rc = dcf::forward_maybe_graph(m, vs, (int)T, nq, text, text_mask, text_len, nullptr, logits2_out, offsets_out, masks_out,
+                                          (hipStream_t)stream);
+  m->drop = nullptr;
+  return rc;
+}
+
+int dcf_model_set_dropout(dcf_model* m, float vid_proj_p, float vid_path_p, float fus_proj_p, float fus_path_p, float refine_p,
+                          int64_t seed) {
+  DCF_CHECK(m, "dcf_model_set_dropout: null model");
+  const float p[5] = {vid_proj_p, vid_path_p, fus_proj_p, fus_path_p, refine_p};
+  for (int i = 0; i < 5; ++i) DCF_CHECK(p[i] >= 0.f && p[i] < 1.f, "dcf_model_set_dropout: rate %d = %g outside [0, 1)", i, (double)p[i]);
+  auto& d = m->drop_state;
+  d.active = false;
+  for (int i = 0; i < 5; ++i) {
+    d.p[i] = p[i];
+    d.scale[i] = 1.0f / (1.0f - p[i]);
+    d.active = d.active || p[i] > 0.f;
+  }
+  d.seed = (uint64_t)seed;
+  return 0;
 }
 
 int dcf_forward_eval_gated(dcf_model* m, const float* vid, const float* shallow_vid, const uint8_t* vid_mask, int64_t T,

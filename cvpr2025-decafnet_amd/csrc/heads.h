@@ -57,6 +57,9 @@ struct RefineArgs {
   unsigned* status;                   // f16: sticky numerics word (bit 0 raised on a non-finite intermediate), may be null
   int stack_layers;                   // f16 with fragment images: how many leading TCN layers run as ONE launch over LDS windows (k_tcn_stack):
                                       // -1 = default (5: dilations 1 .. 16), 0 / 1 = none, at most 5 and never the last layer
+  // the training forward's dropout of every layer (tcn.py:27; dropout.h): drop_p > 0 runs the layers one by one with it, on the
+  // (B', 32, T0) tensor whose first sequence is drop_b0.  drop_p = 0 (value-initialised): no dropout, the kernels of before
+  uint64_t drop_seed; float drop_p, drop_scale; int drop_b0;
 };
 int launch_refine(const RefineArgs& a, const LevelTable& host_lt, hipStream_t st);
 // masked max-pool (k3, s2) of the 32 refined channels (columns [E, E + 32) of F) from the rows of one level to the next

@@ -4,6 +4,7 @@
 // (k_tcn_layer_mfma); the fp32 vector-ALU layer (k_tcn_layer) serves the other arithmetic modes.
 #include "common.h"
 #include "heads.h"
+#include "dropout.h"
 
 namespace dcf {
 
@@ -417,11 +418,15 @@ __device__ __forceinline__ void load_row32(const float* __restrict__ src, float 
 // 96 inputs of a row are parked in an LDS column so the reduction loops stay ROLLED (fully unrolled the compiler
 // hoists every weight read and spills; scalar s_loads were latency bound).  Summation order per output is the
 // same as a plain loop over (tap, channel), LayerNorm statistics are taken over channels 0..31 in order.
+// DROP: the training forward's dropout on the conv_1x1 output (tcn.py:27), element (b0 + r / T0, channel, r % T0) of the
+// (B', 32, T0) tensor (dropout.h)
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void k_tcn_layer(const float* __restrict__ X, float* __restrict__ Y,
                                                     const float* __restrict__ wd, const float* __restrict__ bd,
                                                     const float* __restrict__ wp, const float* __restrict__ bp,
                                                     const float* __restrict__ lnw, const float* __restrict__ lnb,
-                                                    const uint8_t* __restrict__ mask, int B, int T0, int dil) {
+                                                    const uint8_t* __restrict__ mask, int B, int T0, int dil,
+                                                    uint64_t dseed = 0, DropSite dsite = DropSite{}, int b0 = 0) {
   __shared__ f32x4 s_wd[3 * TCN_HID * TCN_HID / 4];
   __shared__ f32x4 s_wp[TCN_HID * TCN_HID / 4];
   __shared__ float s_x[3 * TCN_HID][64];
@@ -471,6 +476,12 @@ __global__ __launch_bounds__(256) void k_tcn_layer(const float* __restrict__ X, 
     o[4] += w1.x * hv; o[5] += w1.y * hv; o[6] += w1.z * hv; o[7] += w1.w * hv;
   }
   const float m = (live && mask[r]) ? 1.f : 0.f;
+  if constexpr (DROP) {
+    const int64_t bg = (int64_t)b0 + (live ? r / T0 : 0);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      o[c] = drop_keep(dseed, dsite.site, (uint64_t)((bg * TCN_HID + c0 + c) * T0 + t), dsite.p) ? o[c] * dsite.scale : 0.f;
+  }
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     o[c] = (s_x[TCN_HID + c0 + c][lane] + o[c]) * m;       // residual = centre tap
@@ -579,14 +590,16 @@ int launch_tcn_frag_image(const float* wd, const float* wp, const float* wo, uns
 }
 
 // frag != nullptr: the layer's fragment image (launch_tcn_frag_image); otherwise the workgroup builds the fragments itself
-template <bool LAST>
+// DROP: the dropout of the conv_1x1 output, as k_tcn_layer<true>
+template <bool LAST, bool DROP = false>
 __global__ __launch_bounds__(256) void k_tcn_layer_mfma(const float* __restrict__ X, float* __restrict__ Y, const h16x8* __restrict__ frag,
                                                          const float* __restrict__ wd, const float* __restrict__ bd,
                                                          const float* __restrict__ wp, const float* __restrict__ bp,
                                                          const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                          const uint8_t* __restrict__ mask, int B, int T0, int dil, int tiles_per_wave,
                                                          const float* __restrict__ wo, const float* __restrict__ bo,
-                                                         float* __restrict__ F, int64_t ldf, int E, unsigned* __restrict__ status) {
+                                                         float* __restrict__ F, int64_t ldf, int E, unsigned* __restrict__ status,
+                                                         uint64_t dseed = 0, DropSite dsite = DropSite{}, int b0 = 0) {
   const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wave = blockIdx.x * 4 + wv;
@@ -691,8 +704,12 @@ __global__ __launch_bounds__(256) void k_tcn_layer_mfma(const float* __restrict_
     float o[16], sum = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const float v = acc2[e] * TCN_UNSCALE + bp4[e >> 2][e & 3];
+      float v = acc2[e] * TCN_UNSCALE + bp4[e >> 2][e & 3];
       bad |= !(__builtin_fabsf(v) <= 3.4028234664e38f);
+      if constexpr (DROP) {                              // accumulator element e = channel 8 (e >> 2) + 4 h + (e & 3)
+        const int64_t ch = 8 * (e >> 2) + 4 * h + (e & 3), bg = (int64_t)b0 + (live ? r / T0 : 0);
+        v = drop_keep(dseed, dsite.site, (uint64_t)((bg * TCN_HID + ch) * T0 + t), dsite.p) ? v * dsite.scale : 0.f;
+      }
       o[e] = (res[e >> 2][e & 3] + v) * m;
       sum += o[e];
     }
@@ -1067,7 +1084,7 @@ int launch_refine(const RefineArgs& a, const LevelTable& lt, hipStream_t st) {
     int nl = a.stack_layers < 0 ? 5 : a.stack_layers;
     if (nl > TS_MAXL) nl = TS_MAXL;
     if (nl > a.n_layers - 1) nl = a.n_layers - 1;        // (the last layer carries conv_out)
-    bool have = a.f16 && nl >= 2 && a.T0 >= 1;
+    bool have = a.f16 && nl >= 2 && a.T0 >= 1 && !(a.drop_p > 0.f);     // (dropout: layer by layer, k_tcn_stack has none)
     for (int i = 0; i < nl && have; ++i) have = fimg(i) != nullptr;
     if (have) {
       TcnStackArgs sa{};
@@ -1087,20 +1104,39 @@ int launch_refine(const RefineArgs& a, const LevelTable& lt, hipStream_t st) {
   }
   for (int i = first; i < a.n_layers; ++i) {
     DCF_CHECK(a.host_w_dil && a.host_w_dil[i], "refine: missing TCN layer %d", i);
+    if (a.drop_p > 0.f) {                                // the training forward's dropout (site refine.layers[i], tcn.py:27)
+      DropSite ds;
+      ds.site = drop_site(DROP_G_REFINE, (uint32_t)i, DROP_TCN); ds.p = a.drop_p; ds.scale = a.drop_scale;
+      if (a.f16 && i + 1 < a.n_layers) {
+        hipLaunchKernelGGL((k_tcn_layer_mfma<false, true>), gm, dim3(256), 0, st, (const float*)cur, nxt, fimg(i), a.host_w_dil[i], a.host_b_dil[i],
+                           a.host_w_pw[i], a.host_b_pw[i], a.host_ln_w[i], a.host_ln_b[i], a.mask_all, a.B, a.T0, 1 << i, tpw,
+                           (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (int64_t)0, 0, a.status, a.drop_seed, ds, a.drop_b0);
+      } else if (a.f16) {
+        hipLaunchKernelGGL((k_tcn_layer_mfma<true, true>), gm, dim3(256), 0, st, (const float*)cur, nxt, fimg(i), a.host_w_dil[i], a.host_b_dil[i],
+                           a.host_w_pw[i], a.host_b_pw[i], a.host_ln_w[i], a.host_ln_b[i], a.mask_all, a.B, a.T0, 1 << i, tpw,
+                           a.w_out, a.b_out, a.F, a.ldf, a.E, a.status, a.drop_seed, ds, a.drop_b0);
+        out_done = true;
+      } else {
+        hipLaunchKernelGGL(k_tcn_layer<true>, g64, dim3(256), 0, st, (const float*)cur, nxt, a.host_w_dil[i], a.host_b_dil[i], a.host_w_pw[i],
+                           a.host_b_pw[i], a.host_ln_w[i], a.host_ln_b[i], a.mask_all, a.B, a.T0, 1 << i, a.drop_seed, ds, a.drop_b0);
+      }
+      float* t = cur; cur = nxt; nxt = t;
+      continue;
+    }
     if (a.f16) {
       if (i + 1 < a.n_layers) {
-        hipLaunchKernelGGL(k_tcn_layer_mfma<false>, gm, dim3(256), 0, st, (const float*)cur, nxt, fimg(i), a.host_w_dil[i], a.host_b_dil[i],
+        hipLaunchKernelGGL((k_tcn_layer_mfma<false, false>), gm, dim3(256), 0, st, (const float*)cur, nxt, fimg(i), a.host_w_dil[i], a.host_b_dil[i],
                            a.host_w_pw[i], a.host_b_pw[i], a.host_ln_w[i], a.host_ln_b[i], a.mask_all, a.B, a.T0, 1 << i, tpw,
-                           (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (int64_t)0, 0, a.status);
+                           (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (int64_t)0, 0, a.status, (uint64_t)0, DropSite{}, 0);
       } else {
-        hipLaunchKernelGGL(k_tcn_layer_mfma<true>, gm, dim3(256), 0, st, (const float*)cur, nxt, fimg(i), a.host_w_dil[i], a.host_b_dil[i],
+        hipLaunchKernelGGL((k_tcn_layer_mfma<true, false>), gm, dim3(256), 0, st, (const float*)cur, nxt, fimg(i), a.host_w_dil[i], a.host_b_dil[i],
                            a.host_w_pw[i], a.host_b_pw[i], a.host_ln_w[i], a.host_ln_b[i], a.mask_all, a.B, a.T0, 1 << i, tpw,
-                           a.w_out, a.b_out, a.F, a.ldf, a.E, a.status);
+                           a.w_out, a.b_out, a.F, a.ldf, a.E, a.status, (uint64_t)0, DropSite{}, 0);
         out_done = true;
       }
     } else {
-      hipLaunchKernelGGL(k_tcn_layer, g64, dim3(256), 0, st, (const float*)cur, nxt, a.host_w_dil[i], a.host_b_dil[i], a.host_w_pw[i],
-                         a.host_b_pw[i], a.host_ln_w[i], a.host_ln_b[i], a.mask_all, a.B, a.T0, 1 << i);
+      hipLaunchKernelGGL(k_tcn_layer<false>, g64, dim3(256), 0, st, (const float*)cur, nxt, a.host_w_dil[i], a.host_b_dil[i], a.host_w_pw[i],
+                         a.host_b_pw[i], a.host_ln_w[i], a.host_ln_b[i], a.mask_all, a.B, a.T0, 1 << i, (uint64_t)0, DropSite{}, 0);
     }
     float* t = cur; cur = nxt; nxt = t;
   }

@@ -453,6 +453,8 @@ class PtTransformerEarlyFusionIterative(nn.Module):
     """
 
     MODEL_KIND = 0
+    _dropout = None                                 # enable_dropout: (refine_pdrop, private generator or None)
+    last_dropout_seed = None                        # the 64-bit key of the last training forward with dropout
 
     def __init__(self, opt, second_fusion=True):
         super().__init__()
@@ -504,6 +506,61 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         # 'always' or 'never'
         self.graph_mode = 'auto'
 
+    # -- training-forward dropout ----------------------------------------------------------
+    def enable_dropout(self, seed=None, refine_pdrop=0.5):
+        """Turn on dropout and drop-path in the training forward (``forward(..., eval=False)``): opt's vid_net / fusion
+        ``proj_pdrop`` and ``path_pdrop`` and ``refine_pdrop`` for the Dropout the reference hard-codes into every refinement TCN
+        layer (tcn.py:5,13: 0.5).  The masks come from a counter-based stream (Philox4x32-10, include/decafnet_hip.h
+        dcf_model_set_dropout), not from torch's: their distribution is the reference's, their bits are not torch's draws.
+        seed=None: every training forward draws its 64-bit key from torch's default CPU generator (``torch.manual_seed``
+        reproduces a run); an int seeds a private ``torch.Generator`` that supplies the keys.  ``last_dropout_seed`` holds the
+        key of the last training forward."""
+        refine_pdrop = float(refine_pdrop)
+        if not 0.0 <= refine_pdrop < 1.0:
+            raise ValueError(f'refine_pdrop = {refine_pdrop} must lie in [0, 1)')
+        gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+        self._dropout = (refine_pdrop, gen)
+
+    def disable_dropout(self):
+        """Back to the deterministic training forward (every dropout probability must then be 0, as before)."""
+        self._dropout = None
+
+    def _dropout_rates(self):
+        """(vid proj, vid path, fusion proj, fusion path, refine) for dcf_model_set_dropout -- or None without enable_dropout,
+        where every probability > 0 is refused as it always was.  Raises before anything touches the GPU."""
+        mo = self.opt['model'] if isinstance(self.opt, dict) else self.opt.model
+        prob = lambda part, key: float(dict(mo[part]).get(key, 0.0) or 0.0)
+        if self._dropout is None:
+            for part in ('vid_net', 'text_net', 'fusion'):
+                for key in ('attn_pdrop', 'proj_pdrop', 'path_pdrop', 'cdrop'):
+                    if prob(part, key) != 0.0:
+                        raise NotImplementedError(f'training-mode forward: opt.model.{part}.{key} must be 0 (forward values only: no dropout '
+                                                  f'random stream, no backward pass)')
+            return None
+        if self.MODEL_KIND != 0:
+            raise NotImplementedError(f'enable_dropout: {type(self).__name__} (one classification head) has no dropout forward; '
+                                      f'PtTransformerEarlyFusionIterative only')
+        if self.second_fusion:
+            raise NotImplementedError('enable_dropout: second_fusion=True is not implemented (build the model with second_fusion=False)')
+        for part in ('vid_net', 'fusion'):
+            if prob(part, 'attn_pdrop') != 0.0:
+                raise NotImplementedError(f'enable_dropout: opt.model.{part}.attn_pdrop must be 0 (attention-map dropout is not implemented)')
+        if prob('vid_net', 'cdrop') != 0.0:
+            raise NotImplementedError('enable_dropout: opt.model.vid_net.cdrop must be 0 (channel dropout is not implemented)')
+        for key in ('attn_pdrop', 'proj_pdrop', 'path_pdrop', 'cdrop'):
+            if prob('text_net', key) != 0.0:
+                raise NotImplementedError(f'enable_dropout: opt.model.text_net.{key} must be 0 (text-encoder dropout is not implemented)')
+        rates = (prob('vid_net', 'proj_pdrop'), prob('vid_net', 'path_pdrop'), prob('fusion', 'proj_pdrop'),
+                 prob('fusion', 'path_pdrop'), self._dropout[0])
+        for name, p in zip(('vid_net.proj_pdrop', 'vid_net.path_pdrop', 'fusion.proj_pdrop', 'fusion.path_pdrop', 'refine_pdrop'), rates):
+            if not 0.0 <= p < 1.0:
+                raise ValueError(f'enable_dropout: {name} = {p} must lie in [0, 1)')
+        return rates
+
+    def _next_dropout_seed(self):
+        halves = torch.randint(0, 1 << 32, (2,), dtype=torch.int64, generator=self._dropout[1])
+        return int(halves[0]) | int(halves[1]) << 32
+
     # -- reference API ---------------------------------------------------------------------
     def encode_text(self, tokens, token_masks):
         """model.py:434-436: tokens (bs, C_t, Lq) f32, token_masks (bs, 1, Lq) bool -> ((bs, TE, Lk), (bs, 1, Lk)),
@@ -524,18 +581,14 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         (B', T_l) / (B', T_l) / (B', T_l, 2) / (B', T_l) bool with B' = sum(text_size) rows in (video, query) order; the classes with
         one classification head (PtTransformer, PtTransformerEarlyFusion: model.py:110-161, :300-373) return (fpn_logits, fpn_offsets,
         fpn_masks) as theirs do.
-        There is no backward pass and no random number stream here: every dropout / drop-path probability of ``opt`` must
-        be 0, and the Dropout(0.5) the reference hard-codes into every layer of the refinement TCN (tcn.py:5,13;
-        model.py:424-425 passes no dropout argument) is taken at p = 0 too -- the values are those of the reference's
-        train()-mode forward with that module's dropout disabled.  The outputs carry no autograd graph; the reference's Trainer
+        There is no backward pass.  Without ``enable_dropout()`` there is no random number stream: every dropout / drop-path
+        probability of ``opt`` must be 0, and the Dropout(0.5) the reference hard-codes into every layer of the refinement TCN
+        (tcn.py:5,13; model.py:424-425 passes no dropout argument) is taken at p = 0 too -- the values are those of the
+        reference's train()-mode forward with that module's dropout disabled.  With it, opt's vid_net / fusion proj_pdrop and
+        path_pdrop and the TCN's rate drop values on the GPU's counter-based stream (``enable_dropout``).  The outputs carry no autograd graph; the reference's Trainer
         is out of scope."""
         assert mv_data is None
-        mo = self.opt['model'] if isinstance(self.opt, dict) else self.opt.model
-        for part in ('vid_net', 'text_net', 'fusion'):
-            for key in ('attn_pdrop', 'proj_pdrop', 'path_pdrop', 'cdrop'):
-                if float(dict(mo[part]).get(key, 0.0) or 0.0) != 0.0:
-                    raise NotImplementedError(f'training-mode forward: opt.model.{part}.{key} must be 0 (forward values only: no dropout '
-                                              f'random stream, no backward pass)')
+        rates = self._dropout_rates()
         if not vid.is_cuda:
             raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
         bs, T = vid.size(0), vid.size(-1)
@@ -591,6 +644,12 @@ class PtTransformerEarlyFusionIterative(nn.Module):
             self._probe_numerics()
             return tuple(logits2.split(sizes_l, 1)), tuple(offsets.split(sizes_l, 1)), tuple(masks.split(sizes_l, 1))
         logits1 = torch.empty(nq, S, device=dev, dtype=torch.float32)
+        seed = 0
+        if rates is not None:
+            seed = self._next_dropout_seed()
+            self.last_dropout_seed = seed
+        sseed = seed - (1 << 64) if seed >= 1 << 63 else seed          # the key's 64 bits as the ABI's int64
+        _lib.check(lib.dcf_model_set_dropout(eng.handle, *(rates or (0.0,) * 5), sseed), 'dcf_model_set_dropout')
         _lib.check(lib.dcf_forward_train_videos(eng.handle, bs, vptr, sptr, mptr_v, T, nqs, tptr, mptr, tlen, cptr, _lib.ptr(logits1),
                                                 _lib.ptr(logits2), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()),
                    'dcf_forward_train_videos')

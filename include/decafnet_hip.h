@@ -171,6 +171,29 @@ int dcf_forward_train_videos(dcf_model* m, int32_t nvid, const float* const* vid
                              const uint8_t* const* text_mask, const int32_t* text_len, const float* const* text_cls,
                              float* logits1_out, float* logits2_out, float* offsets_out, uint8_t* masks_out, void* stream);
 
+/* Dropout and drop-path of the training forward (ABI version 11).  Read by dcf_forward_train_videos only: the evaluation,
+ * hybrid and dcf_op_* entry points never see this state.  Rates: vid_net.proj_pdrop / path_pdrop (stem and branch encoders),
+ * fusion.proj_pdrop / path_pdrop (the early-fusion decoders), the Dropout of every refinement TCN layer (tcn.py:27).  Each
+ * rate must lie in [0, 1); all zero = inactive (the deterministic forward of every probability 0).  While active the forward
+ * takes the unfused kernel sequence and launches eagerly (the seed is a kernel argument, never a captured graph).
+ *
+ * The random stream (the masks are NOT torch's draws, torch's stream is not reproducible outside torch; their distribution
+ * is the reference's):
+ *   Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85;
+ *   key = (seed & 0xffffffff, seed >> 32); counter = (j & 0xffffffff, j >> 32, site, 0), j = e >> 2; element e takes word e & 3;
+ *   u = (word >> 8) * 2^-24; an element is kept iff u >= p (p as fp32); kept values are multiplied by 1.0f / (1.0f - p).
+ *   e = index in the reference's layout: dropout on the (B', C, T_l) tensor e = (b * C + c) * T_l + t, b the (video, query)
+ *       row in repeat_interleave order (model.py:579-582), T_l the padded length of the level; drop-path (per sample) e = b.
+ *   site = group << 16 | layer << 4 | sub: group 1 fusion.layers[i], 2 vid_net.stem[i], 3 vid_net.branch[i], 4 refine.layers[i];
+ *       sub 0 attention proj_drop (blocks.py:392; the decoder's acts on the (B', 2E, T) scale / shift tensor, c < E scale),
+ *       1 FFN dropout after the GELU, 2 FFN dropout after ffn.proj (blocks.py:535-538), 3 drop_path_attn, 4 drop_path_ffn,
+ *       5 the TCN layer's dropout (tcn.py:27). */
+int dcf_model_set_dropout(dcf_model* m, float vid_proj_p, float vid_path_p, float fus_proj_p, float fus_path_p, float refine_p,
+                          int64_t seed);
+/* Test aid: the keep bits (1 = kept) of elements e0 .. e0 + n - 1 of `site` under `seed` and rate p -> out (n bytes, device).
+ * ABI version 11. */
+int dcf_debug_dropout_keep(int64_t seed, int32_t site, int64_t e0, int64_t n, float p, uint8_t* out, void* stream);
+
 /* Point losses, forward values (libs/modeling/loss.py; used by Trainer.forward_backward, libs/worker_v2.py:441-461).
  *   dcf_sigmoid_focal_loss <- sigmoid_focal_loss(inputs, targets, alpha, gamma, smoothing, reduction)   (loss.py:5-57)
  *   dcf_ctr_iou_loss       <- ctr_giou_loss / ctr_diou_loss(input_offsets, target_offsets, reduction, eps) (loss.py:60-166)
