@@ -65,6 +65,10 @@ def make_opt(D=1024, E=256, TE=256, text_in=300, n_levels=8, win=9, n_heads=4, s
             reg_head=dict(name='reg', embd_dim=E, num_fpn_levels=n_levels, n_layers=head_layers),
         ),
         pt_gen=dict(regression_range=4, sigma=0.5, num_fpn_levels=n_levels),
+        # the Trainer's objective (libs/core/opt.py:132-134, :147-157): read by loss.PointObjective / evaluator.calc_loss
+        train=dict(center_sampling='radius', center_sampling_radius=1.5, loss_norm=160, loss_norm_momentum=0.9, loss_weight=1.0,
+                   reg_loss='diou'),
+        loss=dict(fc_a=0.5, fc_s=0.2),
         eval=dict(ranks=(1, 5), iou_threshs=(0.3, 0.5), pre_nms_thresh=0.001, pre_nms_topk=2000,
                   seg_len_thresh=0.1),
         nms=dict(mode='soft_nms', iou_thresh=0.1, min_score=0.001, max_num_segs=5, sigma=0.9,

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import loss as _loss
 from . import nms as _nms
 
 
@@ -103,6 +104,31 @@ def padded_length(vid_len: int, max_vid_len: int, num_fpn_levels: int, mha_win_s
         stride = min_chunk_size(num_fpn_levels, mha_win_size) * vid_stride
         input_len = (vid_len + (stride - 1)) // stride * stride
     return input_len
+
+
+def calc_loss(outputs, targets, opt, pt_gen=None):
+    """Evaluator._calc_loss (worker_v2.py:1029-1061), the validation-time loss: per (video, query) row norm = max(n_pos, 1),
+    cls_loss = calc_focal_loss(logits[masks], labels[masks]) / norm with that function's defaults (smoothing 0.2, alpha 0.5),
+    reg_loss = calc_iou_loss(..., reg_loss='iou') / norm, which selects the GIoU loss; then the mean over the rows, NaN skipped.
+    ``outputs``: (logits, offsets, masks) as per-level tuples of (B', T_l) tensors (what a forward of the single-head form
+    returns; of a two-head training forward pass parts 1 - 3), or the reference's (logits_list, offsets_list, points,
+    masks_list) with one level tuple of (1, T_l) tensors per query.  ``targets`` (B', 2), already divided by vid_stride.
+    One fused pass on the device (loss.PointObjective's kernel, per-row results) and one host read at the end.
+    Returns ({'cls_loss', 'reg_loss'}, per-row (B', 2) array)."""
+    if len(outputs) == 4:                                                   # the reference's tuple: per query, then per level
+        lg, of, _, mk = outputs
+        outputs = tuple(tuple(torch.cat([q[l] for q in part], 0) for l in range(len(part[0]))) for part in (lg, of, mk))
+    tr = opt['train']
+    params, use_offset = _loss.pt_gen_params(opt, pt_gen)
+    rows, _ = _loss._objective(outputs, targets, params, use_offset, tr.get('center_sampling', 'radius'), tr['center_sampling_radius'],
+                               0.5, 0.2, 'iou', None, 1, 1.0)
+    norm = rows[:, 3].clamp(min=1)
+    per_row = torch.stack((rows[:, 1] / norm, rows[:, 2] / norm), 1).cpu().numpy()      # the one host read
+    stats = {}
+    for k, name in enumerate(('cls_loss', 'reg_loss')):
+        v = [float(x) for x in per_row[:, k] if not np.isnan(x)]
+        stats[name] = float(np.mean(v)) if v else float('nan')
+    return stats, per_row
 
 
 class GroundingEvaluator:

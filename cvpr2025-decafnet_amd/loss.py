@@ -6,6 +6,10 @@ autograd graph (training is out of scope).
 The reference indexes with boolean masks before calling (``logits[fpn_masks]``, ``offsets[pos_masks]``,
 worker_v2.py:446-458), which compacts on the device and synchronises the host for the output size; ``select=`` takes the mask
 instead and leaves everything on the device.
+
+The label side of the objective lives here too (csrc/objective.hip): ``annotate_points_per_video`` / ``annotate_points``
+(worker_v2.py:93-133, :575-637) and ``PointObjective``, the fused pass over the training forward's packed outputs that returns the
+Trainer's loss dict (worker_v2.py:441-476) without materialising labels or ground-truth offsets and without a host wait.
 """
 from __future__ import annotations
 
@@ -98,3 +102,217 @@ def calc_iou_loss(pred_offsets, gt_offsets, reg_loss='diou', reduction='sum', se
     """worker_v2.py:89-91."""
     fn = ctr_diou_loss if reg_loss == 'diou' else ctr_giou_loss
     return fn(pred_offsets, gt_offsets, reduction=reduction, select=select)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Point annotation and the Trainer's objective (csrc/objective.hip).  The kernels derive the candidate points from their index
+# in the packed pyramid layout; the point table the reference passes around is used only to recover that layout's parameters.
+
+def _pt_gen_params(ranges, max_seq_len):
+    """(regression_range, sigma, max_seq_len) that make PtGenerator.__init__ (model.py:686-696) produce `ranges`, or None"""
+    ranges = [(float(a), float(b)) for a, b in ranges]
+    rr = ranges[0][1]
+    if ranges[0][0] != 0.0 or not rr > 0:
+        return None
+    sigma = ranges[1][0] / rr if len(ranges) > 1 else 1.0
+    if not 0 < sigma <= 1:
+        return None
+    msl = int(ranges[-1][1]) - 1 if max_seq_len is None else int(max_seq_len)
+    want, cur = [(0.0, rr)], rr
+    for l in range(1, len(ranges)):
+        lo, hi = cur * sigma, cur * 2
+        if l == len(ranges) - 1:
+            hi = max(hi, msl + 1)
+        want.append((lo, hi))
+        cur = hi
+    f32 = lambda r: torch.tensor(r, dtype=torch.float64).to(torch.float32)            # noqa: E731  (the buffer's rounding)
+    if not torch.equal(f32(want), f32(ranges)):
+        return None
+    return rr, sigma, msl
+
+
+def _point_layout(points):
+    """T, L, (regression_range, sigma, max_seq_len), use_offset of a PtGenerator point table (a tuple of levels or their cat);
+    ValueError when the table is anything else"""
+    def bad(why):
+        return ValueError(f'points is not a PtGenerator table ({why}): the kernels derive the candidate points from their index')
+
+    if isinstance(points, (tuple, list)):
+        levels = [p.detach().cpu().float() for p in points]
+    else:
+        p = points.detach().cpu().float()
+        if p.dim() != 2 or p.size(-1) != 4 or p.size(0) == 0:
+            raise bad(f'shape {tuple(p.shape)}')
+        stride = p[:, 3]
+        cuts = (torch.nonzero(stride[1:] != stride[:-1]).flatten() + 1).tolist()
+        levels = list(torch.tensor_split(p, cuts))
+    L = len(levels)
+    if L < 1 or L > 16 or any(lv.dim() != 2 or lv.size(-1) != 4 for lv in levels):
+        raise bad('levels')
+    T = levels[0].size(0)
+    if T == 0 or T % (1 << (L - 1)) or any(lv.size(0) != T >> l for l, lv in enumerate(levels)):
+        raise bad('level lengths are not T >> l')
+    use_offset = bool(levels[0][0, 0] == 0.5)
+    ranges = []
+    for l, lv in enumerate(levels):
+        s = float(1 << l)
+        x = torch.arange(lv.size(0), dtype=torch.float32) * s + (s - 0.5 if use_offset else 0.0)       # model.py:710-712, see PtGenerator
+        if not (torch.equal(lv[:, 0], x) and bool((lv[:, 3] == s).all()) and bool((lv[:, 1:3] == lv[0, 1:3]).all())):
+            raise bad(f'level {l}')
+        ranges.append((float(lv[0, 1]), float(lv[0, 2])))
+    params = _pt_gen_params(ranges, None)
+    if params is None or params[2] < T:
+        raise bad('regression ranges')
+    return T, L, params, use_offset
+
+
+def _annotate(targets, T, L, params, use_offset, center_sampling, center_sampling_radius, predicates):
+    if not targets.is_cuda:
+        raise RuntimeError('targets must live on the MI355X: the annotation has no CPU path')
+    tg = targets.float().reshape(-1, 2).contiguous()
+    n, S = tg.size(0), sum(T >> l for l in range(L))
+    labels = torch.empty(n, S, dtype=torch.bool, device=tg.device)
+    offsets = torch.empty(n, S, 2, dtype=torch.float32, device=tg.device)
+    win = torch.empty_like(labels) if predicates else None
+    rng = torch.empty_like(labels) if predicates else None
+    rr, sigma, msl = params
+    _lib.check(_lib.lib().dcf_annotate_points(_lib.ptr(tg), n, T, L, rr, sigma, int(use_offset), msl, int(center_sampling == 'radius'),
+                                              float(center_sampling_radius), _lib.ptr(labels), _lib.ptr(offsets), _lib.ptr(win), _lib.ptr(rng),
+                                              _lib.current_stream()), 'dcf_annotate_points')
+    return labels, offsets, win, rng
+
+
+def annotate_points_per_video(points, target, center_sampling='radius', center_sampling_radius=1.5):
+    """worker_v2.py:93-133: (labels (p,), offsets (p, 2), [inside_window, inside_range]) of one target segment."""
+    T, L, params, use_offset = _point_layout(points)
+    labels, offsets, win, rng = _annotate(target.reshape(1, 2), T, L, params, use_offset, center_sampling, center_sampling_radius, True)
+    return labels[0], offsets[0], [win[0], rng[0]]
+
+
+def annotate_points(points, targets, center_sampling='radius', center_sampling_radius=1.5):
+    """Trainer._annotate_points (worker_v2.py:575-637): labels (bs, p) bool and offsets (bs, p, 2) of every target, one launch."""
+    T, L, params, use_offset = _point_layout(points)
+    labels, offsets, _, _ = _annotate(targets, T, L, params, use_offset, center_sampling, center_sampling_radius, False)
+    return labels, offsets
+
+
+def _packed(parts):
+    """the (B', S[, 2]) tensor whose level split `parts` is: the storage the training forward filled when the parts are its
+    `split` views (modeling.py), a `cat` otherwise"""
+    if torch.is_tensor(parts):
+        return parts.contiguous()
+    base = parts[0]._base
+    if base is not None and base.is_contiguous() and base.dim() == parts[0].dim():
+        off, ok = 0, True
+        for p in parts:
+            ok = ok and p._base is base and p.stride() == base.stride() and p.size(0) == base.size(0)
+            ok = ok and p.storage_offset() == base.storage_offset() + off * base.stride(1)
+            off += p.size(1)
+        if ok and off == base.size(1):
+            return base
+    return torch.cat(tuple(parts), 1).contiguous()
+
+
+def _objective(outputs, targets, pt_params, use_offset, center_sampling, radius, alpha, smoothing, reg_loss, norm_of, world_size, loss_weight):
+    """dcf_point_objective on the level tuples a forward returns: (rows (B', 4), out4 or None when ``norm_of`` is None)"""
+    if len(outputs) == 4:
+        l1, l2, off, msk = (_packed(p) for p in outputs)
+    elif len(outputs) == 3:
+        l1, (l2, off, msk) = None, (_packed(p) for p in outputs)
+    else:
+        raise ValueError('outputs: the 4 (or, for the classes with one classification head, 3) parts the training forward returns')
+    if torch.is_tensor(outputs[-1]):
+        raise ValueError('outputs must be per-level tuples (the level lengths define the point layout)')
+    if not (l2.is_cuda and targets.is_cuda):
+        raise RuntimeError('the objective runs on the MI355X: outputs and targets must live there')
+    n, S = l2.shape
+    sizes = [p.size(1) for p in outputs[-1]]
+    T, L = sizes[0], len(sizes)
+    if sizes != [T >> l for l in range(L)] or T % (1 << (L - 1)):
+        raise ValueError(f'level lengths {sizes} are not a pyramid T >> l')
+    tg = targets.float().reshape(-1, 2).contiguous()
+    assert tg.size(0) == n and off.shape == (n, S, 2) and msk.shape == (n, S) and msk.dtype == torch.bool
+    assert l2.dtype == torch.float32 and off.dtype == torch.float32 and (l1 is None or (l1.dtype == torch.float32 and l1.shape == l2.shape))
+    rows = torch.empty(n, 4, dtype=torch.float32, device=l2.device)
+    out4 = torch.empty(4, dtype=torch.float32, device=l2.device) if norm_of is not None else None
+    rr, sigma, msl = pt_params
+    _lib.check(_lib.lib().dcf_point_objective(
+        _lib.ptr(l1), _lib.ptr(l2), _lib.ptr(off), _lib.ptr(msk), _lib.ptr(tg), n, T, L, rr, sigma, int(use_offset), msl,
+        int(center_sampling == 'radius'), float(radius), float(alpha), float(smoothing), int(reg_loss == 'diou'), 1e-8,
+        _lib.ptr(norm_of(l2.device)) if norm_of is not None else None, float(world_size), float(loss_weight), _lib.ptr(rows), _lib.ptr(out4),
+        _lib.current_stream()), 'dcf_point_objective')
+    return rows, out4
+
+
+def pt_gen_params(opt, pt_gen=None):
+    """((regression_range, sigma, max_seq_len), use_offset) of a PtGenerator, or of the one ``opt`` describes"""
+    if pt_gen is not None:
+        params = _pt_gen_params(pt_gen.regression_range, pt_gen.max_seq_len)
+        if params is None:
+            raise ValueError('pt_gen.regression_range is not what PtGenerator.__init__ derives')
+        return params, bool(pt_gen.use_offset)
+    pg = opt['pt_gen']
+    return ((float(pg['regression_range']), float(pg['sigma']), int(pg.get('max_seq_len') or opt['model']['vid_net']['max_seq_len'])),
+            bool(pg.get('use_offset', False)))
+
+
+class PointObjective:
+    """What Trainer._microbatch_forward_backward does after the model call (worker_v2.py:428-476), forward values only, as one
+    fused pass over the training forward's packed outputs: point annotation, pos = labels & masks, the focal losses of both
+    heads on the valid points, the DIoU / GIoU loss on the positive points, the division by the running loss_norm, the
+    world-size factor and total = cls + loss_weight * reg.  Nothing waits on the host: loss_norm lives on the device.
+
+    ``opt.train`` supplies center_sampling, center_sampling_radius, loss_norm, loss_norm_momentum, loss_weight, reg_loss and
+    ``opt.loss`` fc_a, fc_s; the point layout comes from ``pt_gen`` (a PtGenerator) or from ``opt.pt_gen`` and the video
+    network's max_seq_len."""
+
+    def __init__(self, opt, pt_gen=None, world_size=1):
+        tr, ls = opt['train'], opt['loss']
+        self.center_sampling = tr.get('center_sampling', 'radius')
+        self.center_sampling_radius = float(tr['center_sampling_radius'])
+        self.loss_norm_momentum = float(tr['loss_norm_momentum'])
+        self.loss_weight = float(tr['loss_weight'])
+        self.reg_loss = tr['reg_loss']
+        self.fc_a, self.fc_s = float(ls['fc_a']), float(ls['fc_s'])
+        self.world_size = int(world_size)
+        self.pt_params, self.use_offset = pt_gen_params(opt, pt_gen)
+        self._loss_norm0 = float(tr['loss_norm'])
+        self._norm64 = None              # the running norm in fp64 on the device (the reference keeps a Python float)
+        self._norm32 = None              # ... and the fp32 copy the kernel reads
+        self.per_row = None
+
+    def _norm(self, device):
+        if self._norm64 is None or self._norm64.device != device:
+            if self._norm64 is None:
+                self._norm64 = torch.full((1,), self._loss_norm0, dtype=torch.float64, device=device)
+            else:
+                self._norm64 = self._norm64.to(device)
+            self._norm32 = self._norm64.to(torch.float32)
+        return self._norm32
+
+    @property
+    def loss_norm(self):
+        """the running normaliser (a host read: for logging and checkpoints, not for the step)"""
+        return self._loss_norm0 if self._norm64 is None else float(self._norm64)
+
+    @loss_norm.setter
+    def loss_norm(self, v):
+        self._loss_norm0, self._norm64, self._norm32 = float(v), None, None
+
+    def update_norm(self, norm_sum):
+        """worker_v2.py:381-382: loss_norm = m * loss_norm + (1 - m) * max(sum of the ranks' norms, 1).  ``norm_sum``: the
+        (all-gathered and summed) norm of the step, a device tensor (no host wait) or a number."""
+        m = self.loss_norm_momentum
+        if torch.is_tensor(norm_sum) and norm_sum.is_cuda:
+            self._norm(norm_sum.device)
+            self._norm64 = m * self._norm64 + (1. - m) * norm_sum.to(torch.float64).reshape(1).clamp(min=1)
+            self._norm32 = self._norm64.to(torch.float32)
+        else:
+            self.loss_norm = m * self.loss_norm + (1. - m) * max(float(norm_sum), 1)
+        return self
+
+    def __call__(self, outputs, targets):
+        rows, out4 = _objective(outputs, targets, self.pt_params, self.use_offset, self.center_sampling, self.center_sampling_radius, self.fc_a,
+                                self.fc_s, self.reg_loss, self._norm, self.world_size, self.loss_weight)
+        self.per_row = rows
+        return {'cls': out4[0], 'reg': out4[1], 'total': out4[2], 'norm': out4[3].to(torch.int64)}

@@ -1125,8 +1125,10 @@ class PtGenerator(nn.Module):
         tics = torch.arange(0, max_seq_len, 1.0)
         for l in range(num_fpn_levels):
             stride = 2 ** l
-            pts = tics[::stride][:, None].clone()
+            pts = tics[::stride][:, None]
             if use_offset:
+                # in place on a strided VIEW of the tics, as the reference does (model.py:710-712): the tics a coarser level
+                # takes already carry the shifts of the finer ones, so level l sits at j * 2^l + 2^l - 0.5
                 pts += 0.5 * stride
             r = torch.as_tensor(rng[l], dtype=torch.float32)[None].repeat(len(pts), 1)
             s = torch.full((len(pts), 1), float(stride))

@@ -207,6 +207,34 @@ int dcf_sigmoid_focal_loss(const float* inputs, const float* targets, const uint
 int dcf_ctr_iou_loss(const float* input_offsets, const float* target_offsets, const uint8_t* select, int64_t n, int32_t kind,
                      float eps, float* elem_out, float* sum_out, int32_t* count_out, void* stream);
 
+/* Point annotation and the Trainer's objective on the packed (B', S) outputs of dcf_forward_train_videos (ABI version 12).  No
+ * backward pass.  The candidate points are not an argument: point i of a row follows from (T, L) and the parameters of
+ * PtGenerator (libs/modeling/model.py:668-743) -- level l holds T >> l points of stride 2^l at (i - first_l) * 2^l
+ * (+ 2^l - 0.5 with use_offset: the reference adds 0.5 * 2^l in place on a strided view of one tic array, model.py:710-712, so
+ * level l carries the shifts of the levels below it too), with the regression range of model.py:686-696 built from regression_range, sigma and
+ * max_seq_len as PtGenerator.__init__ builds it.  1 <= L <= 16, T a multiple of 2^(L-1), T <= max_seq_len, T < 2^23.
+ * targets (nrows, 2): the segments, already divided by vid_stride.  center_sampling: 1 = 'radius' (within `radius` strides of
+ * the segment centre), 0 = anything else (inside the segment).
+ *   dcf_annotate_points <- annotate_points_per_video per target (libs/worker_v2.py:93-133) = Trainer._annotate_points
+ *     (:575-637): labels_out (nrows, S) bytes, offsets_out (nrows, S, 2), optionally the two predicates the function returns
+ *     third (in_window_out, in_range_out: (nrows, S) bytes).  Bit-equal to the reference.
+ *   dcf_point_objective <- Trainer._microbatch_forward_backward after the model call (:441-476), without the backward:
+ *     pos = labels & masks, norm = pos.sum(), calc_focal_loss (:85-87, label l * (1 - smoothing) + smoothing / 2, gamma 2) of
+ *     both heads over masks, calc_iou_loss (:89-91; iou_kind 0 GIoU, 1 DIoU) over pos, each / loss_norm * world_size,
+ *     cls = (cls1 + cls2) / 2, total = cls + loss_weight * reg.  Labels and ground-truth offsets are formed in registers and
+ *     never written.  logits1 may be NULL (one classification head: cls = cls2, Evaluator._calc_loss :1029-1061).
+ *     loss_norm_dev: one float on the device (the Trainer's running loss_norm), read by the kernel so that the host never waits.
+ *     rows_out (optional, (nrows, 4)): per row (focal1_sum, focal2_sum, iou_sum, n_pos), focal over masks, iou over
+ *     labels & masks.  out4 (optional, 4 floats): cls, reg, total, norm.  Sums are taken in a fixed order that depends on
+ *     (nrows, S) alone (deterministic); the only allocation is stream-ordered scratch sized from (nrows, S). */
+int dcf_annotate_points(const float* targets, int32_t nrows, int64_t T, int32_t L, double regression_range, double sigma, int32_t use_offset,
+                        int64_t max_seq_len, int32_t center_sampling, double radius, uint8_t* labels_out, float* offsets_out,
+                        uint8_t* in_window_out, uint8_t* in_range_out, void* stream);
+int dcf_point_objective(const float* logits1, const float* logits2, const float* offsets, const uint8_t* masks, const float* targets,
+                        int32_t nrows, int64_t T, int32_t L, double regression_range, double sigma, int32_t use_offset, int64_t max_seq_len,
+                        int32_t center_sampling, double radius, float alpha, double smoothing, int32_t iou_kind, float eps,
+                        const float* loss_norm_dev, float world_size, float loss_weight, float* rows_out, float* out4, void* stream);
+
 /* Throughput extension: several videos of the SAME padded length T in one forward (the reference evaluates one video per
  * call, model.py:496; videos no longer than opt.model.max_vid_len are all padded to that length, worker_v2.py:969-976).
  * Video v has nq_per_video[v] queries; text / text_mask / text_len and the outputs list the queries of all videos in
