@@ -56,6 +56,10 @@ SIGNATURES = {
     'dcf_annotate_points': (i32, [c_f32p, i32, i64, i32, f64, f64, i32, i64, i32, f64, c_u8p, c_f32p, c_u8p, c_u8p, vp]),
     'dcf_point_objective': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, i32, i64, i32, f64, f64, i32, i64, i32, f64, f32, f64, i32, f32,
                                   c_f32p, f32, f32, c_f32p, c_f32p, vp]),
+    'dcf_sigmoid_focal_loss_grad': (i32, [c_f32p, c_f32p, c_u8p, i64, f32, f32, i32, c_f32p, c_f32p, c_i32p, c_f32p, vp]),
+    'dcf_ctr_iou_loss_grad': (i32, [c_f32p, c_f32p, c_u8p, i64, i32, f32, c_f32p, c_f32p, c_i32p, c_f32p, vp]),
+    'dcf_point_objective_grad': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, i32, i64, i32, f64, f64, i32, i64, i32, f64, f32, f64, i32, f32,
+                                       c_f32p, f32, f32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, i32, c_f32p, c_f32p, vp]),
     'dcf_forward_eval_gated': (i32, [vp, c_f32p, c_f32p, c_u8p, i64, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                      ctypes.POINTER(i32), c_f32p, c_f32p, c_f32p, c_u8p, vp]),
     'dcf_hybrid_phase1': (i32, [vp, i32, c_f32p, c_f32p, c_u8p, i64, i64, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i32),

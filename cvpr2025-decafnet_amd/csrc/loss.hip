@@ -1,7 +1,8 @@
-// Point losses of the training objective, forward values only (libs/modeling/loss.py; Trainer.forward_backward,
-// libs/worker_v2.py:441-461).  Elementwise arithmetic in the reference's fp32 operation order; the boolean-mask selections of
-// the caller (`logits[fpn_masks]`, `offsets[pos_masks]`) are a byte mask here instead of a compaction; sums are taken in a
-// fixed order (chunk partials, then one workgroup over the partials) so a value does not depend on scheduling.
+// Point losses of the training objective (libs/modeling/loss.py; Trainer.forward_backward, libs/worker_v2.py:441-461): values, and
+// their gradients with respect to the predictions (k_loss_grad, the elementwise backward of `total_loss.backward()`, :467-468).
+// Elementwise arithmetic in the reference's fp32 operation order; the boolean-mask selections of the caller (`logits[fpn_masks]`,
+// `offsets[pos_masks]`) are a byte mask here instead of a compaction; sums are taken in a fixed order (chunk partials, then one
+// workgroup over the partials) so a value does not depend on scheduling.
 #include "../../include/decafnet_hip.h"
 #include "common.h"
 #include "loss_elem.h"
@@ -100,6 +101,50 @@ static int run_loss(LossArgs a, float* sum_out, int32_t* count_out, hipStream_t 
   return 0;
 }
 
+// Gradient of the reduced loss with respect to `a`: elementwise, so no partials and no ordering question.  The upstream gradient
+// is per element (reduction 'none': grad_elem[i]) or one device scalar ('sum' / 'mean': *grad_scalar, NULL = 1), for 'mean'
+// divided by the selected count read from the device (*count; 0 gives zeros, as `0.0 * loss.sum()` does).
+struct LossGradArgs {
+  const float* grad_elem;
+  const float* grad_scalar;
+  const int* count;
+  float* grad;             // [n] (focal) / [n][2] (IoU)
+};
+
+template <bool IOU>
+__global__ __launch_bounds__(LOSS_NT) void k_loss_grad(LossArgs p, LossGradArgs q) {
+  const long long i = (long long)blockIdx.x * LOSS_NT + threadIdx.x;
+  if (i >= p.n) return;
+  float up = q.grad_elem ? q.grad_elem[i] : (q.grad_scalar ? *q.grad_scalar : 1.f);
+  bool sel = !p.select || p.select[i] != 0;
+  if (q.count) {
+    const int c = *q.count;
+    if (c > 0) up = up / (float)c;
+    else sel = false;
+  }
+  if constexpr (IOU) {
+    float gl = 0.f, gr = 0.f;
+    if (sel) {
+      iou_grad_elem(p.a[2 * i], p.a[2 * i + 1], p.b[2 * i], p.b[2 * i + 1], p.kind, p.eps, gl, gr);
+      gl *= up;
+      gr *= up;
+    }
+    q.grad[2 * i] = gl;
+    q.grad[2 * i + 1] = gr;
+  } else {
+    q.grad[i] = sel ? up * focal_grad_elem(p.a[i], p.b[i], p.alpha, p.gamma, p.smoothing != 0) : 0.f;
+  }
+}
+
+template <bool IOU>
+static int run_loss_grad(const LossArgs& a, const LossGradArgs& g, hipStream_t st) {
+  if (a.n <= 0) return 0;
+  ProfScope prof(IOU ? "ctr_iou_loss_grad" : "sigmoid_focal_loss_grad", st, 0.0, (IOU ? 24.0 : 12.0) * (double)a.n);
+  hipLaunchKernelGGL(k_loss_grad<IOU>, dim3((unsigned)((a.n + LOSS_NT - 1) / LOSS_NT)), dim3(LOSS_NT), 0, st, a, g);
+  DCF_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace dcf
 
 extern "C" {
@@ -117,6 +162,27 @@ int dcf_ctr_iou_loss(const float* input_offsets, const float* target_offsets, co
             "dcf_ctr_iou_loss: bad arguments");
   dcf::LossArgs a{input_offsets, target_offsets, select, (long long)n, 0.f, 0.f, eps, 0, kind, elem_out, nullptr, nullptr};
   return dcf::run_loss<true>(a, sum_out, count_out, (hipStream_t)stream);
+}
+
+int dcf_sigmoid_focal_loss_grad(const float* inputs, const float* targets, const uint8_t* select, int64_t n, float alpha, float gamma,
+                                int32_t smoothing, const float* grad_elem, const float* grad_scalar, const int32_t* count_dev,
+                                float* grad_out, void* stream) {
+  DCF_CHECK(n >= 0 && n < (1ll << 38) && (n == 0 || (inputs && targets && grad_out)) && !(grad_elem && (grad_scalar || count_dev)),
+            "dcf_sigmoid_focal_loss_grad: bad arguments");
+  dcf::LossArgs a{inputs, targets, select, (long long)n, alpha, gamma, 0.f, smoothing, 0, nullptr, nullptr, nullptr};
+  dcf::LossGradArgs g{grad_elem, grad_scalar, (const int*)count_dev, grad_out};
+  return dcf::run_loss_grad<false>(a, g, (hipStream_t)stream);
+}
+
+int dcf_ctr_iou_loss_grad(const float* input_offsets, const float* target_offsets, const uint8_t* select, int64_t n, int32_t kind,
+                          float eps, const float* grad_elem, const float* grad_scalar, const int32_t* count_dev, float* grad_out,
+                          void* stream) {
+  DCF_CHECK(n >= 0 && n < (1ll << 38) && (n == 0 || (input_offsets && target_offsets && grad_out)) && (kind == 0 || kind == 1) &&
+                !(grad_elem && (grad_scalar || count_dev)),
+            "dcf_ctr_iou_loss_grad: bad arguments");
+  dcf::LossArgs a{input_offsets, target_offsets, select, (long long)n, 0.f, 0.f, eps, 0, kind, nullptr, nullptr, nullptr};
+  dcf::LossGradArgs g{grad_elem, grad_scalar, (const int*)count_dev, grad_out};
+  return dcf::run_loss_grad<true>(a, g, (hipStream_t)stream);
 }
 
 }  // extern "C"

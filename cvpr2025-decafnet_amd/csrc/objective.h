@@ -46,11 +46,25 @@ struct ObjectiveArgs {
   float* part;                          // [nrows][bpr][4] scratch
 };
 
+// Gradient side of k_objective: d total / d (logits1, logits2, offsets), times the upstream gradients
+struct ObjectiveGradArgs {
+  float* g_logits1;                     // [nrows][S] or nullptr (with logits1)
+  float* g_logits2;                     // [nrows][S]
+  float* g_offsets;                     // [nrows][S][2]
+  const float* loss_norm;               // device scalar
+  const float* grad_total;              // device scalar: upstream gradient of `total`, nullptr = 1
+  const float* grad_parts;              // device float[2]: upstream gradients of `cls` and `reg` on their own, nullptr = 0
+  float world_size, loss_weight;
+  int accumulate;                       // 1: add into the g_* buffers instead of overwriting them
+};
+
 int launch_annotate(const AnnotateArgs& a, int nrows, hipStream_t st);
 // bytes of scratch launch_objective needs for (nrows, S): the partials and the row results
 size_t objective_scratch_bytes(int nrows, int S);
 int objective_blocks_per_row(int S);
 int launch_objective(const ObjectiveArgs& a, int nrows, const float* loss_norm, float world_size, float loss_weight, float* rows_scratch,
                      float* rows_out, float* out4, hipStream_t st);
+int launch_objective_grad(const ObjectiveArgs& a, const ObjectiveGradArgs& g, int nrows, float* rows_scratch, float* rows_out, float* out4,
+                          hipStream_t st);
 
 }  // namespace dcf

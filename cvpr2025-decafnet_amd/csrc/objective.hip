@@ -4,7 +4,9 @@
 // The annotation is bit-equal to the reference: strides are powers of two, so i * stride, stride * radius, x / stride and
 // 0.5 * (a + b) are exact and a contracted multiply-add gives the bits of the separate operations; what remains are single fp32
 // adds, subtracts, min / max and comparisons in the reference's order.  Sums: fixed partials per workgroup, then one ordered pass
-// (no floating-point atomics), the split being a function of (B', S) alone.
+// (no floating-point atomics), the split being a function of (B', S) alone.  The gradient of the objective with respect to the
+// packed outputs (`total_loss.backward()`, worker_v2.py:467-468, cut at the forward's outputs) is a second instantiation of the same
+// kernel: labels and ground-truth offsets come from the same annotate_point, the derivative from loss_elem.h.
 #include "../../include/decafnet_hip.h"
 #include "common.h"
 #include "loss_elem.h"
@@ -124,8 +126,46 @@ __device__ __forceinline__ void objective_point(const ObjectiveArgs& p, const Le
   }
 }
 
-// grid (bpr, nrows): workgroup (k, b) reduces the points [k * OBJ_PER_BLOCK, (k + 1) * OBJ_PER_BLOCK) of row b to one partial
-__global__ __launch_bounds__(OBJ_NT) void k_objective(ObjectiveArgs p) {
+// Gradient of the objective at one point: the factors of worker_v2.py:447-465 are folded into s_cls (world_size / loss_norm / n_heads
+// times the upstream gradient) and s_reg (world_size / loss_norm times loss_weight and the upstream gradient).  0 outside masks
+// (logits) and outside labels & masks (offsets).
+struct PointGrad {
+  float g1, g2, gl, gr;
+};
+
+__device__ __forceinline__ PointGrad grad_point(const ObjectiveArgs& p, float s_cls, float s_reg, const LevelCtx& c, int j, float t0, float t1,
+                                                bool valid, float x1, float x2, float ol, float orr, bool two_heads) {
+  PointGrad o{0.f, 0.f, 0.f, 0.f};
+  if (!valid) return o;
+  const PointGt g = annotate_point(p.rule, c, j, t0, t1);
+  const bool pos = g.in_window && g.in_range;
+  const float t = pos ? p.t_pos : p.t_neg;
+  if (two_heads) o.g1 = s_cls * focal_grad_elem(x1, t, p.alpha, 2.f, true);
+  o.g2 = s_cls * focal_grad_elem(x2, t, p.alpha, 2.f, true);
+  if (pos) {
+    iou_grad_elem(ol, orr, g.left, g.right, p.kind, p.eps, o.gl, o.gr);
+    o.gl *= s_reg;
+    o.gr *= s_reg;
+  }
+  return o;
+}
+
+__device__ __forceinline__ void put4(float* dst, float4 v, bool accumulate) {
+  float4* d = reinterpret_cast<float4*>(dst);
+  if (accumulate) {
+    const float4 o = *d;
+    v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+  }
+  *d = v;
+}
+
+__device__ __forceinline__ void put1(float* dst, float v, bool accumulate) { *dst = accumulate ? *dst + v : v; }
+
+// grid (bpr, nrows): workgroup (k, b) works on the points [k * OBJ_PER_BLOCK, (k + 1) * OBJ_PER_BLOCK) of row b.  VAL: reduces them to
+// one partial of the four sums.  GRAD: writes (or, with accumulate, adds) the gradient of every point of the range -- elementwise,
+// no atomics, so deterministic by construction.  Both from one pass over the inputs when both are set.
+template <bool VAL, bool GRAD>
+__global__ __launch_bounds__(OBJ_NT) void k_objective(ObjectiveArgs p, ObjectiveGradArgs q) {
   __shared__ float s_part[OBJ_NT / 64][4];
   const int b = blockIdx.y;
   const int S = p.rule.S;
@@ -136,6 +176,20 @@ __global__ __launch_bounds__(OBJ_NT) void k_objective(ObjectiveArgs p) {
   const float* l2 = p.logits2 + row;
   const float* of = p.offsets + 2 * row;
   const uint8_t* mk = p.masks + row;
+  float s_cls = 0.f, s_reg = 0.f;
+  float *g1 = nullptr, *g2 = nullptr, *go = nullptr;
+  bool acc = false;
+  if constexpr (GRAD) {
+    const double k = (double)q.world_size / (double)*q.loss_norm;
+    const double up = q.grad_total ? (double)*q.grad_total : 1.0;
+    const double up_cls = q.grad_parts ? (double)q.grad_parts[0] : 0.0, up_reg = q.grad_parts ? (double)q.grad_parts[1] : 0.0;
+    s_cls = (float)(k * (up + up_cls) / (two ? 2.0 : 1.0));
+    s_reg = (float)(k * ((double)q.loss_weight * up + up_reg));
+    g1 = two ? q.g_logits1 + row : nullptr;
+    g2 = q.g_logits2 + row;
+    go = q.g_offsets + 2 * row;
+    acc = q.accumulate != 0;
+  }
   Acc a{0.f, 0.f, 0.f, 0};
 #pragma unroll
   for (int k = 0; k < OBJ_GROUPS; ++k) {
@@ -146,27 +200,60 @@ __global__ __launch_bounds__(OBJ_NT) void k_objective(ObjectiveArgs p) {
       // the whole group lies on one level: one level context, 16-byte loads (rows and level starts are multiples of 4 points)
       const LevelCtx c = level_ctx(p.rule, l, t0, t1);
       const uint32_t m4 = *reinterpret_cast<const uint32_t*>(mk + i0);
-      if (m4 == 0) continue;
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (m4 == 0) {
+        if constexpr (GRAD) {
+          if (!acc) {
+            if (two) put4(g1 + i0, z, false);
+            put4(g2 + i0, z, false);
+            put4(go + 2 * i0, z, false);
+            put4(go + 2 * i0 + 4, z, false);
+          }
+        }
+        continue;
+      }
       const float4 a1 = two ? *reinterpret_cast<const float4*>(l1 + i0) : z;
       const float4 a2 = *reinterpret_cast<const float4*>(l2 + i0);
       const float4 o01 = *reinterpret_cast<const float4*>(of + 2 * i0);
       const float4 o23 = *reinterpret_cast<const float4*>(of + 2 * i0 + 4);
       const int j = i0 - p.rule.off[l];
-      objective_point(p, c, j + 0, t0, t1, (m4 & 0x000000FFu) != 0, a1.x, a2.x, o01.x, o01.y, two, a);
-      objective_point(p, c, j + 1, t0, t1, (m4 & 0x0000FF00u) != 0, a1.y, a2.y, o01.z, o01.w, two, a);
-      objective_point(p, c, j + 2, t0, t1, (m4 & 0x00FF0000u) != 0, a1.z, a2.z, o23.x, o23.y, two, a);
-      objective_point(p, c, j + 3, t0, t1, (m4 & 0xFF000000u) != 0, a1.w, a2.w, o23.z, o23.w, two, a);
+      if constexpr (VAL) {
+        objective_point(p, c, j + 0, t0, t1, (m4 & 0x000000FFu) != 0, a1.x, a2.x, o01.x, o01.y, two, a);
+        objective_point(p, c, j + 1, t0, t1, (m4 & 0x0000FF00u) != 0, a1.y, a2.y, o01.z, o01.w, two, a);
+        objective_point(p, c, j + 2, t0, t1, (m4 & 0x00FF0000u) != 0, a1.z, a2.z, o23.x, o23.y, two, a);
+        objective_point(p, c, j + 3, t0, t1, (m4 & 0xFF000000u) != 0, a1.w, a2.w, o23.z, o23.w, two, a);
+      }
+      if constexpr (GRAD) {
+        const PointGrad d0 = grad_point(p, s_cls, s_reg, c, j + 0, t0, t1, (m4 & 0x000000FFu) != 0, a1.x, a2.x, o01.x, o01.y, two);
+        const PointGrad d1 = grad_point(p, s_cls, s_reg, c, j + 1, t0, t1, (m4 & 0x0000FF00u) != 0, a1.y, a2.y, o01.z, o01.w, two);
+        const PointGrad d2 = grad_point(p, s_cls, s_reg, c, j + 2, t0, t1, (m4 & 0x00FF0000u) != 0, a1.z, a2.z, o23.x, o23.y, two);
+        const PointGrad d3 = grad_point(p, s_cls, s_reg, c, j + 3, t0, t1, (m4 & 0xFF000000u) != 0, a1.w, a2.w, o23.z, o23.w, two);
+        if (two) put4(g1 + i0, make_float4(d0.g1, d1.g1, d2.g1, d3.g1), acc);
+        put4(g2 + i0, make_float4(d0.g2, d1.g2, d2.g2, d3.g2), acc);
+        put4(go + 2 * i0, make_float4(d0.gl, d0.gr, d1.gl, d1.gr), acc);
+        put4(go + 2 * i0 + 4, make_float4(d2.gl, d2.gr, d3.gl, d3.gr), acc);
+      }
     } else {
       // the shortest levels, the end of a row, or operands that are not 16-byte aligned: point by point
       for (int i = i0; i < min(i0 + 4, S); ++i) {
-        if (mk[i] == 0) continue;
+        const bool valid = mk[i] != 0;
+        if (!GRAD && !valid) continue;
         const int li = level_of(p.rule, i);
         const LevelCtx c = level_ctx(p.rule, li, t0, t1);
-        objective_point(p, c, i - p.rule.off[li], t0, t1, true, two ? l1[i] : 0.f, l2[i], of[2 * i], of[2 * i + 1], two, a);
+        const float x1 = two && valid ? l1[i] : 0.f, x2 = valid ? l2[i] : 0.f;
+        const float ol = valid ? of[2 * i] : 0.f, orr = valid ? of[2 * i + 1] : 0.f;
+        if constexpr (VAL) objective_point(p, c, i - p.rule.off[li], t0, t1, valid, x1, x2, ol, orr, two, a);
+        if constexpr (GRAD) {
+          const PointGrad d = grad_point(p, s_cls, s_reg, c, i - p.rule.off[li], t0, t1, valid, x1, x2, ol, orr, two);
+          if (two) put1(g1 + i, d.g1, acc);
+          put1(g2 + i, d.g2, acc);
+          put1(go + 2 * i, d.gl, acc);
+          put1(go + 2 * i + 1, d.gr, acc);
+        }
       }
     }
   }
+  if constexpr (!VAL) return;
   const float f1 = wave_sum(a.f1), f2 = wave_sum(a.f2), io = wave_sum(a.iou);
   const float np = wave_sum((float)a.npos);                       // <= 2048 per workgroup: exact in fp32
   if ((threadIdx.x & 63) == 63) {
@@ -242,12 +329,30 @@ int launch_objective(const ObjectiveArgs& a, int nrows, const float* loss_norm, 
                      float* rows_out, float* out4, hipStream_t st) {
   ProfScope prof("point_objective", st, 0.0, (a.logits1 ? 17.0 : 13.0) * (double)nrows * a.rule.S);
   if (nrows > 0) {
-    hipLaunchKernelGGL(k_objective, dim3(a.bpr, nrows), dim3(OBJ_NT), 0, st, a);
+    hipLaunchKernelGGL((k_objective<true, false>), dim3(a.bpr, nrows), dim3(OBJ_NT), 0, st, a, ObjectiveGradArgs{});
     DCF_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(k_objective_final, dim3(1), dim3(OBJ_NT), 0, st, (const float*)a.part, nrows, a.bpr, a.logits1 ? 1 : 0, loss_norm,
                      world_size, loss_weight, rows_scratch, rows_out, out4);
   DCF_HIP(hipGetLastError());
+  return 0;
+}
+
+// The gradient alone (rows_out and out4 NULL: one launch, a.part unused) or values and gradient from one pass over the inputs
+int launch_objective_grad(const ObjectiveArgs& a, const ObjectiveGradArgs& g, int nrows, float* rows_scratch, float* rows_out, float* out4,
+                          hipStream_t st) {
+  const bool val = rows_out || out4;
+  ProfScope prof(val ? "point_objective_value_grad" : "point_objective_grad", st, 0.0, (a.logits1 ? 33.0 : 25.0) * (double)nrows * a.rule.S);
+  if (nrows > 0) {
+    if (val) hipLaunchKernelGGL((k_objective<true, true>), dim3(a.bpr, nrows), dim3(OBJ_NT), 0, st, a, g);
+    else hipLaunchKernelGGL((k_objective<false, true>), dim3(a.bpr, nrows), dim3(OBJ_NT), 0, st, a, g);
+    DCF_HIP(hipGetLastError());
+  }
+  if (val) {
+    hipLaunchKernelGGL(k_objective_final, dim3(1), dim3(OBJ_NT), 0, st, (const float*)a.part, nrows, a.bpr, a.logits1 ? 1 : 0, g.loss_norm,
+                       g.world_size, g.loss_weight, rows_scratch, rows_out, out4);
+    DCF_HIP(hipGetLastError());
+  }
   return 0;
 }
 
@@ -305,6 +410,45 @@ int dcf_point_objective(const float* logits1, const float* logits2, const float*
   a.part = reinterpret_cast<float*>(scratch);
   float* rows = a.part + (size_t)(nrows > 0 ? nrows : 1) * a.bpr * 4;
   const int rc = dcf::launch_objective(a, nrows, loss_norm_dev, world_size, loss_weight, rows, rows_out, out4, st);
+  DCF_HIP(hipFreeAsync(scratch, st));
+  return rc;
+}
+
+int dcf_point_objective_grad(const float* logits1, const float* logits2, const float* offsets, const uint8_t* masks, const float* targets,
+                             int32_t nrows, int64_t T, int32_t L, double regression_range, double sigma, int32_t use_offset, int64_t max_seq_len,
+                             int32_t center_sampling, double radius, float alpha, double smoothing, int32_t iou_kind, float eps,
+                             const float* loss_norm_dev, float world_size, float loss_weight, const float* grad_total_dev,
+                             const float* grad_parts_dev, float* g_logits1, float* g_logits2, float* g_offsets, int32_t accumulate,
+                             float* rows_out, float* out4, void* stream) {
+  dcf::ObjectiveArgs a{};
+  DCF_CHECK(nrows >= 0 && (nrows == 0 || (logits2 && offsets && masks && targets && g_logits2 && g_offsets)) && (iou_kind == 0 || iou_kind == 1) &&
+                loss_norm_dev && (nrows == 0 || (logits1 == nullptr) == (g_logits1 == nullptr)),
+            "dcf_point_objective_grad: bad arguments (g_logits1 goes with logits1; loss_norm_dev is required)");
+  DCF_CHECK(dcf::make_point_rule(a.rule, T, L, regression_range, sigma, use_offset, max_seq_len, center_sampling, radius),
+            "dcf_point_objective_grad: (T = %lld, L = %d, regression_range = %g, sigma = %g, max_seq_len = %lld) is not a PtGenerator layout "
+            "(1 <= L <= 16, T a multiple of 2^(L-1), T <= max_seq_len, T < 2^23, 0 < sigma <= 1)", (long long)T, L, regression_range, sigma,
+            (long long)max_seq_len);
+  hipStream_t st = (hipStream_t)stream;
+  a.logits1 = logits1;
+  a.logits2 = logits2;
+  a.offsets = offsets;
+  a.masks = masks;
+  a.targets = targets;
+  a.vec = a.rule.S % 4 == 0 && ((uintptr_t)masks & 3) == 0 &&
+          (((uintptr_t)logits1 | (uintptr_t)logits2 | (uintptr_t)offsets | (uintptr_t)g_logits1 | (uintptr_t)g_logits2 | (uintptr_t)g_offsets) & 15) == 0;
+  a.alpha = alpha;
+  a.t_neg = (float)(smoothing / 2);                                // as dcf_point_objective
+  a.t_pos = (float)(1.0 - smoothing) + a.t_neg;
+  a.eps = eps;
+  a.kind = iou_kind;
+  a.bpr = dcf::objective_blocks_per_row(a.rule.S);
+  dcf::ObjectiveGradArgs g{g_logits1, g_logits2, g_offsets, loss_norm_dev, grad_total_dev, grad_parts_dev, world_size, loss_weight, accumulate != 0};
+  if (!rows_out && !out4) return dcf::launch_objective_grad(a, g, nrows, nullptr, nullptr, nullptr, st);
+  char* scratch = nullptr;
+  DCF_HIP(hipMallocAsync((void**)&scratch, dcf::objective_scratch_bytes(nrows > 0 ? nrows : 1, a.rule.S), st));
+  a.part = reinterpret_cast<float*>(scratch);
+  float* rows = a.part + (size_t)(nrows > 0 ? nrows : 1) * a.bpr * 4;
+  const int rc = dcf::launch_objective_grad(a, g, nrows, rows, rows_out, out4, st);
   DCF_HIP(hipFreeAsync(scratch, st));
   return rc;
 }

@@ -235,6 +235,49 @@ int dcf_point_objective(const float* logits1, const float* logits2, const float*
                         int32_t center_sampling, double radius, float alpha, double smoothing, int32_t iou_kind, float eps,
                         const float* loss_norm_dev, float world_size, float loss_weight, float* rows_out, float* out4, void* stream);
 
+/* Gradients of the point losses and of the Trainer's objective: `total_loss.backward()` (libs/worker_v2.py:467-468) cut at the
+ * three tensors the training forward returns.  Nothing below those outputs is differentiated here.  Additions to ABI version 12.
+ *
+ * Sub-gradient convention.  The reference wraps its losses in torch.jit.script, and its scripted gradient is not a stable
+ * function at the non-smooth points (ctr_diou_loss, reduction 'sum', gradient with respect to pred):
+ *
+ *   pred, gt                                  scripted reference                        same body, eager autograd
+ *   [2,3], [2,3] (both min / max tie)         [0.2, 0.2]                                [0, 0]
+ *   [0,1], [0,2] (left tie)                   [0.375, -0.625]                           [-0.03125, -0.625]
+ *   [0,0], [0,0] (union under eps)            first call [-5e7, -5e7], later [0, 0]     [-5e7, -5e7]
+ *   [0,0], [1,2]; any tie-free pair           equal                                     equal
+ *
+ * These kernels follow eager PyTorch autograd (derivatives.yaml): minimum / maximum give each argument half the gradient at
+ * a == b; clamp(min=eps) passes the gradient where x >= eps and blocks it below; `targets >= 0.5` and the label rule carry no
+ * gradient.  Away from ties and clamp edges this is what the scripted reference computes as well.
+ *
+ *   dcf_sigmoid_focal_loss_grad <- d sigmoid_focal_loss / d inputs (loss.py:5-57; every alpha, gamma, smoothing)
+ *   dcf_ctr_iou_loss_grad       <- d ctr_giou_loss / d input_offsets (loss.py:60-109, kind 0), d ctr_diou_loss (:111-166, kind 1)
+ *     grad_out (n floats / n x 2 floats) is overwritten; unselected elements get 0.  The upstream gradient is grad_elem
+ *     (n floats, reduction 'none') or *grad_scalar (one device float, 'sum' / 'mean'; NULL = 1), not both.  count_dev
+ *     (optional, one device int32, the count_out of the forward call): reduction 'mean' -- the gradient is divided by it on the
+ *     device, and a count of 0 gives zeros (`0.0 * loss.sum()`, loss.py:105,164).
+ *   dcf_point_objective_grad <- the backward of what dcf_point_objective computes, arguments as there:
+ *       g_logits_h = focal'(x_h, t) * world_size / loss_norm / n_heads * (grad_total + grad_cls)            on masks, 0 elsewhere
+ *       g_offsets  = iou'(pred, gt) * world_size / loss_norm * (loss_weight * grad_total + grad_reg)        on labels & masks, 0 elsewhere
+ *     grad_total_dev: one device float, the upstream gradient of `total` (NULL = 1).  grad_parts_dev: two device floats, the
+ *     upstream gradients of `cls` and `reg` taken on their own (NULL = 0, 0).  g_logits1 is NULL exactly when logits1 is.
+ *     accumulate != 0 adds into the g_* buffers instead of overwriting them (micro-batches, worker_v2.py:366-376).  rows_out /
+ *     out4 (both optional): when either is given the same pass also produces the values of dcf_point_objective, bit-equal to
+ *     that call.  One elementwise launch for the gradient: no atomics, no scratch, no host wait, deterministic. */
+int dcf_sigmoid_focal_loss_grad(const float* inputs, const float* targets, const uint8_t* select, int64_t n, float alpha, float gamma,
+                                int32_t smoothing, const float* grad_elem, const float* grad_scalar, const int32_t* count_dev,
+                                float* grad_out, void* stream);
+int dcf_ctr_iou_loss_grad(const float* input_offsets, const float* target_offsets, const uint8_t* select, int64_t n, int32_t kind,
+                          float eps, const float* grad_elem, const float* grad_scalar, const int32_t* count_dev, float* grad_out,
+                          void* stream);
+int dcf_point_objective_grad(const float* logits1, const float* logits2, const float* offsets, const uint8_t* masks, const float* targets,
+                             int32_t nrows, int64_t T, int32_t L, double regression_range, double sigma, int32_t use_offset, int64_t max_seq_len,
+                             int32_t center_sampling, double radius, float alpha, double smoothing, int32_t iou_kind, float eps,
+                             const float* loss_norm_dev, float world_size, float loss_weight, const float* grad_total_dev,
+                             const float* grad_parts_dev, float* g_logits1, float* g_logits2, float* g_offsets, int32_t accumulate,
+                             float* rows_out, float* out4, void* stream);
+
 /* Throughput extension: several videos of the SAME padded length T in one forward (the reference evaluates one video per
  * call, model.py:496; videos no longer than opt.model.max_vid_len are all padded to that length, worker_v2.py:969-976).
  * Video v has nq_per_video[v] queries; text / text_mask / text_len and the outputs list the queries of all videos in
