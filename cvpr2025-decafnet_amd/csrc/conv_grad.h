@@ -1,0 +1,37 @@
+// Gradients of the two operators every differentiable block of the network is built from: MaskedConv1D (k = 1 / 3, dense) and the
+// channel LayerNorm (conv_grad.hip).  Token-major (B*T, C) fp32 rows like the forward.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace dcf {
+
+// dY enters the fp16 planes of the matrix-core kernels multiplied by 2^(CG_TARGET_EXP - floor(log2 max|dY|)): its largest element
+// lands in [2^14, 2^15) whatever the loss normaliser made of it, every element within 2^-18 of the largest keeps all 22 bits of
+// the two planes, and the absolute representation error below that is 2^-40 of the largest element.
+constexpr int CG_TARGET_EXP = 14;
+constexpr int CG_MAX_SLICES = 64;       // row slices of the matrix-core weight gradient (fp32 partials per slice, summed in order)
+constexpr int CG_SMALL_SLICE = 256;     // rows per slice of the vector-ALU weight gradient (N = 1, 2)
+
+struct ConvGradArgs {
+  const float* X;          // (rows, Cin) forward input (weight gradient)
+  const float* dY;         // (rows, N)
+  const uint8_t* flags;    // (rows) bit0 = row valid (mask), bit1 = a left neighbour exists in the sequence, bit2 = a right one
+  const unsigned* absmax;  // device word: bits of max |dY|
+  float* part;             // (nslices, N, k, Cin) partial sums in the scaled domain
+  float* dbpart;           // (nslices, N) or nullptr
+  int rows, Cin, N, k, slice_rows, nslices;
+};
+
+struct LnBwdArgs {
+  const float* X; const float* w; const float* b; const float* dOut;
+  float* dX;
+  float* part;             // (nwg, 2, C): per-workgroup sums of (dy * xhat, dy), or nullptr when neither is wanted
+  int rows, C, relu, rows_per_wave;
+};
+
+int launch_absmax(const float* x, int64_t n, unsigned* word, hipStream_t st);
+int launch_wgrad(const ConvGradArgs& a, hipStream_t st);
+int launch_ln_bwd(const LnBwdArgs& a, int nwg, hipStream_t st);
+
+}  // namespace dcf

@@ -445,6 +445,30 @@ int dcf_op_conv3_split(const float* X, const uint8_t* mask, const float* W_ock, 
 /* channel LayerNorm (libs/modeling/blocks.py:125-131) per row; w/b may be NULL. */
 int dcf_op_layernorm(const float* X, const float* w, const float* b, float* Y, int32_t rows, int32_t C, int32_t relu,
                      void* stream);
+/* Backward of the two operators above (additions to ABI version 12): MaskedConv1D, dense, k = 1 / 3, padding (k - 1) / 2, and the
+ * channel LayerNorm, on token-major rows.  They differentiate
+ *   Y[b,t,n] = bias[n] + sum_j sum_c W[n,c,j] m[b,t+j-p] X[b,t+j-p,c]      (libs/modeling/blocks.py:87-106: `self.conv(x * mask_float)`;
+ *                                                                           taps stay inside sequence b, Y is not masked)
+ *   out = [relu] (LayerNorm(X) * w + b)                                     (blocks.py:125-131, two-pass, eps = 1e-5; the ReLU of
+ *                                                                           head.py:58 / :100 passes the gradient where out > 0)
+ *   dcf_op_conv_bwd_data   : dX[b,t,c] = m[b,t] sum_j sum_n dY[b,t-j+p,n] W[n,c,j]          (what autograd leaves in x.grad)
+ *   dcf_op_conv_bwd_weight : dW[n,c,j] = sum_{b,t} dY[b,t,n] m X[b,t+j-p,c],  db[n] = sum_{b,t} dY[b,t,n]   (conv.weight.grad, conv.bias.grad)
+ *   dcf_op_layernorm_bwd   : dX, dw[c] = sum_rows dy xhat, db[c] = sum_rows dy, dy = dOut where the ReLU passes
+ * W_ock / dW_ock: PyTorch's (N, Cin, k) layout.  mask (B*T bytes) NULL = every row valid.  Cin % 32 == 0; N % 32 == 0 (f16x3 on the
+ * matrix cores, the arithmetic of the forward) or N = 1, 2 (vector ALU: the heads' output convolutions); C % 32 == 0, C <= 1024;
+ * anything else fails with a message.  accumulate != 0 adds into dW / db / dw (`.grad +=`), otherwise they are overwritten; db, dw
+ * may be NULL.  dY is not assumed to be masked: a non-zero dY at a padded row is used.
+ * The fp16 planes take dY times a power of two chosen on the device from max |dY| (no host wait); sums run over fixed row slices
+ * in a fixed order without floating-point atomics, so results are bit-identical from run to run and scaling dY by a power of two
+ * scales them by exactly that.  If a sum comes out non-finite (inf / NaN operands, |X| >= 4094, |W| >= 255.9) the outputs hold the
+ * non-finite values and the NEXT call of one of these three functions returns -1 once, with a message; nothing falls back to
+ * another arithmetic. */
+int dcf_op_conv_bwd_data(const float* dY, const uint8_t* mask, const float* W_ock, float* dX, int32_t B, int32_t T, int32_t Cin,
+                         int32_t N, int32_t k, void* stream);
+int dcf_op_conv_bwd_weight(const float* X, const uint8_t* mask, const float* dY, float* dW_ock, float* db, int32_t B, int32_t T,
+                           int32_t Cin, int32_t N, int32_t k, int32_t accumulate, void* stream);
+int dcf_op_layernorm_bwd(const float* X, const float* w, const float* b, const float* dOut, float* dX, float* dw, float* db,
+                         int32_t rows, int32_t C, int32_t relu, int32_t accumulate, void* stream);
 /* cross-attention core (libs/modeling/blocks.py:374-389): Q (B*T, C), K/V (B*Lk, C), kvmask (B*Lk) -> O (B*T, C) */
 int dcf_op_xattn(const float* Q, const float* K, const float* V, const uint8_t* kvmask, float* O, int32_t B, int32_t T,
                  int32_t Lk, int32_t C, int32_t heads, void* stream);
