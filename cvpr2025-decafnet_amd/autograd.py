@@ -1,13 +1,16 @@
-"""Differentiable MaskedConv1D and channel LayerNorm on the MI355X, and a prediction head composed of them.
+"""Differentiable MaskedConv1D, channel LayerNorm and sliding-window attention on the MI355X, and blocks composed of them.
 
-``masked_conv1d`` and ``channel_layer_norm`` are ``torch.autograd.Function``s over the library's single-operator entry points:
-the forwards are the kernels the network's forward runs (dcf_op_conv3_split / dcf_op_linear_split / dcf_op_layernorm), the
-backwards are dcf_op_conv_bwd_data / dcf_op_conv_bwd_weight / dcf_op_layernorm_bwd (csrc/conv_grad.hip), all on the current
-stream and without a host wait.  Tensors are token-major ``(B, T, C)`` fp32 on the GPU; there is no CPU path.
+``masked_conv1d``, ``channel_layer_norm`` and ``window_attention`` are ``torch.autograd.Function``s over the library's
+single-operator entry points: the forwards are the kernels the network's forward runs (dcf_op_conv3_split / dcf_op_linear_split /
+dcf_op_layernorm / dcf_op_local_attn), the backwards are dcf_op_conv_bwd_data / dcf_op_conv_bwd_weight / dcf_op_layernorm_bwd
+(csrc/conv_grad.hip) and dcf_op_local_attn_bwd (csrc/attn_grad.hip), all on the current stream and without a host wait.  Tensors
+are token-major ``(B, T, C)`` fp32 on the GPU; there is no CPU path.
 
-``conv_head`` runs one pyramid level through a ClsHead / RegHead (libs/modeling/head.py:53-64, :95-108) built from the two, so a
-head trains end to end with ``loss.PointObjective``.  It is a demonstration of the operators, not the training forward:
-``forward(..., eval=False)`` still returns plain tensors and the gradient of the network stops at the pyramid features.
+``conv_head`` runs one pyramid level through a ClsHead / RegHead (libs/modeling/head.py:53-64, :95-108) and ``masked_mha`` runs the
+local-window MaskedMHA of an encoder block (blocks.py:348-373, :391-392), so a head -- and the attention in front of it -- trains end
+to end with ``loss.PointObjective``.  Both demonstrate the operators, they are not the training forward: ``forward(..., eval=False)``
+still returns plain tensors.  Of a TransformerEncoder block the depthwise q / k / v convolutions, the stride-2 pooling skip and the
+attention-map dropout have no backward yet, and neither has the cross attention of the fusion blocks.
 """
 import torch
 
@@ -116,6 +119,38 @@ class _ChannelLayerNormFn(torch.autograd.Function):
                 gb.reshape(ctx.shapes[1]) if gb is not None else None, None)
 
 
+class _WindowAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, mask, n_heads, window):
+        qd, kd, vd = (_rows(z, 'window_attention') for z in (q, k, v))
+        B, T, C = qd.shape
+        if kd.shape != qd.shape or vd.shape != qd.shape:
+            raise ValueError(f'window_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
+        if window <= 0 or window % 2 == 0:
+            raise ValueError(f'window_attention: window = {window} must be odd and positive (global attention has no backward)')
+        m = _mask_rows(mask, B, T)
+        if m is None:
+            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)       # the forward core reads its mask unconditionally
+        o = torch.empty_like(qd)
+        _lib.check(_lib.lib().dcf_op_local_attn(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, C, int(n_heads), int(window),
+                                                _lib.current_stream()), 'dcf_op_local_attn')
+        ctx.save_for_backward(qd, kd, vd, m)
+        ctx.n_heads, ctx.window = int(n_heads), int(window)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, m = ctx.saved_tensors
+        B, T, C = q.shape
+        go = go.float().contiguous()
+        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
+        if gq is not None or gk is not None or gv is not None:
+            _lib.check(_lib.lib().dcf_op_local_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
+                                                        _lib.ptr(gv), B, T, C, ctx.n_heads, ctx.window, _lib.current_stream()),
+                       'dcf_op_local_attn_bwd')
+        return gq, gk, gv, None, None, None
+
+
 def masked_conv1d(x, mask, weight, bias=None):
     """MaskedConv1D.forward (blocks.py:87-106; stride 1, groups 1, k = 1 or 3, padding (k - 1) / 2) on token-major ``x`` (B, T, Cin):
     ``conv(x * mask) + bias`` -> (B, T, N).  ``mask``: (B, T) or (B, 1, T) bool, None = all valid; ``weight``: (N, Cin, k)."""
@@ -141,3 +176,23 @@ def conv_head(x, mask, head, level=None):
         return torch.relu(head.scales[level].scale * masked_conv1d(x, mask, out.weight, out.bias))
     out = head.cls_head.conv
     return masked_conv1d(x, mask, out.weight, out.bias).squeeze(-1)
+
+
+def window_attention(q, k, v, mask, n_heads, window):
+    """The sliding-window attention core of MaskedMHA (blocks.py:204-325, :357-373) on token-major ``q`` / ``k`` / ``v`` (B, T, C), heads
+    concatenated along C: softmax over the keys |j - t| <= window // 2 of the sequence, d^-1/4 on q and on k, -1e4 on padded keys,
+    zero rows at padded queries -> (B, T, C).  ``mask``: (B, T) or (B, 1, T) bool, None = all valid; ``window`` odd and positive."""
+    return _WindowAttentionFn.apply(q, k, v, mask, n_heads, window)
+
+
+def masked_mha(q_in, k_in, v_in, mask, mha):
+    """MaskedMHA.forward (blocks.py:327-373, :391-393; local branch, no dropout) on token-major inputs (B, T, C), with ``mha`` a
+    modeling.MaskedMHA of ``window_size > 0``: proj(window_attention(query(q_in), key(k_in), value(v_in))).  The four projections are
+    k = 1 convolutions that do not mask their input (the reference's are plain nn.Conv1d)."""
+    if mha.window_size <= 0:
+        raise ValueError('masked_mha: a MaskedMHA with window_size > 0 is required (global attention has no backward)')
+    q = masked_conv1d(q_in, None, mha.query.weight, mha.query.bias)
+    k = masked_conv1d(k_in, None, mha.key.weight, mha.key.bias)
+    v = masked_conv1d(v_in, None, mha.value.weight, mha.value.bias)
+    ctx = window_attention(q, k, v, mask, mha.n_heads, mha.window_size)
+    return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)

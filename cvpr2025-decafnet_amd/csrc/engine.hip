@@ -25,6 +25,7 @@
 
 #include "../../include/decafnet_hip.h"
 #include "attn.h"
+#include "attn_grad.h"
 #include "common.h"
 #include "dec_chain.h"
 #include "dropout.h"
@@ -2913,6 +2914,19 @@ int dcf_op_local_attn(const float* Q, const float* K, const float* V, const uint
   }
   dcf::LocalAttnArgs a{Q, K, V, mask, O, B, T, C, heads, window};
   return dcf::launch_local_attn(a, (hipStream_t)stream);
+}
+
+int dcf_op_local_attn_bwd(const float* Q, const float* K, const float* V, const uint8_t* mask, const float* dO, float* dQ, float* dK,
+                          float* dV, int32_t B, int32_t T, int32_t C, int32_t heads, int32_t window, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  dcf::LocalAttnGradArgs a{Q, K, V, mask, dO, dQ, dK, dV, nullptr, B, T, C, heads, window};
+  DCF_CHECK(B > 0 && T > 0 && heads > 0, "dcf_op_local_attn_bwd: empty batch (B=%d T=%d heads=%d)", B, T, heads);
+  if (!dK && !dV) return dcf::launch_local_attn_bwd(a, st);
+  // the row statistics the key-side gather reads: stream-ordered scratch, no host wait
+  DCF_HIP(hipMallocAsync((void**)&a.stats, dcf::local_attn_grad_stats_bytes((int64_t)B * T, heads), st));
+  const int rc = dcf::launch_local_attn_bwd(a, st);
+  DCF_HIP(hipFreeAsync(a.stats, st));
+  return rc;
 }
 
 int dcf_op_sidekick(const float* shallow, const float* text_cls, float* correl, int32_t D, int32_t T, int32_t nq,

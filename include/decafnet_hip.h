@@ -476,6 +476,24 @@ int dcf_op_xattn(const float* Q, const float* K, const float* V, const uint8_t* 
  * every valid key of the sequence (blocks.py:339-356, :374-393; head dimension 32 or 64) */
 int dcf_op_local_attn(const float* Q, const float* K, const float* V, const uint8_t* mask, float* O, int32_t B, int32_t T,
                       int32_t C, int32_t heads, int32_t window, void* stream);
+/* Backward of the sliding-window core above for window > 0 (addition to ABI version 12).  It differentiates, per sequence b, head h
+ * (head dimension d, channels h*d .. h*d + d - 1 of a row) and query row t, with half = window / 2 and scale = d^-1/4:
+ *   s[t,j] = (scale q[t]) . (scale k[j]) + pen[j]     for |j - t| <= half, 0 <= j < T      (keys outside the sequence do not exist)
+ *   pen[j] = -1e4 if key j is padded, else 0                                               (blocks.py:279: finite)
+ *   p[t,.] = softmax_j s[t,j],  O[t] = sum_j p[t,j] v[j];   O[t] = 0 and p[t,.] = 0 if QUERY t is padded   (blocks.py:293)
+ * and returns, given dO,
+ *   dP[t,j] = dO[t] . v[j],   delta[t] = sum_j p[t,j] dP[t,j],   dS[t,j] = p[t,j] (dP[t,j] - delta[t])
+ *   dV[j] = sum_t p[t,j] dO[t],   dQ[t] = scale^2 sum_j dS[t,j] k[j],   dK[j] = scale^2 sum_t dS[t,j] q[t]
+ * with the sums over t running over the live queries whose window holds j.  Q / K / V / dO / dQ / dK / dV: (B*T, C) token-major fp32,
+ * mask (B*T bytes) NULL = every row valid.  Any of dQ / dK / dV may be NULL: the work that only feeds it is skipped and the others
+ * keep their bits.  Shapes: those of the forward (power-of-two head dimension in [4, 256], C % 4 == 0, C <= 1024), window odd;
+ * window = 0 (global attention) and anything else unsupported fail with a message.  dO is not assumed to be masked, but a padded
+ * query row passes nothing on: dQ is exactly 0 there, and dK = dV = 0 exactly at a padded key row (exp(-1e4 - m) is 0).
+ * fp32 on the vector ALU; dK / dV are gathered per key row in ascending t, without floating-point atomics: results are bit-identical
+ * from run to run and scaling dO by a power of two scales them by exactly that.  The per-row softmax statistics live in scratch
+ * that is allocated and freed on `stream`; no host wait. */
+int dcf_op_local_attn_bwd(const float* Q, const float* K, const float* V, const uint8_t* mask, const float* dO, float* dQ, float* dK,
+                          float* dV, int32_t B, int32_t T, int32_t C, int32_t heads, int32_t window, void* stream);
 /* sidekick scoring (model.py:500-505): shallow (D, T) channel-major, text_cls (nq, D) -> correl (nq, T) */
 int dcf_op_sidekick(const float* shallow, const float* text_cls, float* correl, int32_t D, int32_t T, int32_t nq,
                     int32_t norm, void* stream);
