@@ -29,7 +29,7 @@ from test_conv_grad_cpu import FIXTURES, fixture_case
 
 pytestmark = pytest.mark.gpu
 FLOOR = 2.0 ** -21
-E2E_TOL = dict(rtol=2e-4, atol=2e-4)          # tests/test_gpu_e2e.py TOL
+E2E_TOL = dict(rtol=2e-4, atol=2e-4)          # what tests/test_gpu_e2e.py used before its gates moved to the rule
 
 
 def check(tag, got, g64, g32):

@@ -12,7 +12,7 @@ import philox_ref as P
 from conftest import Golden, load_pkg
 
 pytestmark = pytest.mark.gpu
-TOL = dict(rtol=2e-4, atol=2e-4)          # test_gpu_e2e.py's
+TOL = dict(rtol=2e-4, atol=2e-4)          # the former TOL of test_gpu_e2e.py (no fp64 side here: the oracle draws no masks)
 
 
 def keep_gpu(pkg, seed, site, e0, n, p):

@@ -17,7 +17,7 @@ import objective_cases as C
 
 pytestmark = pytest.mark.gpu
 TOL_SUM = dict(rtol=2e-5, atol=1e-6)          # loss sums against the reference (tests/test_gpu_e2e.py, the loss block)
-TOL_E2E = dict(rtol=2e-4, atol=2e-4)          # tests/test_gpu_e2e.py TOL: the forward's own error enters
+TOL_E2E = dict(rtol=2e-4, atol=2e-4)          # the former TOL of tests/test_gpu_e2e.py: the forward's own error enters
 
 
 def digest(t):

@@ -1,5 +1,8 @@
 """Pin the CPU oracle (oracle/) against fixtures produced by the real reference
-(tests/golden/make_golden.py).  CPU only."""
+(tests/golden/make_golden.py).  CPU only.
+
+The fp32 oracle's logits and offsets are held to the fixtures at 2e-5 (measured: within 3.2e-6 of the fp64 oracle, which
+tests/test_forward_parity_cpu.py pins to the same fixtures at 1e-5; profiles/forward_parity.md)."""
 import os
 import sys
 
@@ -170,8 +173,8 @@ def test_end_to_end(name):
         close(inter['per_query'][q]['vid_map'], g.t(f'q{q}/vid_map'), atol=2e-5)
         close(inter['per_query'][q]['fused'], g.t(f'q{q}/fused'), atol=5e-5)
         for l in range(kw['n_levels']):
-            close(logits[q][l], g.t(f'q{q}/l{l}/logits'), atol=1e-4, rtol=1e-4)
-            close(offsets[q][l], g.t(f'q{q}/l{l}/offsets'), atol=1e-4, rtol=1e-4)
+            close(logits[q][l], g.t(f'q{q}/l{l}/logits'), atol=2e-5, rtol=2e-5)
+            close(offsets[q][l], g.t(f'q{q}/l{l}/offsets'), atol=2e-5, rtol=2e-5)
             assert torch.equal(masks[q][l], g.t(f'q{q}/l{l}/mask'))
     pts = R.generate_points(kw['max_seq_len'] * 10, kw['n_levels'], 4, 0.5)
     for l in range(kw['n_levels']):
@@ -229,7 +232,7 @@ def test_training_forward_and_losses_match_reference():
             if name == 'masks':
                 assert torch.equal(part[l], want)
             else:
-                torch.testing.assert_close(part[l], want, rtol=1e-4, atol=1e-4)
+                torch.testing.assert_close(part[l], want, rtol=2e-5, atol=2e-5)
     l1 = torch.cat([g.t(f'logits1/l{l}') for l in range(L)], 1)
     l2 = torch.cat([g.t(f'logits2/l{l}') for l in range(L)], 1)
     off = torch.cat([g.t(f'offsets/l{l}') for l in range(L)], 1)
@@ -270,7 +273,7 @@ def test_training_forward_of_the_single_head_classes_matches_reference(name):
             if pn == 'masks':
                 assert torch.equal(part[l], want)
             else:
-                torch.testing.assert_close(part[l], want, rtol=1e-4, atol=1e-4)
+                torch.testing.assert_close(part[l], want, rtol=2e-5, atol=2e-5)
 
 
 # ------------------------------------------------------------------ G5
@@ -350,8 +353,8 @@ def test_secondary_compositions(name):
                              second_fusion=True)
     for q in range(meta['nq']):
         for l in range(kw['n_levels']):
-            close(out[0][q][l], g.t(f'q{q}/l{l}/logits'), atol=1e-4, rtol=1e-4)
-            close(out[1][q][l], g.t(f'q{q}/l{l}/offsets'), atol=1e-4, rtol=1e-4)
+            close(out[0][q][l], g.t(f'q{q}/l{l}/logits'), atol=2e-5, rtol=2e-5)
+            close(out[1][q][l], g.t(f'q{q}/l{l}/offsets'), atol=2e-5, rtol=2e-5)
             assert torch.equal(out[2][q][l], g.t(f'q{q}/l{l}/mask'))
 
 
