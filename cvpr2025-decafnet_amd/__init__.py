@@ -6,8 +6,8 @@ The directory name is not a valid Python identifier; import it with
 Sub-modules: ``modeling`` (libs/modeling drop-in), ``nms`` (libs/nms drop-in), ``evaluator``
 (the Evaluator hot-path harness), ``config`` / ``synth`` (plain-dict opt tree, synthetic data),
 ``data`` (feature files, text-CLS table, annotation file -> per-video dicts), ``dropin`` (runs the reference's own
-``eval.py`` / ``Evaluator`` on this package without editing it), ``loss`` (libs/modeling/loss.py forward values), ``autograd`` (differentiable MaskedConv1D / channel LayerNorm and a head
-composed of them), ``dist`` (T-sharding over ranks), ``build`` (hipcc driver),
+``eval.py`` / ``Evaluator`` on this package without editing it), ``loss`` (libs/modeling/loss.py forward values), ``autograd`` (differentiable MaskedConv1D / channel LayerNorm / window attention /
+depthwise convolution / max pooling / GELU / LayerScale residual, and heads and whole TransformerEncoder blocks composed of them), ``dist`` (T-sharding over ranks), ``build`` (hipcc driver),
 ``_lib`` (ctypes binding of the C ABI).
 """
 from . import config, synth  # noqa: F401

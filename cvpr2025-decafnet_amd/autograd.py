@@ -1,16 +1,22 @@
-"""Differentiable MaskedConv1D, channel LayerNorm and sliding-window attention on the MI355X, and blocks composed of them.
+"""Differentiable operators of the video encoder on the MI355X, and blocks composed of them, up to a whole TransformerEncoder block.
 
-``masked_conv1d``, ``channel_layer_norm`` and ``window_attention`` are ``torch.autograd.Function``s over the library's
-single-operator entry points: the forwards are the kernels the network's forward runs (dcf_op_conv3_split / dcf_op_linear_split /
-dcf_op_layernorm / dcf_op_local_attn), the backwards are dcf_op_conv_bwd_data / dcf_op_conv_bwd_weight / dcf_op_layernorm_bwd
-(csrc/conv_grad.hip) and dcf_op_local_attn_bwd (csrc/attn_grad.hip), all on the current stream and without a host wait.  Tensors
+``masked_conv1d``, ``channel_layer_norm``, ``window_attention``, ``depthwise_conv1d``, ``masked_max_pool1d``, ``gelu`` and
+``layer_scale_residual`` are ``torch.autograd.Function``s over the library's single-operator entry points.  The forwards of the first
+three are the kernels the network's forward runs (dcf_op_conv3_split / dcf_op_linear_split / dcf_op_layernorm / dcf_op_local_attn), their
+backwards are dcf_op_conv_bwd_data / dcf_op_conv_bwd_weight / dcf_op_layernorm_bwd (csrc/conv_grad.hip) and dcf_op_local_attn_bwd
+(csrc/attn_grad.hip); the other four are the forward / backward pairs of csrc/enc_grad.hip (dcf_op_dwconv3, dcf_op_masked_maxpool,
+dcf_op_gelu, dcf_op_layerscale_residual and their ``_bwd``).  Everything runs on the current stream and without a host wait.  Tensors
 are token-major ``(B, T, C)`` fp32 on the GPU; there is no CPU path.
 
-``conv_head`` runs one pyramid level through a ClsHead / RegHead (libs/modeling/head.py:53-64, :95-108) and ``masked_mha`` runs the
-local-window MaskedMHA of an encoder block (blocks.py:348-373, :391-392), so a head -- and the attention in front of it -- trains end
-to end with ``loss.PointObjective``.  Both demonstrate the operators, they are not the training forward: ``forward(..., eval=False)``
-still returns plain tensors.  Of a TransformerEncoder block the depthwise q / k / v convolutions, the stride-2 pooling skip and the
-attention-map dropout have no backward yet, and neither has the cross attention of the fusion blocks.
+``conv_head`` runs one pyramid level through a ClsHead / RegHead (libs/modeling/head.py:53-64, :95-108), ``masked_mha`` the
+local-window MaskedMHA (blocks.py:348-373, :391-392), ``ffn`` the FFN (blocks.py:535-538), ``conv_attn_layer`` a ConvAttNLayer
+(blocks.py:462-473) and ``transformer_encoder`` a whole TransformerEncoder block of the video encoder (blocks.py:578-591; stride 1 or 2,
+local window), so the stem, every pyramid level and the heads behind them train end to end with ``loss.PointObjective``.  There is no
+dropout and no drop-path in any of these functions: they are the reference's blocks with every dropout probability at 0.  They
+demonstrate the operators, they are not the training forward: ``forward(..., eval=False)`` still returns plain tensors.
+
+Without a backward yet: the cross attention and the AdaLN of the fusion blocks, the k = 5 / stride-2 embedding convolutions, global
+attention (the text encoder; stride 0 / window 0 blocks are refused here), the refinement TCN and the gate.
 """
 import torch
 
@@ -81,13 +87,15 @@ class _MaskedConv1dFn(torch.autograd.Function):
             gx = torch.empty_like(x)
             _lib.check(L.dcf_op_conv_bwd_data(_lib.ptr(gy), _lib.ptr(m), _lib.ptr(w), _lib.ptr(gx), B, T, Cin, N, k, st), 'dcf_op_conv_bwd_data')
         want_b = ctx.has_bias and ctx.needs_input_grad[3]
-        if ctx.needs_input_grad[2]:
+        if ctx.needs_input_grad[2] or want_b:
+            # a bias whose weight is frozen still takes its sum from the weight kernel (db rides along with dW there): the same bits
+            # whether or not the weight asks for a gradient
             gw = torch.empty_like(w)
             gb = torch.empty(N, dtype=torch.float32, device=x.device) if want_b else None
             _lib.check(L.dcf_op_conv_bwd_weight(_lib.ptr(x), _lib.ptr(m), _lib.ptr(gy), _lib.ptr(gw), _lib.ptr(gb), B, T, Cin, N, k, 0, st),
                        'dcf_op_conv_bwd_weight')
-        elif want_b:
-            gb = gy.sum((0, 1))
+            if not ctx.needs_input_grad[2]:
+                gw = None
         return gx, None, gw, gb
 
 
@@ -196,3 +204,215 @@ def masked_mha(q_in, k_in, v_in, mask, mha):
     v = masked_conv1d(v_in, None, mha.value.weight, mha.value.bias)
     ctx = window_attention(q, k, v, mask, mha.n_heads, mha.window_size)
     return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
+
+
+def _byte_mask(mask, B, T, name):
+    """(B, T) bool on the GPU or None, from (B, T) / (B, 1, T) of any integer type"""
+    m = _mask_rows(mask, B, T)
+    if m is not None and not m.is_cuda:
+        raise RuntimeError(f'{name}: the mask must be on the GPU (there is no CPU path)')
+    return m
+
+
+class _DepthwiseConv1dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, stride, *weights):
+        B, T, C = x.shape
+        n = len(weights)
+        if stride not in (1, 2) or T % stride:
+            raise ValueError(f'depthwise_conv1d: stride = {stride} must be 1 or 2 and divide T = {T}')
+        if not 1 <= n <= 3 or any(tuple(w.shape) != (C, 1, 3) for w in weights):
+            raise ValueError(f'depthwise_conv1d: one to three (C, 1, 3) weights on {C} channels are required (k = 3, groups = C), got '
+                             f'{[tuple(w.shape) for w in weights]}')
+        xd = _rows(x, 'depthwise_conv1d')
+        m = _byte_mask(mask, B, T, 'depthwise_conv1d')
+        w = torch.stack([z.detach().float().reshape(C, 3) for z in weights]).contiguous()
+        y = torch.empty(n, B, T // stride, C, dtype=torch.float32, device=xd.device)
+        _lib.check(_lib.lib().dcf_op_dwconv3(_lib.ptr(xd), _lib.ptr(m), _lib.ptr(w), _lib.ptr(y), B, T, C, n, stride, _lib.current_stream()),
+                   'dcf_op_dwconv3')
+        ctx.save_for_backward(xd, m, w)
+        ctx.stride = stride
+        return tuple(y.unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gys):
+        x, m, w = ctx.saved_tensors
+        B, T, C = x.shape
+        n = w.size(0)
+        gy = torch.stack([g.float() for g in gys]).contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gw = torch.empty_like(w) if any(ctx.needs_input_grad[3:]) else None
+        if gx is not None or gw is not None:
+            _lib.check(_lib.lib().dcf_op_dwconv3_bwd(_lib.ptr(x), _lib.ptr(m), _lib.ptr(w), _lib.ptr(gy), _lib.ptr(gx), _lib.ptr(gw), B, T, C, n,
+                                                     ctx.stride, 0, _lib.current_stream()), 'dcf_op_dwconv3_bwd')
+        gws = tuple(gw[i].reshape(C, 1, 3) if need else None for i, need in enumerate(ctx.needs_input_grad[3:]))
+        return (gx, None, None) + gws
+
+
+class _MaskedMaxPool1dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask):
+        B, T, C = x.shape
+        if T % 2:
+            raise ValueError(f'masked_max_pool1d: T = {T} must be a multiple of the stride 2')
+        xd = _rows(x, 'masked_max_pool1d')
+        m = _byte_mask(mask, B, T, 'masked_max_pool1d')
+        y = torch.empty(B, T // 2, C, dtype=torch.float32, device=xd.device)
+        mo = torch.empty(B, T // 2, dtype=torch.bool, device=xd.device)
+        _lib.check(_lib.lib().dcf_op_masked_maxpool(_lib.ptr(xd), _lib.ptr(m), _lib.ptr(y), _lib.ptr(mo), B, T, C, _lib.current_stream()),
+                   'dcf_op_masked_maxpool')
+        ctx.save_for_backward(xd, m)
+        ctx.mark_non_differentiable(mo)
+        return y, mo
+
+    @staticmethod
+    def backward(ctx, gy, _):
+        x, m = ctx.saved_tensors
+        B, T, C = x.shape
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        gx = torch.empty_like(x)
+        _lib.check(_lib.lib().dcf_op_masked_maxpool_bwd(_lib.ptr(x), _lib.ptr(m), _lib.ptr(gy.float().contiguous()), _lib.ptr(gx), B, T, C,
+                                                        _lib.current_stream()), 'dcf_op_masked_maxpool_bwd')
+        return gx, None
+
+
+class _GeluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        if not (torch.is_tensor(x) and x.is_cuda):
+            raise RuntimeError('gelu: a tensor on the GPU is required (there is no CPU path)')
+        xd = x.detach().float().contiguous()
+        y = torch.empty_like(xd)
+        if xd.numel():
+            _lib.check(_lib.lib().dcf_op_gelu(_lib.ptr(xd), _lib.ptr(y), xd.numel(), _lib.current_stream()), 'dcf_op_gelu')
+        ctx.save_for_backward(xd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        if x.numel():
+            _lib.check(_lib.lib().dcf_op_gelu_bwd(_lib.ptr(x), _lib.ptr(gy.float().contiguous()), _lib.ptr(gx), x.numel(), _lib.current_stream()),
+                       'dcf_op_gelu_bwd')
+        return gx
+
+
+class _LayerScaleResidualFn(torch.autograd.Function):
+    """h None: y = r * r_mask (how transformer_encoder masks its input, blocks.py:581)"""
+
+    @staticmethod
+    def forward(ctx, r, h, scale, r_mask, h_mask):
+        B, T, C = r.shape
+        rd = _rows(r, 'layer_scale_residual')
+        hd = ls = None
+        if h is not None:
+            hd = _rows(h, 'layer_scale_residual')
+            if hd.shape != rd.shape or scale.numel() != C:
+                raise ValueError(f'layer_scale_residual: r {tuple(r.shape)}, h {tuple(h.shape)}, scale {tuple(scale.shape)} do not agree')
+            ls = scale.detach().float().reshape(C).contiguous()
+        mr, mh = _byte_mask(r_mask, B, T, 'layer_scale_residual'), _byte_mask(h_mask, B, T, 'layer_scale_residual')
+        y = torch.empty_like(rd)
+        _lib.check(_lib.lib().dcf_op_layerscale_residual(_lib.ptr(rd), _lib.ptr(mr), _lib.ptr(hd), _lib.ptr(mh), _lib.ptr(ls), _lib.ptr(y), B * T, C,
+                                                         _lib.current_stream()), 'dcf_op_layerscale_residual')
+        ctx.save_for_backward(hd, ls, mr, mh)
+        ctx.scale_shape = None if scale is None else scale.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        h, ls, mr, mh = ctx.saved_tensors
+        B, T, C = gy.shape
+        gy = gy.float().contiguous()
+        need_r, need_h, need_s = ctx.needs_input_grad[:3]
+        need_h, need_s = need_h and h is not None, need_s and h is not None
+        gr = torch.empty_like(gy) if need_r else None
+        gh = torch.empty_like(gy) if need_h else None
+        gs = torch.empty(C, dtype=torch.float32, device=gy.device) if need_s else None
+        if need_r or need_h or need_s:
+            _lib.check(_lib.lib().dcf_op_layerscale_residual_bwd(_lib.ptr(gy), _lib.ptr(h), _lib.ptr(mr), _lib.ptr(mh), _lib.ptr(ls), _lib.ptr(gr),
+                                                                 _lib.ptr(gh), _lib.ptr(gs), B * T, C, 0, _lib.current_stream()),
+                       'dcf_op_layerscale_residual_bwd')
+        return gr, gh, gs.reshape(ctx.scale_shape) if gs is not None else None, None, None
+
+
+def depthwise_conv1d(x, mask, weights, stride=1):
+    """One to three depthwise MaskedConv1D (blocks.py:87-106 with groups = C: k = 3, padding 1, no bias, stride 1 or 2) sharing the
+    token-major input ``x`` (B, T, C): ``conv_i(x * mask)``, not masked afterwards -> (tuple of (B, T / stride, C), ``mask[:, ::stride]``).
+    ``weights``: a sequence of PyTorch's (C, 1, 3) weights (q / k / v_conv of a ConvAttNLayer); ``mask``: (B, T) or (B, 1, T), None = all
+    valid (then the returned mask is None)."""
+    B, T, _ = x.shape
+    ys = _DepthwiseConv1dFn.apply(x, mask, int(stride), *weights)
+    m = _mask_rows(mask, B, T)
+    return ys, (None if m is None else m[:, ::int(stride)].contiguous())
+
+
+def masked_max_pool1d(x, mask):
+    """masked_max_pool1d (blocks.py:31-47) with kernel 3, stride 2, padding 1 on token-major ``x`` (B, T, C), T even: padded slots take the
+    (detached) minimum of their channel over the sequence, windows stay inside the sequence, the result is multiplied by the pooled mask
+    -> ((B, T / 2, C), pooled mask (B, T / 2)).  The gradient goes to the lowest position that holds a window's maximum."""
+    return _MaskedMaxPool1dFn.apply(x, mask)
+
+
+def gelu(x):
+    """nn.GELU() of FFN.actv (blocks.py:531): ``x * Phi(x)`` elementwise, any shape."""
+    return _GeluFn.apply(x)
+
+
+def layer_scale_residual(r, h, scale, r_mask=None, h_mask=None):
+    """A residual through LayerScale (blocks.py:670-682 with pdrop = 0): ``r * r_mask + scale * (h * h_mask)`` on token-major (B, T, C),
+    ``scale`` of C elements in any shape (the reference keeps (1, C, 1)); blocks.py:586 is ``r_mask = mask``, :589-590 ``h_mask = mask``."""
+    return _LayerScaleResidualFn.apply(r, h, scale, r_mask, h_mask)
+
+
+def ffn(x, ffn_module):
+    """FFN.forward (blocks.py:535-538, no dropout) on token-major ``x`` (B, T, C), with ``ffn_module`` a modeling.FFN:
+    proj(gelu(fc(x))), the two k = 1 convolutions unmasked (the reference's are plain nn.Conv1d).  Saved for the backward: ``x`` (by fc),
+    the pre-activation fc(x) (by gelu, which recomputes Phi and phi from it) and gelu(fc(x)) (by proj, as the operand of its weight
+    gradient) -- two (B, T, 4 C) tensors per call."""
+    h = masked_conv1d(x, None, ffn_module.fc.weight, ffn_module.fc.bias)
+    return masked_conv1d(gelu(h), None, ffn_module.proj.weight, ffn_module.proj.bias)
+
+
+def conv_attn_layer(x, mask, layer):
+    """ConvAttNLayer.forward (blocks.py:462-473; no dropout) on token-major ``x`` (B, T, C), with ``layer`` a modeling.ConvAttNLayer of
+    stride 1 or 2 and ``window_size > 0``: q / k / v = {q,k,v}_norm({q,k,v}_conv(x, mask)), then the local MaskedMHA under the strided
+    mask -> ((B, T / stride, C), ``mask[:, ::stride]``)."""
+    if not hasattr(layer, 'q_conv'):
+        raise ValueError('conv_attn_layer: stride 0 (no depthwise convolutions: the text encoder) has no backward here')
+    if layer.attn.window_size <= 0:
+        raise ValueError('conv_attn_layer: window_size = 0 (global attention) has no backward')
+    B, T, _ = x.shape
+    if mask is None:
+        mask = torch.ones(B, T, dtype=torch.bool, device=x.device)
+    (q, k, v), mask = depthwise_conv1d(x, mask, [layer.q_conv.conv.weight, layer.k_conv.conv.weight, layer.v_conv.conv.weight], layer.q_conv.stride)
+    q = channel_layer_norm(q, layer.q_norm.weight, layer.q_norm.bias)
+    k = channel_layer_norm(k, layer.k_norm.weight, layer.k_norm.bias)
+    v = channel_layer_norm(v, layer.v_norm.weight, layer.v_norm.bias)
+    return masked_mha(q, k, v, mask, layer.attn), mask
+
+
+def transformer_encoder(x, mask, block):
+    """TransformerEncoder.forward (blocks.py:578-591) on token-major ``x`` (B, T, C), with ``block`` a modeling.TransformerEncoder of
+    stride 1 or 2 and ``window_size > 0`` (a stem or pyramid block of the video encoder) -> (y (B, T / stride, C), ``mask[:, ::stride]``).
+    To the letter: the input is multiplied by the mask (:581); at stride 2 the skip is masked_max_pool1d of that (:584) but is masked
+    with the convolution's mask ``mask[:, ::2]``, not with the pooled one (:586); the output is not masked, so padded rows hold
+    ``drop_path_attn.scale * attn.proj.bias``.  No attention / projection dropout and no
+    drop-path: the block with every dropout probability at 0."""
+    if block.stride not in (1, 2):
+        raise ValueError(f'transformer_encoder: stride = {block.stride}: only the video encoder\'s blocks (stride 1 or 2) have a backward; '
+                         f'stride 0 is the text encoder')
+    if block.window_size <= 0:
+        raise ValueError('transformer_encoder: window_size = 0 (global attention) has no backward')
+    B, T, _ = x.shape
+    if T % block.stride:
+        raise ValueError(f'transformer_encoder: T = {T} must be a multiple of the stride {block.stride}')
+    if mask is None:
+        mask = torch.ones(B, T, dtype=torch.bool, device=x.device)
+    x = _LayerScaleResidualFn.apply(x, None, None, mask, None)
+    skip = masked_max_pool1d(x, mask)[0] if block.stride == 2 else x
+    h, mask = conv_attn_layer(channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias), mask, block.attn)
+    x = layer_scale_residual(skip, h, block.drop_path_attn.scale, r_mask=mask)
+    h = ffn(channel_layer_norm(x, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn)
+    return layer_scale_residual(x, h, block.drop_path_ffn.scale, h_mask=mask), mask

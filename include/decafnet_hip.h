@@ -494,6 +494,46 @@ int dcf_op_local_attn(const float* Q, const float* K, const float* V, const uint
  * that is allocated and freed on `stream`; no host wait. */
 int dcf_op_local_attn_bwd(const float* Q, const float* K, const float* V, const uint8_t* mask, const float* dO, float* dQ, float* dK,
                           float* dV, int32_t B, int32_t T, int32_t C, int32_t heads, int32_t window, void* stream);
+/* Forward / backward pairs of what a TransformerEncoder block (libs/modeling/blocks.py:541-591) needs besides the operators above
+ * (additions to ABI version 12; csrc/enc_grad.hip).  Conventions of all eight: token-major fp32 rows (B*T, C), C % 4 == 0, C <= 1024,
+ * 16-byte aligned pointers; a mask is B*T bytes, NULL = every row valid; everything runs on `stream` without a host wait, scratch is
+ * allocated and freed on it; no floating-point atomics -- the two column reductions (dW, dls) run over fixed row slices and a balanced
+ * tree in a fixed order, so results are bit-identical from run to run and scaling the upstream gradient by a power of two scales them
+ * by exactly that; an output pointer that is NULL skips the work that only feeds it; accumulate != 0 adds into the parameter gradient
+ * (`.grad +=`); unsupported shapes fail with a message.  The upstream gradient is not assumed to be masked.
+ *
+ * Depthwise MaskedConv1D (blocks.py:87-106 with groups = C; k = 3, padding 1, no bias, stride s = 1 or 2 dividing T), n = 1 .. 3
+ * convolutions sharing one input (n = 3: q / k / v_conv of ConvAttNLayer, blocks.py:437-445, :464-466; n = 1: a pool_only branch
+ * layer, the decoder's q_conv).  W (n, C, 3): PyTorch's (C, 1, 3) weights stacked; Y / dY (n, B*T/s, C); X is read once for all n.
+ *   Y_i[b,o,c] = sum_j W_i[c,j] m[b,s o+j-1] X[b,s o+j-1,c]        (taps stay inside sequence b; Y is not masked; the mask of Y is m[b, s o])
+ *   dX[b,t,c]  = m[b,t] sum_i sum_j dY_i[b,o,c] W_i[c,j]           over the (o, j) with s o + j - 1 = t, i then j ascending
+ *   dW_i[c,j]  = sum_{b,o} dY_i[b,o,c] m[b,s o+j-1] X[b,s o+j-1,c] */
+int dcf_op_dwconv3(const float* X, const uint8_t* mask, const float* W, float* Y, int32_t B, int32_t T, int32_t C, int32_t n,
+                   int32_t stride, void* stream);
+int dcf_op_dwconv3_bwd(const float* X, const uint8_t* mask, const float* W, const float* dY, float* dX, float* dW, int32_t B, int32_t T,
+                       int32_t C, int32_t n, int32_t stride, int32_t accumulate, void* stream);
+/* masked_max_pool1d (blocks.py:31-47) with kernel 3, stride 2, padding 1; T even; Y / dY (B*T/2, C), mask_out (B*T/2 bytes, may be NULL).
+ *   f[b,t,c]  = m[b,t] ? X[b,t,c] : min_t' X[b,t',c]              (the minimum over all T rows of the channel; detached, blocks.py:38)
+ *   mo[b,o]   = m[b,2o-1] | m[b,2o] | m[b,2o+1]                   (positions inside the sequence)
+ *   Y[b,o,c]  = mo[b,o] max_{t in {2o-1, 2o, 2o+1}, 0 <= t < T} f[b,t,c]
+ *   dX[b,t,c] = m[b,t] sum of dY[b,o,c] mo[b,o] over the at most two windows o whose maximum sits at t
+ * The backward recomputes the selection from (X, mask): among equal values the lowest position holds the maximum (torch's CPU pooling
+ * takes the first `val > max`), and the choice is made on the filled values f -- a padded slot that wins swallows the gradient. */
+int dcf_op_masked_maxpool(const float* X, const uint8_t* mask, float* Y, uint8_t* mask_out, int32_t B, int32_t T, int32_t C, void* stream);
+int dcf_op_masked_maxpool_bwd(const float* X, const uint8_t* mask, const float* dY, float* dX, int32_t B, int32_t T, int32_t C,
+                              void* stream);
+/* exact (erf) GELU of FFN.actv (blocks.py:531, :536) on n elements: Y = X Phi(X), dX = dY (Phi(X) + X phi(X)), Phi / phi the standard
+ * normal distribution function / density; Phi from erfc of |x| / sqrt 2 (the lower tail keeps its relative accuracy), phi from exp with
+ * the rounding residual of x^2 carried. */
+int dcf_op_gelu(const float* X, float* Y, int64_t n, void* stream);
+int dcf_op_gelu_bwd(const float* X, const float* dY, float* dX, int64_t n, void* stream);
+/* LayerScale residual (blocks.py:670-682 inside :586 and :589-590): Y = R m_R + ls (H m_H), ls (C) broadcast over the rows, either
+ * mask NULL (`skip * mask + ls * h` of :586 is m_H NULL, `x + ls * (h * mask)` of :589-590 is m_R NULL).  H NULL: Y = R m_R.
+ *   dR = dY m_R,   dH = ls dY m_H,   dls[c] = sum_rows dY H m_H */
+int dcf_op_layerscale_residual(const float* R, const uint8_t* mR, const float* H, const uint8_t* mH, const float* ls, float* Y, int32_t rows,
+                               int32_t C, void* stream);
+int dcf_op_layerscale_residual_bwd(const float* dY, const float* H, const uint8_t* mR, const uint8_t* mH, const float* ls, float* dR, float* dH,
+                                   float* dls, int32_t rows, int32_t C, int32_t accumulate, void* stream);
 /* sidekick scoring (model.py:500-505): shallow (D, T) channel-major, text_cls (nq, D) -> correl (nq, T) */
 int dcf_op_sidekick(const float* shallow, const float* text_cls, float* correl, int32_t D, int32_t T, int32_t nq,
                     int32_t norm, void* stream);
