@@ -1,22 +1,27 @@
-"""Differentiable operators of the video encoder on the MI355X, and blocks composed of them, up to a whole TransformerEncoder block.
+"""Differentiable operators of the video encoder and of the fusion decoder on the MI355X, and blocks composed of them, up to a whole
+TransformerEncoder block and a whole XAttNFusion stack.
 
-``masked_conv1d``, ``channel_layer_norm``, ``window_attention``, ``depthwise_conv1d``, ``masked_max_pool1d``, ``gelu`` and
-``layer_scale_residual`` are ``torch.autograd.Function``s over the library's single-operator entry points.  The forwards of the first
-three are the kernels the network's forward runs (dcf_op_conv3_split / dcf_op_linear_split / dcf_op_layernorm / dcf_op_local_attn), their
-backwards are dcf_op_conv_bwd_data / dcf_op_conv_bwd_weight / dcf_op_layernorm_bwd (csrc/conv_grad.hip) and dcf_op_local_attn_bwd
-(csrc/attn_grad.hip); the other four are the forward / backward pairs of csrc/enc_grad.hip (dcf_op_dwconv3, dcf_op_masked_maxpool,
-dcf_op_gelu, dcf_op_layerscale_residual and their ``_bwd``).  Everything runs on the current stream and without a host wait.  Tensors
-are token-major ``(B, T, C)`` fp32 on the GPU; there is no CPU path.
+``masked_conv1d``, ``channel_layer_norm``, ``window_attention``, ``cross_attention``, ``depthwise_conv1d``, ``masked_max_pool1d``,
+``gelu``, ``layer_scale_residual`` and ``adaln_modulate`` are ``torch.autograd.Function``s over the library's single-operator entry
+points.  The forwards of the first four are the kernels the network's forward runs (dcf_op_conv3_split / dcf_op_linear_split /
+dcf_op_layernorm / dcf_op_local_attn / dcf_op_xattn), their backwards are dcf_op_conv_bwd_data / dcf_op_conv_bwd_weight /
+dcf_op_layernorm_bwd (csrc/conv_grad.hip), dcf_op_local_attn_bwd (csrc/attn_grad.hip) and dcf_op_xattn_bwd (csrc/xattn_grad.hip); the
+other five are the forward / backward pairs of csrc/enc_grad.hip (dcf_op_dwconv3, dcf_op_masked_maxpool, dcf_op_gelu,
+dcf_op_layerscale_residual and their ``_bwd``) and of csrc/xattn_grad.hip (dcf_op_adaln, dcf_op_adaln_bwd).  Everything runs on the
+current stream and without a host wait.  Tensors are token-major ``(B, T, C)`` fp32 on the GPU; there is no CPU path.
 
 ``conv_head`` runs one pyramid level through a ClsHead / RegHead (libs/modeling/head.py:53-64, :95-108), ``masked_mha`` the
 local-window MaskedMHA (blocks.py:348-373, :391-392), ``ffn`` the FFN (blocks.py:535-538), ``conv_attn_layer`` a ConvAttNLayer
 (blocks.py:462-473) and ``transformer_encoder`` a whole TransformerEncoder block of the video encoder (blocks.py:578-591; stride 1 or 2,
-local window), so the stem, every pyramid level and the heads behind them train end to end with ``loss.PointObjective``.  There is no
-dropout and no drop-path in any of these functions: they are the reference's blocks with every dropout probability at 0.  They
-demonstrate the operators, they are not the training forward: ``forward(..., eval=False)`` still returns plain tensors.
+local window); ``xattn_mha`` is MaskedMHA in its global cross-attention branch (blocks.py:327-356, :374-393), ``conv_xattn_layer`` a
+ConvXAttNLayer (blocks.py:513-520), ``transformer_decoder`` a whole TransformerDecoder layer (blocks.py:632-650, 'adaln' or 'affine')
+and ``xattn_fusion`` the XAttNFusion stack (fusion.py:56-66).  So the stem, every pyramid level, the text-conditioned fusion and the
+heads behind them train end to end with ``loss.PointObjective``.  There is no dropout and no drop-path in any of these functions:
+they are the reference's blocks with every dropout probability at 0.  They demonstrate the operators, they are not the training
+forward: ``forward(..., eval=False)`` still returns plain tensors.
 
-Without a backward yet: the cross attention and the AdaLN of the fusion blocks, the k = 5 / stride-2 embedding convolutions, global
-attention (the text encoder; stride 0 / window 0 blocks are refused here), the refinement TCN and the gate.
+Without a backward yet: the k = 5 / stride-2 embedding convolutions, global self-attention (the text encoder; stride 0 / window 0
+blocks are refused here), the refinement TCN and the gate.
 """
 import torch
 
@@ -416,3 +421,147 @@ def transformer_encoder(x, mask, block):
     x = layer_scale_residual(skip, h, block.drop_path_attn.scale, r_mask=mask)
     h = ffn(channel_layer_norm(x, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn)
     return layer_scale_residual(x, h, block.drop_path_ffn.scale, h_mask=mask), mask
+
+
+class _CrossAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, kv_mask, n_heads):
+        qd, kd, vd = (_rows(z, 'cross_attention') for z in (q, k, v))
+        B, T, C = qd.shape
+        Lk = kd.size(1)
+        if kd.shape != (B, Lk, C) or vd.shape != kd.shape:
+            raise ValueError(f'cross_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree ((B, T, C) and (B, Lk, C))')
+        if not 1 <= Lk <= 64:
+            raise ValueError(f'cross_attention: Lk = {Lk} keys (1 to 64 have a backward)')
+        if C % n_heads or C // n_heads not in (16, 32, 64, 128):
+            raise ValueError(f'cross_attention: C = {C} on {n_heads} heads: the head dimension must be 16, 32, 64 or 128')
+        m = _byte_mask(kv_mask, B, Lk, 'cross_attention')
+        if m is None:
+            m = torch.ones(B, Lk, dtype=torch.bool, device=qd.device)      # the forward core reads its mask unconditionally
+        o = torch.empty_like(qd)
+        _lib.check(_lib.lib().dcf_op_xattn(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, Lk, C, int(n_heads),
+                                           _lib.current_stream()), 'dcf_op_xattn')
+        ctx.save_for_backward(qd, kd, vd, m)
+        ctx.n_heads = int(n_heads)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, m = ctx.saved_tensors
+        B, T, C = q.shape
+        go = go.float().contiguous()
+        gq, gk, gv = (torch.empty_like(z) if need else None for z, need in zip((q, k, v), ctx.needs_input_grad[:3]))
+        if gq is not None or gk is not None or gv is not None:
+            _lib.check(_lib.lib().dcf_op_xattn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
+                                                   _lib.ptr(gv), B, T, k.size(1), C, ctx.n_heads, _lib.current_stream()), 'dcf_op_xattn_bwd')
+        return gq, gk, gv, None, None
+
+
+class _AdaLnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, h, norm):
+        B, T, C = x.shape
+        xd, hd = _rows(x, 'adaln_modulate'), _rows(h, 'adaln_modulate')
+        if hd.shape != (B, T, 2 * C):
+            raise ValueError(f'adaln_modulate: x {tuple(x.shape)} needs h (B, T, 2 C), got {tuple(h.shape)}')
+        m = _byte_mask(mask, B, T, 'adaln_modulate')
+        y = torch.empty_like(xd)
+        _lib.check(_lib.lib().dcf_op_adaln(_lib.ptr(xd), _lib.ptr(m), _lib.ptr(hd), _lib.ptr(y), B * T, C, int(bool(norm)), _lib.current_stream()),
+                   'dcf_op_adaln')
+        ctx.save_for_backward(xd, m, hd)
+        ctx.norm = int(bool(norm))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, m, h = ctx.saved_tensors
+        B, T, C = x.shape
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gh = torch.empty_like(h) if ctx.needs_input_grad[2] else None
+        gy = gy.float().contiguous()
+        if gx is not None or gh is not None:
+            _lib.check(_lib.lib().dcf_op_adaln_bwd(_lib.ptr(x), _lib.ptr(m), _lib.ptr(h), _lib.ptr(gy), _lib.ptr(gx), _lib.ptr(gh),
+                                                   B * T, C, ctx.norm, _lib.current_stream()), 'dcf_op_adaln_bwd')
+        return gx, None, gh, None
+
+
+def cross_attention(q, k, v, kv_mask, n_heads):
+    """The global cross-attention core of MaskedMHA (blocks.py:374-389) on token-major ``q`` (B, T, C) and ``k`` / ``v`` (B, Lk, C), heads
+    concatenated along C: softmax over the valid keys of the sequence, d^-1/4 on q and on k, masked keys filled with -inf -> (B, T, C).
+    ``kv_mask``: (B, Lk) or (B, 1, Lk), None = all valid; every sequence needs a valid key.  There is no query mask.  Lk from 1 to 64,
+    head dimension 16, 32, 64 or 128."""
+    return _CrossAttentionFn.apply(q, k, v, kv_mask, n_heads)
+
+
+def adaln_modulate(x, mask, h, norm=True):
+    """blocks.py:643-645 on token-major ``x`` (B, T, C) and the cross-attention output ``h`` (B, T, 2 C):
+    ``adaln(x * mask) * h[..., :C] + h[..., C:]`` with adaln the channel LayerNorm without affine parameters (``norm``, xattn_mode
+    'adaln') or the identity (xattn_mode 'affine').  ``mask``: (B, T) or (B, 1, T), None = all valid."""
+    return _AdaLnFn.apply(x, mask, h, norm)
+
+
+def _repeat(x, kv_size, n):
+    """``x.repeat_interleave(kv_size, dim=0)`` with the known result size ``n`` (no host wait for the sum of the counts)"""
+    return x.repeat_interleave(torch.as_tensor(kv_size, device=x.device), dim=0, output_size=n)
+
+
+def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None):
+    """MaskedMHA.forward in its global branch as the fusion calls it (blocks.py:327-356, :374-393; k = v = kv, no dropout) on token-major
+    ``q_in`` (B, T, Cq) and ``kv_in`` (B', Lk, Ckv), with ``mha`` a modeling.MaskedMHA of ``window_size = 0``:
+    proj(cross_attention(query(q_in), key(kv_in), value(kv_in))) -> (B', T, out_dim).  ``kv_size`` (B,): how many of the B' key
+    sequences belong to each query sequence; the PROJECTED query is repeated to match (:352-355)."""
+    if mha.window_size != 0:
+        raise ValueError('xattn_mha: a MaskedMHA with window_size = 0 is required (the local branch is masked_mha)')
+    q = masked_conv1d(q_in, None, mha.query.weight, mha.query.bias)
+    k = masked_conv1d(kv_in, None, mha.key.weight, mha.key.bias)
+    v = masked_conv1d(kv_in, None, mha.value.weight, mha.value.bias)
+    if kv_size is not None and k.size(0) != q.size(0):
+        q = _repeat(q, kv_size, k.size(0))
+    ctx = cross_attention(q, k, v, kv_mask, mha.n_heads)
+    return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
+
+
+def conv_xattn_layer(q, q_mask, kv, kv_mask, layer, kv_size=None):
+    """ConvXAttNLayer.forward (blocks.py:513-520; stride 1, no dropout) on token-major ``q`` (B, T, C) and ``kv`` (B', Lk, Ckv), with
+    ``layer`` a modeling.ConvXAttNLayer: xattn(q_norm(q_conv(q, q_mask)), kv) -> ((B', T, out_dim), the mask repeated like the batch)."""
+    B, T, _ = q.shape
+    (qc,), _ = depthwise_conv1d(q, q_mask, [layer.q_conv.conv.weight], 1)
+    qc = channel_layer_norm(qc, layer.q_norm.weight, layer.q_norm.bias)
+    out = xattn_mha(qc, kv, kv_mask, layer.xattn, kv_size)
+    q_mask = _mask_rows(q_mask, B, T)
+    if kv_size is not None and q_mask is not None and out.size(0) != q_mask.size(0):
+        q_mask = _repeat(q_mask, kv_size, out.size(0))
+    return out, q_mask
+
+
+def transformer_decoder(q, q_mask, kv, kv_mask, block, kv_size=None):
+    """TransformerDecoder.forward (blocks.py:632-650) on token-major ``q`` (B, T, E) and ``kv`` (B', Lk, TE), with ``block`` a
+    modeling.TransformerDecoder -> (y (B', T, E), the query mask (B', T)).  To the letter: the input is multiplied by the mask (:635);
+    the cross attention sees ln_xattn_q of that and ln_xattn_kv(kv); with ``kv_size`` the query residual is repeated to the B' text
+    queries (:641-642); the residual is masked again, normalised without affine parameters ('adaln') or left as it is ('affine'), and
+    modulated by the two halves of the cross-attention output (:643-645); the FFN branch is masked, the output is not, so padded rows
+    hold the shift.  No dropout and no drop-path."""
+    B, T, _ = q.shape
+    q_mask = torch.ones(B, T, dtype=torch.bool, device=q.device) if q_mask is None else _mask_rows(q_mask, B, T)
+    q = _LayerScaleResidualFn.apply(q, None, None, q_mask, None)
+    h, mask = conv_xattn_layer(channel_layer_norm(q, block.ln_xattn_q.weight, block.ln_xattn_q.bias), q_mask,
+                               channel_layer_norm(kv, block.ln_xattn_kv.weight, block.ln_xattn_kv.bias), kv_mask, block.xattn, kv_size)
+    if kv_size is not None and q.size(0) != h.size(0):
+        q = _repeat(q, kv_size, h.size(0))
+    q = adaln_modulate(q, mask, h, norm=block.xattn_mode == 'adaln')
+    h = ffn(channel_layer_norm(q, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn)
+    return layer_scale_residual(q, h, block.drop_path_ffn.scale, h_mask=mask), mask
+
+
+def xattn_fusion(vid, vid_mask, text, text_mask, fusion, kv_size=None):
+    """XAttNFusion._forward (fusion.py:56-66) on token-major ``vid`` (B, T, E) and ``text`` (B', Lk, TE), with ``fusion`` a
+    modeling.XAttNFusion: its decoder layers, ln_out, and the repeat by ``kv_size`` when no layer expanded the batch
+    -> (fused (B', T, E), mask (B', T))."""
+    B, T, _ = vid.shape
+    vid_mask = torch.ones(B, T, dtype=torch.bool, device=vid.device) if vid_mask is None else _mask_rows(vid_mask, B, T)
+    for layer in fusion.layers:
+        vid, vid_mask = transformer_decoder(vid, vid_mask, text, text_mask, layer, kv_size)
+    vid = channel_layer_norm(vid, fusion.ln_out.weight, fusion.ln_out.bias)
+    if kv_size is not None and vid.size(0) != text.size(0):
+        vid, vid_mask = _repeat(vid, kv_size, text.size(0)), _repeat(vid_mask, kv_size, text.size(0))
+    return vid, vid_mask

@@ -534,6 +534,36 @@ int dcf_op_layerscale_residual(const float* R, const uint8_t* mR, const float* H
                                int32_t C, void* stream);
 int dcf_op_layerscale_residual_bwd(const float* dY, const float* H, const uint8_t* mR, const uint8_t* mH, const float* ls, float* dR, float* dH,
                                    float* dls, int32_t rows, int32_t C, int32_t accumulate, void* stream);
+/* Backward of the cross-attention core dcf_op_xattn and the AdaLN modulation of a fusion decoder layer with its backward (additions to
+ * ABI version 12; csrc/xattn_grad.hip).  Token-major fp32, 16-byte aligned pointers, everything on `stream` without a host wait, scratch
+ * allocated and freed on it, no floating-point atomics; an output pointer that is NULL skips the work that only feeds it and leaves the
+ * bits of the others unchanged; unsupported shapes fail with a message, nothing falls back to another arithmetic.
+ *
+ * dcf_op_xattn_bwd differentiates, per sequence b, head h (head dimension d = C / heads), query row t < T and key j < Lk, scale = d^-1/4:
+ *   s[t,j] = (scale q[t]) . (scale k[j])     over the keys with kvmask[b,j] != 0; a masked key contributes exactly 0 (blocks.py:381-384)
+ *   p[t,.] = softmax_j s[t,j],   O[t] = sum_j p[t,j] v[j]
+ * and returns, given dO,
+ *   dP[t,j] = dO[t] . v[j],   delta[t] = sum_j p[t,j] dP[t,j],   dS[t,j] = p[t,j] (dP[t,j] - delta[t])
+ *   dQ[t] = scale^2 sum_j dS[t,j] k[j],   dK[j] = scale^2 sum_t dS[t,j] q[t],   dV[j] = sum_t p[t,j] dO[t]
+ * Q / dO / dQ: (B*T, C); K / V / dK / dV: (B*Lk, C); kvmask (B*Lk bytes), NULL = every key valid.  There is no query mask (the
+ * reference's global branch has none): dO at every row is used.  dK = dV = 0 exactly at a masked key.  A sequence without a valid key is
+ * NaN in the forward and undefined here.  delta is formed from p and dP, so a one-key sequence gives dQ = dK = 0 exactly.
+ * Shapes: 1 <= Lk <= 64, head dimension 16, 32, 64 or 128, C % 4 == 0, C <= 1024, any T >= 1, B <= 65535; Lk = 0, Lk > 64 and any other
+ * head dimension fail with a message (there is no slower variant).  fp32 on the vector ALU, the exponential with its rounding residual
+ * carried.  dK / dV are summed per workgroup over slices of 512 query rows of a sequence (a constant: the order depends on the shapes
+ * alone, never on the device), the slices then in a fixed blocked order: results are bit-identical from run to run and scaling dO by
+ * a power of two scales them by exactly that.
+ *
+ * dcf_op_adaln, per row: Y = N(X m) * H[:, :C] + H[:, C:]  (blocks.py:643-645), X / Y (rows, C), H (rows, 2C) the cross-attention output
+ * (scale | shift), m (rows bytes) the row mask, NULL = every row valid; N = the affine-free channel LayerNorm (blocks.py:125-131, two-pass,
+ * eps 1e-5) for norm != 0, the identity for norm = 0 (xattn_mode 'affine', blocks.py:622-626).  A masked row has N(0) = 0: Y = shift.
+ * dcf_op_adaln_bwd: dH[:, :C] = dY * N(X m),  dH[:, C:] = dY,  dX = m LN'(dY * H[:, :C])  (norm = 0: m dY * H[:, :C]); dX = 0 exactly at
+ * a masked row.  dX or dH may be NULL.  C % 4 == 0, C <= 1024. */
+int dcf_op_xattn_bwd(const float* Q, const float* K, const float* V, const uint8_t* kvmask, const float* dO, float* dQ, float* dK,
+                     float* dV, int32_t B, int32_t T, int32_t Lk, int32_t C, int32_t heads, void* stream);
+int dcf_op_adaln(const float* X, const uint8_t* mask, const float* H, float* Y, int32_t rows, int32_t C, int32_t norm, void* stream);
+int dcf_op_adaln_bwd(const float* X, const uint8_t* mask, const float* H, const float* dY, float* dX, float* dH, int32_t rows, int32_t C,
+                     int32_t norm, void* stream);
 /* sidekick scoring (model.py:500-505): shallow (D, T) channel-major, text_cls (nq, D) -> correl (nq, T) */
 int dcf_op_sidekick(const float* shallow, const float* text_cls, float* correl, int32_t D, int32_t T, int32_t nq,
                     int32_t norm, void* stream);
