@@ -107,6 +107,10 @@ SIGNATURES = {
     'dcf_op_xattn_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]),
     'dcf_op_adaln': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, i32, i32, i32, vp]),
     'dcf_op_adaln_bwd': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, vp]),
+    'dcf_op_refine_in': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, i32, i32, i32, vp]),
+    'dcf_op_refine_in_bwd': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, vp]),
+    'dcf_op_tcn_layer': (i32, [c_f32p] + [c_u8p] + [c_f32p] * 7 + [i32, i32, i32, i64, f32, i32, i32, vp]),
+    'dcf_op_tcn_layer_bwd': (i32, [c_f32p] + [c_u8p] + [c_f32p] * 14 + [i32, i32, i32, i64, f32, i32, i32, i32, vp]),
     'dcf_op_sidekick': (i32, [c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, vp]),
     'dcf_op_gate': (i32, [c_f32p, c_u8p, c_f32p, c_u8p, i32, i32, i32, f64, i32, vp]),
     'dcf_op_encoder': (i32, [vp, ctypes.c_char_p, c_f32p, c_u8p, i32, i32, i32, c_f32p, c_u8p, vp]),

@@ -1,5 +1,5 @@
-"""Differentiable operators of the video encoder and of the fusion decoder on the MI355X, and blocks composed of them, up to a whole
-TransformerEncoder block and a whole XAttNFusion stack.
+"""Differentiable operators of the video encoder, of the fusion decoder and of the refinement stage on the MI355X, and blocks composed
+of them, up to a whole TransformerEncoder block, a whole XAttNFusion stack and ``fuse_and_predict`` of PtTransformerEarlyFusionIterative.
 
 ``masked_conv1d``, ``channel_layer_norm``, ``window_attention``, ``cross_attention``, ``depthwise_conv1d``, ``masked_max_pool1d``,
 ``gelu``, ``layer_scale_residual`` and ``adaln_modulate`` are ``torch.autograd.Function``s over the library's single-operator entry
@@ -20,8 +20,15 @@ heads behind them train end to end with ``loss.PointObjective``.  There is no dr
 they are the reference's blocks with every dropout probability at 0.  They demonstrate the operators, they are not the training
 forward: ``forward(..., eval=False)`` still returns plain tensors.
 
+``refine_in`` and ``tcn_layer`` are the forward / backward pairs of csrc/refine_grad.hip (dcf_op_refine_in, dcf_op_tcn_layer and their
+``_bwd``): the stacking of the nearest-upsampled first-pass logits fused with refine.conv_1x1 (model.py:449-455) and one
+DilatedResidualLayer (tcn.py:21-38).  ``tcn`` is the whole refinement TCN (tcn.py:66-84) and ``fuse_and_predict`` is model.py:442-471:
+the three outputs ``loss.PointObjective`` consumes, with a graph.  The refinement is the one place where the reference hard-wires a
+dropout in training (tcn.py:5,13: 0.5), so these three take ``dropout = (seed, p, b0)``: the keep bits are those of the training
+forward (``model.enable_dropout``; csrc/dropout.h), recomputed in the backward.
+
 Without a backward yet: the k = 5 / stride-2 embedding convolutions, global self-attention (the text encoder; stride 0 / window 0
-blocks are refused here), the refinement TCN and the gate.
+blocks are refused here) and the gate.
 """
 import torch
 
@@ -565,3 +572,173 @@ def xattn_fusion(vid, vid_mask, text, text_mask, fusion, kv_size=None):
     if kv_size is not None and vid.size(0) != text.size(0):
         vid, vid_mask = _repeat(vid, kv_size, text.size(0)), _repeat(vid_mask, kv_size, text.size(0))
     return vid, vid_mask
+
+
+_TCN_C = 32        # channels of the refinement TCN (model.py:424)
+
+
+def _drop_args(dropout, name):
+    """(seed, p, b0) of ``dropout`` = None or (seed, p, b0)"""
+    if dropout is None:
+        return 0, 0.0, 0
+    seed, p, b0 = dropout
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'{name}: dropout p = {p} must lie in [0, 1)')
+    if int(b0) < 0:
+        raise ValueError(f'{name}: dropout b0 = {b0} must not be negative')
+    return int(seed), p, int(b0)
+
+
+def _vec(t, n, name, what):
+    if t.numel() != n:
+        raise ValueError(f'{name}: {what} {tuple(t.shape)} must hold {n} elements')
+    return t.detach().float().reshape(n).contiguous()
+
+
+class _RefineInFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits1, mask0, weight, bias):
+        if not (torch.is_tensor(logits1) and logits1.is_cuda and logits1.dim() == 2):
+            raise RuntimeError('refine_in: (B, S) logits on the GPU are required (there is no CPU path)')
+        B, S = logits1.shape
+        if weight.dim() not in (2, 3) or weight.size(0) != _TCN_C or weight[0].numel() != weight.size(1):
+            raise ValueError(f'refine_in: weight {tuple(weight.shape)} must be ({_TCN_C}, L) or ({_TCN_C}, L, 1)')
+        L = weight.size(1)
+        if not 1 <= L <= 16:
+            raise ValueError(f'refine_in: L = {L} pyramid levels (1 to 16)')
+        T0, rem = divmod(S << (L - 1), (1 << L) - 1)                   # S = sum_l T0 >> l = T0 (2^L - 1) / 2^(L-1)
+        if rem or T0 == 0 or T0 % (1 << (L - 1)):
+            raise ValueError(f'refine_in: S = {S} is not the length of a pyramid of {L} levels (T0 must be a multiple of {1 << (L - 1)})')
+        m = _byte_mask(mask0, B, T0, 'refine_in')
+        lg = logits1.detach().float().contiguous()
+        w, b = weight.detach().float().reshape(_TCN_C, L).contiguous(), _vec(bias, _TCN_C, 'refine_in', 'bias')
+        h = torch.empty(B, T0, _TCN_C, dtype=torch.float32, device=lg.device)
+        _lib.check(_lib.lib().dcf_op_refine_in(_lib.ptr(lg), _lib.ptr(m), _lib.ptr(w), _lib.ptr(b), _lib.ptr(h), B, T0, L, _lib.current_stream()),
+                   'dcf_op_refine_in')
+        ctx.save_for_backward(lg, m, w)
+        ctx.shapes = (weight.shape, bias.shape)
+        return h
+
+    @staticmethod
+    def backward(ctx, gh):
+        lg, m, w = ctx.saved_tensors
+        (B, S), L = lg.shape, w.size(1)
+        gh = gh.float().contiguous()
+        T0 = gh.size(1)
+        gl = torch.empty_like(lg) if ctx.needs_input_grad[0] else None
+        gw = torch.empty_like(w) if ctx.needs_input_grad[2] else None
+        gb = torch.empty(_TCN_C, dtype=torch.float32, device=lg.device) if ctx.needs_input_grad[3] else None
+        if gl is not None or gw is not None or gb is not None:
+            _lib.check(_lib.lib().dcf_op_refine_in_bwd(_lib.ptr(lg), _lib.ptr(m), _lib.ptr(w), _lib.ptr(gh), _lib.ptr(gl), _lib.ptr(gw), _lib.ptr(gb),
+                                                       B, T0, L, 0, _lib.current_stream()), 'dcf_op_refine_in_bwd')
+        return (gl, None, gw.reshape(ctx.shapes[0]) if gw is not None else None, gb.reshape(ctx.shapes[1]) if gb is not None else None)
+
+
+class _TcnLayerFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, wd, bd, wp, bp, lnw, lnb, dilation, site_layer, seed, p, b0):
+        xd = _rows(x, 'tcn_layer')
+        B, T0, C = xd.shape
+        if C != _TCN_C or tuple(wd.shape) != (C, C, 3) or wp.numel() != C * C or wp.size(0) != C:
+            raise ValueError(f'tcn_layer: x {tuple(x.shape)}, conv_dilated {tuple(wd.shape)}, conv_1x1 {tuple(wp.shape)}: the refinement TCN '
+                             f'has {_TCN_C} channels, a ({_TCN_C}, {_TCN_C}, 3) and a ({_TCN_C}, {_TCN_C}[, 1]) weight')
+        if dilation < 1:
+            raise ValueError(f'tcn_layer: dilation = {dilation} must be at least 1')
+        m = _byte_mask(mask, B, T0, 'tcn_layer')
+        params = (wd.detach().float().contiguous(), _vec(bd, C, 'tcn_layer', 'conv_dilated.bias'), wp.detach().float().reshape(C, C).contiguous(),
+                  _vec(bp, C, 'tcn_layer', 'conv_1x1.bias'), _vec(lnw, C, 'tcn_layer', 'norm.weight'), _vec(lnb, C, 'tcn_layer', 'norm.bias'))
+        y = torch.empty_like(xd)
+        _lib.check(_lib.lib().dcf_op_tcn_layer(_lib.ptr(xd), _lib.ptr(m), *(_lib.ptr(t) for t in params), _lib.ptr(y), B, T0, dilation, seed, p,
+                                               site_layer, b0, _lib.current_stream()), 'dcf_op_tcn_layer')
+        ctx.save_for_backward(xd, m, *params)
+        ctx.geom = (dilation, site_layer, seed, p, b0)
+        ctx.shapes = tuple(t.shape for t in (wd, bd, wp, bp, lnw, lnb))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, m, *params = ctx.saved_tensors
+        B, T0, C = x.shape
+        dilation, site_layer, seed, p, b0 = ctx.geom
+        gy = gy.float().contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gp = [torch.empty_like(t) if need else None for t, need in zip(params, ctx.needs_input_grad[2:8])]
+        if gx is not None or any(g is not None for g in gp):
+            _lib.check(_lib.lib().dcf_op_tcn_layer_bwd(_lib.ptr(x), _lib.ptr(m), *(_lib.ptr(t) for t in params), _lib.ptr(gy), _lib.ptr(gx),
+                                                       *(_lib.ptr(g) for g in gp), B, T0, dilation, seed, p, site_layer, b0, 0,
+                                                       _lib.current_stream()), 'dcf_op_tcn_layer_bwd')
+        gp = [g.reshape(shape) if g is not None else None for g, shape in zip(gp, ctx.shapes)]
+        return (gx, None, *gp, None, None, None, None, None)
+
+
+def refine_in(logits1, mask0, tcn_module):
+    """model.py:449-455 fused with TCN.conv_1x1 (tcn.py:69-70), with ``tcn_module`` a modeling.TCN of L input channels: ``logits1`` (B, S),
+    the first-pass logits of the L pyramid levels side by side (level l: T0 >> l entries), each level nearest-upsampled to T0, levels
+    l > 0 multiplied by ``mask0`` (B, T0) or (B, 1, T0) (level 0 is not masked, to the letter), then mapped to 32 channels -> (B, T0, 32)."""
+    return _RefineInFn.apply(logits1, mask0, tcn_module.conv_1x1.weight, tcn_module.conv_1x1.bias)
+
+
+def tcn_layer(x, mask, layer, dilation, dropout=None, site_layer=None):
+    """DilatedResidualLayer.forward (tcn.py:21-38) on token-major ``x`` (B, T0, 32), with ``layer`` a modeling.DilatedResidualLayer:
+    ``LayerNorm((x + drop(conv_1x1(relu(conv_dilated(x))))) * mask)``; the dilated convolution does not mask its input.  ``dropout``:
+    None or (seed, p, b0) -- the keep bits of the training forward for sequence b0 + b of its batch at the site of TCN layer
+    ``site_layer`` (default: log2 of a power-of-two ``dilation``, as modeling.TCN numbers its layers).  The backward saves ``x`` alone."""
+    dilation = int(dilation)
+    seed, p, b0 = _drop_args(dropout, 'tcn_layer')
+    if site_layer is None:
+        if p > 0.0 and (dilation < 1 or dilation & (dilation - 1)):
+            raise ValueError(f'tcn_layer: dropout on a layer of dilation {dilation} needs site_layer (the layer\'s index in its TCN)')
+        site_layer = max(dilation, 1).bit_length() - 1 if not dilation & (dilation - 1) else 0
+    return _TcnLayerFn.apply(x, mask, layer.conv_dilated.weight, layer.conv_dilated.bias, layer.conv_1x1.weight, layer.conv_1x1.bias,
+                             layer.norm.weight, layer.norm.bias, dilation, int(site_layer), seed, p, b0)
+
+
+def tcn(logits1, mask0, tcn_module, dropout=None):
+    """TCN.forward (tcn.py:66-84) behind the stacking of model.py:449-455: ``refine_in``, the layers of dilation 2^i, then
+    ``conv_out(x) * mask0`` -> (B, T0, 32).  ``dropout``: None or (seed, p, b0) for every layer's Dropout (tcn.py:27)."""
+    x = refine_in(logits1, mask0, tcn_module)
+    B, T0, _ = x.shape
+    for i, layer in enumerate(tcn_module.layers):
+        x = tcn_layer(x, mask0, layer, layer.conv_dilated.dilation[0], dropout, site_layer=i)
+    x = masked_conv1d(x, None, tcn_module.conv_out.weight, tcn_module.conv_out.bias)
+    return x if mask0 is None else _LayerScaleResidualFn.apply(x, None, None, _mask_rows(mask0, B, T0), None)
+
+
+def fuse_and_predict(fpn, fpn_masks, model, dropout=None, text=None, text_mask=None, kv_size=None):
+    """PtTransformerEarlyFusionIterative.fuse_and_predict (model.py:442-471) on token-major pyramid levels ``fpn[l]`` (B, T0 >> l, E) with
+    masks ``fpn_masks[l]`` (B, T0 >> l) or (B, 1, T0 >> l), ``model`` a modeling.PtTransformerEarlyFusionIterative -> (logits1, logits2,
+    offsets, masks), tuples over the levels of (B', T_l), (B', T_l), (B', T_l, 2) and (B', T_l) bool: what ``loss.PointObjective`` takes.
+    With ``model.second_fusion`` every level first goes through ``xattn_fusion`` against ``text`` (B', Lk, TE) / ``text_mask`` /
+    ``kv_size``.  To the letter: the refined map is pooled down the pyramid with ``fpn_masks[i - 1]``, the pooled mask is discarded, and
+    the heads see ``fpn_masks[i]``.  ``dropout``: None or (seed, p, b0) for the refinement TCN, the seed as ``model.enable_dropout``
+    hands it out (``model.last_dropout_seed``)."""
+    n_levels = len(model.refine.layers)
+    if len(fpn) != n_levels or len(fpn_masks) != n_levels:
+        raise ValueError(f'fuse_and_predict: {len(fpn)} levels and {len(fpn_masks)} masks for a model of {n_levels} pyramid levels')
+    E = model.cls_head.convs[0].conv.weight.size(1) if len(model.cls_head.convs) else model.cls_head.cls_head.conv.weight.size(1)
+    T0 = fpn[0].size(1) if torch.is_tensor(fpn[0]) and fpn[0].dim() == 3 else 0
+    for l, x in enumerate(fpn):
+        x = _rows(x, 'fuse_and_predict')
+        if x.size(2) != E:
+            raise ValueError(f'fuse_and_predict: level {l} has {x.size(2)} channels, the heads take {E}')
+        if x.size(1) != T0 >> l or (l + 1 < n_levels and x.size(1) % 2):
+            raise ValueError(f'fuse_and_predict: level {l} has length {x.size(1)}: the levels must be T0 >> l = {T0 >> l}, even above the last')
+    masks = [_mask_rows(m, x.size(0), x.size(1)) for m, x in zip(fpn_masks, fpn)]
+    if any(m is None for m in masks):
+        raise ValueError('fuse_and_predict: every level needs its mask')
+    if model.second_fusion:
+        if text is None:
+            raise ValueError('fuse_and_predict: a model with second_fusion needs the text')
+        fused = [xattn_fusion(x, m, text, text_mask, model.fusion, kv_size) for x, m in zip(fpn, masks)]
+        fpn, masks = [f[0] for f in fused], [f[1] for f in fused]
+    logits1 = [conv_head(x, m, model.cls_head) for x, m in zip(fpn, masks)]
+    refined = tcn(torch.cat(logits1, dim=1), masks[0], model.refine, dropout)
+    new_fpn = []
+    for i, x in enumerate(fpn):
+        if i:
+            refined = masked_max_pool1d(refined, masks[i - 1])[0]
+        new_fpn.append(torch.cat([x, refined], dim=2))
+    logits2 = [conv_head(x, m, model.cls_head2) for x, m in zip(new_fpn, masks)]
+    offsets = [conv_head(x, m, model.reg_head, level=l) for l, (x, m) in enumerate(zip(new_fpn, masks))]
+    return tuple(logits1), tuple(logits2), tuple(offsets), tuple(masks)

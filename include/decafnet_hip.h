@@ -564,6 +564,44 @@ int dcf_op_xattn_bwd(const float* Q, const float* K, const float* V, const uint8
 int dcf_op_adaln(const float* X, const uint8_t* mask, const float* H, float* Y, int32_t rows, int32_t C, int32_t norm, void* stream);
 int dcf_op_adaln_bwd(const float* X, const uint8_t* mask, const float* H, const float* dY, float* dX, float* dH, int32_t rows, int32_t C,
                      int32_t norm, void* stream);
+/* Forward / backward pairs of the refinement stage of PtTransformerEarlyFusionIterative (model.py:449-455, tcn.py:21-38; additions to
+ * ABI version 12; csrc/refine_grad.hip).  Conventions of all four: token-major fp32 rows (B*T0, 32), 16-byte aligned pointers; a mask is
+ * B*T0 bytes, NULL = every row valid; everything runs on `stream` without a host wait, scratch is allocated and freed on it; no
+ * floating-point atomics -- parameter gradients are summed over fixed slices of 128 rows (RG_SLICE_ROWS) and then in a fixed blocked
+ * tree, so results are bit-identical from run to run and scaling the upstream gradient by a power of two scales them by exactly that;
+ * an output pointer that is NULL skips the work that only feeds it and leaves the bits of the others unchanged; accumulate != 0 adds
+ * into the parameter gradients (`.grad +=`); unsupported shapes fail with a message.  Weights are in PyTorch's layouts.  fp32 on the
+ * vector ALU, every contraction an fma chain in ascending index; there is no other arithmetic to fall back to.
+ *
+ * dcf_op_refine_in: the stacking of the nearest-upsampled first-pass logits (model.py:449-455) fused with refine.conv_1x1.
+ * logits1 (B, S) in the pyramid order of the forward's outputs: level l at offset sum_{j<l} T_j, T_l = T0 >> l, S = sum_l T_l;
+ * W_in (32, L), b_in (32); 1 <= L <= 16, T0 % 2^(L-1) == 0.
+ *   u[b,t,0] = logits1[b,0,t]   (level 0 is not masked, to the letter),   u[b,t,l] = m0[b,t] logits1[b,l,t >> l]   for l > 0
+ *   H[b,t,c] = b_in[c] + sum_l W_in[c,l] u[b,t,l]
+ *   dlogits1[b,l,s] = sum over the 2^l rows t >> l == s, t ascending, of (l == 0 ? 1 : m0[b,t]) sum_c W_in[c,l] dH[b,t,c]
+ *   dW_in[c,l] = sum_{b,t} dH[b,t,c] u[b,t,l],   db_in[c] = sum_{b,t} dH[b,t,c]
+ *
+ * dcf_op_tcn_layer: one DilatedResidualLayer (tcn.py:21-38) on 32 channels: Wd (32, 32, 3), Wp (32, 32), dilation >= 1.
+ *   h = relu(bd + sum_{j,ci} Wd[.,ci,j] X[b, t + (j-1) dilation, ci])   (taps stay inside sequence b; the input is NOT masked: the
+ *                                                                        reference's convolution is a plain nn.Conv1d)
+ *   o = drop(bp + Wp h),   z = (X + o) m,   Y = LN(z) ln_w + ln_b       (two-pass, eps 1e-5)
+ * drop: element (b, c, t) is kept iff drop_keep(seed, drop_site(DROP_G_REFINE, layer, DROP_TCN), ((b0 + b) * 32 + c) * T0 + t, p)
+ * (csrc/dropout.h: the bits of the training forward, dcf_model_set_dropout) and then multiplied by 1 / (1 - p); p = 0 is the identity
+ * and runs the kernel compiled without dropout.
+ * dcf_op_tcn_layer_bwd saves nothing but X: it recomputes h, o, the keep bits and the LayerNorm statistics, and returns dX, dWd, dbd,
+ * dWp, dbp, dln_w, dln_b (any may be NULL).  ReLU passes nothing at h == 0.  At a padded row dz = 0, but dln_b still takes dY there (the
+ * LayerNorm runs on every row); dX is NOT zero at padded rows: valid neighbours read them through the unmasked side taps. */
+int dcf_op_refine_in(const float* logits1, const uint8_t* mask0, const float* W_in, const float* b_in, float* H, int32_t B, int32_t T0,
+                     int32_t L, void* stream);
+int dcf_op_refine_in_bwd(const float* logits1, const uint8_t* mask0, const float* W_in, const float* dH, float* dlogits1, float* dW_in,
+                         float* db_in, int32_t B, int32_t T0, int32_t L, int32_t accumulate, void* stream);
+int dcf_op_tcn_layer(const float* X, const uint8_t* mask, const float* Wd, const float* bd, const float* Wp, const float* bp,
+                     const float* ln_w, const float* ln_b, float* Y, int32_t B, int32_t T0, int32_t dilation, int64_t seed, float p,
+                     int32_t layer, int32_t b0, void* stream);
+int dcf_op_tcn_layer_bwd(const float* X, const uint8_t* mask, const float* Wd, const float* bd, const float* Wp, const float* bp,
+                         const float* ln_w, const float* ln_b, const float* dY, float* dX, float* dWd, float* dbd, float* dWp, float* dbp,
+                         float* dln_w, float* dln_b, int32_t B, int32_t T0, int32_t dilation, int64_t seed, float p, int32_t layer,
+                         int32_t b0, int32_t accumulate, void* stream);
 /* sidekick scoring (model.py:500-505): shallow (D, T) channel-major, text_cls (nq, D) -> correl (nq, T) */
 int dcf_op_sidekick(const float* shallow, const float* text_cls, float* correl, int32_t D, int32_t T, int32_t nq,
                     int32_t norm, void* stream);
