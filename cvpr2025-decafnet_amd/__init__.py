@@ -8,7 +8,8 @@ Sub-modules: ``modeling`` (libs/modeling drop-in), ``nms`` (libs/nms drop-in), `
 ``data`` (feature files, text-CLS table, annotation file -> per-video dicts), ``dropin`` (runs the reference's own
 ``eval.py`` / ``Evaluator`` on this package without editing it), ``loss`` (libs/modeling/loss.py forward values), ``autograd`` (differentiable MaskedConv1D / channel LayerNorm / window attention /
 cross attention / AdaLN modulation / depthwise convolution / max pooling / GELU / LayerScale residual, and heads, whole TransformerEncoder blocks, whole
-TransformerDecoder layers and the XAttNFusion stack composed of them: ``cross_attention``, ``adaln_modulate``, ``xattn_mha``, ``conv_xattn_layer``, ``transformer_decoder``, ``xattn_fusion``; the refinement stage ``refine_in``, ``tcn_layer``, ``tcn`` and ``fuse_and_predict``), ``dist`` (T-sharding over ranks), ``build`` (hipcc driver),
+TransformerDecoder layers and the XAttNFusion stack composed of them: ``cross_attention``, ``adaln_modulate``, ``xattn_mha``, ``conv_xattn_layer``, ``transformer_decoder``, ``xattn_fusion``; the refinement stage ``refine_in``, ``tcn_layer``, ``tcn`` and ``fuse_and_predict``; the two backbones
+``video_transformer`` (with the k = 5 / stride-2 ``strided_masked_conv1d``) and ``text_transformer``), ``dist`` (T-sharding over ranks), ``build`` (hipcc driver),
 ``_lib`` (ctypes binding of the C ABI).
 """
 from . import config, synth  # noqa: F401

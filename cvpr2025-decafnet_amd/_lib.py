@@ -93,6 +93,9 @@ SIGNATURES = {
     'dcf_op_conv_bwd_data': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]),
     'dcf_op_conv_bwd_weight': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, i32, vp]),
     'dcf_op_layernorm_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, vp]),
+    'dcf_op_conv5s2_split': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]),
+    'dcf_op_conv5s2_bwd_data': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, i32, i32, i32, i32, vp]),
+    'dcf_op_conv5s2_bwd_weight': (i32, [c_f32p, c_u8p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]),
     'dcf_op_xattn': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, i32, i32, i32, i32, i32, vp]),
     'dcf_op_local_attn': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, i32, i32, i32, i32, i32, vp]),
     'dcf_op_local_attn_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]),

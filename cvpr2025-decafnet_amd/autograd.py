@@ -12,11 +12,19 @@ current stream and without a host wait.  Tensors are token-major ``(B, T, C)`` f
 
 ``conv_head`` runs one pyramid level through a ClsHead / RegHead (libs/modeling/head.py:53-64, :95-108), ``masked_mha`` the
 local-window MaskedMHA (blocks.py:348-373, :391-392), ``ffn`` the FFN (blocks.py:535-538), ``conv_attn_layer`` a ConvAttNLayer
-(blocks.py:462-473) and ``transformer_encoder`` a whole TransformerEncoder block of the video encoder (blocks.py:578-591; stride 1 or 2,
-local window); ``xattn_mha`` is MaskedMHA in its global cross-attention branch (blocks.py:327-356, :374-393), ``conv_xattn_layer`` a
+(blocks.py:462-473) and ``transformer_encoder`` a whole TransformerEncoder block (blocks.py:578-591): a block of the video encoder
+(stride 1 or 2, local window) or of the text encoder (stride 0, global self-attention through ``xattn_mha`` with q = k = v, at most 64
+positions); ``xattn_mha`` is MaskedMHA in its global cross-attention branch (blocks.py:327-356, :374-393), ``conv_xattn_layer`` a
 ConvXAttNLayer (blocks.py:513-520), ``transformer_decoder`` a whole TransformerDecoder layer (blocks.py:632-650, 'adaln' or 'affine')
 and ``xattn_fusion`` the XAttNFusion stack (fusion.py:56-66).  So the stem, every pyramid level, the text-conditioned fusion and the
-heads behind them train end to end with ``loss.PointObjective``.  There is no dropout and no drop-path in any of these functions:
+heads behind them train end to end with ``loss.PointObjective``.
+
+``masked_conv1d(..., stride=2)`` / ``strided_masked_conv1d`` is the k = 5 / stride-2 embedding convolution of ``vid_net.stride > 1``
+(video_net.py:62-70): the forward's own path (dcf_op_conv5s2_split) and dcf_op_conv5s2_bwd_data / dcf_op_conv5s2_bwd_weight
+(csrc/conv_grad.hip).  ``video_transformer`` is VideoTransformer.forward (video_net.py:123-164: embd_fc, the embedding convolutions,
+the position encoding, the stem and the branch, ``pool_only`` included) and ``text_transformer`` TextTransformer.forward
+(text_net.py:158-188: embd_fc, the position encoding, the background token, the stride-0 blocks), both in their training branch.  With
+them every trainable parameter of the default model lies in a module that has a differentiable function here.  There is no dropout and no drop-path in any of these functions:
 they are the reference's blocks with every dropout probability at 0.  They demonstrate the operators, they are not the training
 forward: ``forward(..., eval=False)`` still returns plain tensors.
 
@@ -27,8 +35,9 @@ the three outputs ``loss.PointObjective`` consumes, with a graph.  The refinemen
 dropout in training (tcn.py:5,13: 0.5), so these three take ``dropout = (seed, p, b0)``: the keep bits are those of the training
 forward (``model.enable_dropout``; csrc/dropout.h), recomputed in the backward.
 
-Without a backward yet: the k = 5 / stride-2 embedding convolutions, global self-attention (the text encoder; stride 0 / window 0
-blocks are refused here) and the gate.
+Without a backward yet: the gate (it has no parameters: its inputs are features the caller supplies, so it does not stand between these
+functions and a training step), ``vid_map`` on the gated input as one function, TextIdentity's attention pool (``text_transformer``
+refuses a TextIdentity) and global self-attention over more than 64 positions.
 """
 import torch
 
@@ -111,6 +120,43 @@ class _MaskedConv1dFn(torch.autograd.Function):
         return gx, None, gw, gb
 
 
+class _MaskedConv5s2Fn(torch.autograd.Function):
+    """the k = 5 / stride 2 / padding 2 MaskedConv1D without bias (video_net.py:62-70)"""
+
+    @staticmethod
+    def forward(ctx, x, mask, weight):
+        B, T, Cin = x.shape
+        N, Cw, k = weight.shape
+        if Cw != Cin or k != 5:
+            raise ValueError(f'masked_conv1d: stride = 2 admits exactly k = 5 (padding 2, groups = 1): weight {tuple(weight.shape)} on {Cin} channels')
+        if T % 2:
+            raise ValueError(f'masked_conv1d: T = {T} must be a multiple of the stride 2')
+        xd, wd = _rows(x, 'masked_conv1d'), weight.detach().float().contiguous()
+        m = _mask_rows(mask, B, T)
+        y = torch.empty(B, T // 2, N, dtype=torch.float32, device=xd.device)
+        _lib.check(_lib.lib().dcf_op_conv5s2_split(_lib.ptr(xd), _lib.ptr(m), _lib.ptr(wd), _lib.ptr(y), B, T, Cin, N, _F16X3, _lib.current_stream()),
+                   'dcf_op_conv5s2_split')
+        ctx.save_for_backward(xd, m, wd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, m, w = ctx.saved_tensors
+        B, T, Cin = x.shape
+        N = w.size(0)
+        gy = gy.float().contiguous()
+        L, st = _lib.lib(), _lib.current_stream()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            _lib.check(L.dcf_op_conv5s2_bwd_data(_lib.ptr(gy), _lib.ptr(m), _lib.ptr(w), _lib.ptr(gx), B, T, Cin, N, st), 'dcf_op_conv5s2_bwd_data')
+        if ctx.needs_input_grad[2]:
+            gw = torch.empty_like(w)
+            _lib.check(L.dcf_op_conv5s2_bwd_weight(_lib.ptr(x), _lib.ptr(m), _lib.ptr(gy), _lib.ptr(gw), B, T, Cin, N, 0, st),
+                       'dcf_op_conv5s2_bwd_weight')
+        return gx, None, gw
+
+
 class _ChannelLayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
@@ -171,10 +217,27 @@ class _WindowAttentionFn(torch.autograd.Function):
         return gq, gk, gv, None, None, None
 
 
-def masked_conv1d(x, mask, weight, bias=None):
+def masked_conv1d(x, mask, weight, bias=None, stride=1):
     """MaskedConv1D.forward (blocks.py:87-106; stride 1, groups 1, k = 1 or 3, padding (k - 1) / 2) on token-major ``x`` (B, T, Cin):
-    ``conv(x * mask) + bias`` -> (B, T, N).  ``mask``: (B, T) or (B, 1, T) bool, None = all valid; ``weight``: (N, Cin, k)."""
-    return _MaskedConv1dFn.apply(x, mask, weight, bias)
+    ``conv(x * mask) + bias`` -> (B, T, N).  ``mask``: (B, T) or (B, 1, T) bool, None = all valid; ``weight``: (N, Cin, k).
+    ``stride=2`` admits exactly k = 5 (padding 2) without bias, T even -> (B, T / 2, N); the mask that goes with the result is
+    ``mask[:, ::2]`` (``strided_masked_conv1d`` returns it)."""
+    if stride == 1:
+        return _MaskedConv1dFn.apply(x, mask, weight, bias)
+    if stride != 2:
+        raise ValueError(f'masked_conv1d: stride = {stride} (1, or 2 with k = 5)')
+    if bias is not None:
+        raise ValueError('masked_conv1d: stride = 2 is the k = 5 embedding convolution, which has no bias')
+    return _MaskedConv5s2Fn.apply(x, mask, weight)
+
+
+def strided_masked_conv1d(x, mask, weight):
+    """``masked_conv1d(x, mask, weight, stride=2)`` with the mask the reference hands on (blocks.py:101-105, nearest = every other
+    position) -> ((B, T / 2, N), ``mask[:, ::2]``; None stays None)."""
+    B, T, _ = x.shape
+    y = masked_conv1d(x, mask, weight, None, 2)
+    m = _mask_rows(mask, B, T)
+    return y, (None if m is None else m[:, ::2].contiguous())
 
 
 def channel_layer_norm(x, weight, bias, relu=False):
@@ -407,27 +470,49 @@ def conv_attn_layer(x, mask, layer):
 
 def transformer_encoder(x, mask, block):
     """TransformerEncoder.forward (blocks.py:578-591) on token-major ``x`` (B, T, C), with ``block`` a modeling.TransformerEncoder of
-    stride 1 or 2 and ``window_size > 0`` (a stem or pyramid block of the video encoder) -> (y (B, T / stride, C), ``mask[:, ::stride]``).
+    stride 1 or 2 and ``window_size > 0`` (a stem or pyramid block of the video encoder) -> (y (B, T / stride, C), ``mask[:, ::stride]``),
+    or of stride 0 and ``window_size = 0`` (a block of the text encoder: no depthwise convolutions, q = k = v = ln_attn(x * mask) through
+    the global branch of MaskedMHA, ``xattn_mha``; ``cross_attention``'s limits apply and are raised with its own message before
+    anything runs: at most 64 positions, head dimension 16 / 32 / 64 / 128) -> (y (B, T, C), mask).
     To the letter: the input is multiplied by the mask (:581); at stride 2 the skip is masked_max_pool1d of that (:584) but is masked
     with the convolution's mask ``mask[:, ::2]``, not with the pooled one (:586); the output is not masked, so padded rows hold
     ``drop_path_attn.scale * attn.proj.bias``.  No attention / projection dropout and no
     drop-path: the block with every dropout probability at 0."""
-    if block.stride not in (1, 2):
-        raise ValueError(f'transformer_encoder: stride = {block.stride}: only the video encoder\'s blocks (stride 1 or 2) have a backward; '
-                         f'stride 0 is the text encoder')
-    if block.window_size <= 0:
-        raise ValueError('transformer_encoder: window_size = 0 (global attention) has no backward')
-    B, T, _ = x.shape
-    if T % block.stride:
+    if block.stride not in (0, 1, 2):
+        raise ValueError(f'transformer_encoder: stride = {block.stride} (0: the text encoder, 1 or 2: the video encoder)')
+    if (block.stride == 0) != (block.window_size == 0):
+        raise ValueError(f'transformer_encoder: stride = {block.stride} with window_size = {block.window_size}: global attention (window_size = 0) '
+                         f'has a backward in the stride-0 blocks of the text encoder alone, and those have no local window')
+    B, T, C = x.shape
+    if block.stride and T % block.stride:
         raise ValueError(f'transformer_encoder: T = {T} must be a multiple of the stride {block.stride}')
+    if block.stride == 0:
+        # the block is known to be unsupported before anything is launched: cross_attention's own message, with the block named
+        limit = _cross_attention_limit(T, C, block.attn.attn.n_heads)
+        if limit:
+            raise ValueError(f'transformer_encoder: stride = 0 (global self-attention of the text encoder): {limit}')
     if mask is None:
         mask = torch.ones(B, T, dtype=torch.bool, device=x.device)
     x = _LayerScaleResidualFn.apply(x, None, None, mask, None)
-    skip = masked_max_pool1d(x, mask)[0] if block.stride == 2 else x
-    h, mask = conv_attn_layer(channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias), mask, block.attn)
+    if block.stride == 0:
+        mask = _mask_rows(mask, B, T)
+        q = channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias)
+        skip, h = x, xattn_mha(q, q, mask, block.attn.attn)
+    else:
+        skip = masked_max_pool1d(x, mask)[0] if block.stride == 2 else x
+        h, mask = conv_attn_layer(channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias), mask, block.attn)
     x = layer_scale_residual(skip, h, block.drop_path_attn.scale, r_mask=mask)
     h = ffn(channel_layer_norm(x, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn)
     return layer_scale_residual(x, h, block.drop_path_ffn.scale, h_mask=mask), mask
+
+
+def _cross_attention_limit(Lk, C, n_heads):
+    """the message of the limit of ``cross_attention`` that (Lk keys, C channels on n_heads heads) breaks, or None"""
+    if not 1 <= Lk <= 64:
+        return f'cross_attention: Lk = {Lk} keys (1 to 64 have a backward)'
+    if C % n_heads or C // n_heads not in (16, 32, 64, 128):
+        return f'cross_attention: C = {C} on {n_heads} heads: the head dimension must be 16, 32, 64 or 128'
+    return None
 
 
 class _CrossAttentionFn(torch.autograd.Function):
@@ -438,10 +523,9 @@ class _CrossAttentionFn(torch.autograd.Function):
         Lk = kd.size(1)
         if kd.shape != (B, Lk, C) or vd.shape != kd.shape:
             raise ValueError(f'cross_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree ((B, T, C) and (B, Lk, C))')
-        if not 1 <= Lk <= 64:
-            raise ValueError(f'cross_attention: Lk = {Lk} keys (1 to 64 have a backward)')
-        if C % n_heads or C // n_heads not in (16, 32, 64, 128):
-            raise ValueError(f'cross_attention: C = {C} on {n_heads} heads: the head dimension must be 16, 32, 64 or 128')
+        limit = _cross_attention_limit(Lk, C, n_heads)
+        if limit:
+            raise ValueError(limit)
         m = _byte_mask(kv_mask, B, Lk, 'cross_attention')
         if m is None:
             m = torch.ones(B, Lk, dtype=torch.bool, device=qd.device)      # the forward core reads its mask unconditionally
@@ -742,3 +826,72 @@ def fuse_and_predict(fpn, fpn_masks, model, dropout=None, text=None, text_mask=N
     logits2 = [conv_head(x, m, model.cls_head2) for x, m in zip(new_fpn, masks)]
     offsets = [conv_head(x, m, model.reg_head, level=l) for l, (x, m) in enumerate(zip(new_fpn, masks))]
     return tuple(logits1), tuple(logits2), tuple(offsets), tuple(masks)
+
+
+def _position_term(module, t, mask, name):
+    """``pe[:t] * mask`` of a backbone (video_net.py:75-78, :141-151 / text_net.py:121-124, :166-176; the training branch), token-major
+    (B, t, E), or None without ``use_abs_pe``"""
+    if not module.use_abs_pe:
+        return None
+    if t > module.max_seq_len:
+        raise ValueError(f'{name}: {t} positions exceed max_seq_len = {module.max_seq_len} (the training branch does not resample the '
+                         f'position encoding)')
+    pe = getattr(module, 'pe', None)
+    if pe is None:
+        from .modeling import sinusoid_encoding
+        pe = sinusoid_encoding(module.max_seq_len, module.embd_dim // 2) / module.embd_dim ** 0.5
+    pe = pe[:, :t].t().to(device=mask.device, dtype=torch.float32)
+    return pe[None] * mask[..., None].to(torch.float32)
+
+
+def video_transformer(x, mask, vid_net):
+    """VideoTransformer.forward (video_net.py:123-164, the training branch) on token-major ``x`` (B, T, in_dim), with ``vid_net`` a
+    modeling.VideoTransformer -> (fpn, fpn_masks), tuples over the pyramid levels of (B, T_l, E) and (B, T_l) bool.  To the letter:
+    the output of embd_fc is not masked (:133; the convolution behind it masks its input); each embedding convolution, k = 3 or
+    k = 5 / stride 2, is followed by LayerNorm + ReLU; ``pe[:t] * mask`` is added under the mask of the shortened sequence; a
+    ``pool_only`` branch layer is one depthwise k = 3 convolution, stride 1 at the first level and 2 after it."""
+    B, T, _ = x.shape
+    mask = torch.ones(B, T, dtype=torch.bool, device=x.device) if mask is None else _byte_mask(mask, B, T, 'video_transformer')
+    x = masked_conv1d(x, mask, vid_net.embd_fc.conv.weight, vid_net.embd_fc.conv.bias)
+    for conv, norm in zip(vid_net.embd_convs, vid_net.embd_norms):
+        if conv.stride == 2:
+            x, mask = strided_masked_conv1d(x, mask, conv.conv.weight)
+        else:
+            x = masked_conv1d(x, mask, conv.conv.weight, conv.conv.bias)
+        x = channel_layer_norm(x, norm.weight, norm.bias, relu=True)
+    pe = _position_term(vid_net, x.size(1), mask, 'video_transformer')
+    if pe is not None:
+        x = x + pe
+    for block in vid_net.stem:
+        x, mask = transformer_encoder(x, mask, block)
+    fpn, fpn_masks = [], []
+    for block in vid_net.branch:
+        if vid_net.pool_only:
+            (x,), mask = depthwise_conv1d(x, mask, [block.conv.weight], block.stride)
+        else:
+            x, mask = transformer_encoder(x, mask, block)
+        fpn.append(x)
+        fpn_masks.append(mask)
+    return tuple(fpn), tuple(fpn_masks)
+
+
+def text_transformer(tokens, mask, text_net):
+    """TextTransformer.forward (text_net.py:158-188, the training branch) on token-major ``tokens`` (B, L, in_dim), with ``text_net`` a
+    modeling.TextTransformer -> ((B, L [+ 1], TE), mask (B, L [+ 1])).  To the letter: the background token is prepended to every
+    sequence and the mask is extended by its own first column (:179-182); the gradient of ``bkgd_token`` is the sum over the batch.
+    The blocks are global self-attention: L [+ 1] <= 64."""
+    if not hasattr(text_net, 'bkgd_token') or not hasattr(text_net, 'transformer') or hasattr(text_net, 'attn_pool'):
+        raise ValueError(f'text_transformer: {type(text_net).__name__} is not differentiable yet (TextIdentity\'s attention pool has no '
+                         f'backward); a modeling.TextTransformer is required')
+    B, L, _ = tokens.shape
+    mask = torch.ones(B, L, dtype=torch.bool, device=tokens.device) if mask is None else _byte_mask(mask, B, L, 'text_transformer')
+    x = masked_conv1d(tokens, mask, text_net.embd_fc.conv.weight, text_net.embd_fc.conv.bias)
+    pe = _position_term(text_net, L, mask, 'text_transformer')
+    if pe is not None:
+        x = x + pe
+    if text_net.bkgd_token is not None:
+        x = torch.cat((text_net.bkgd_token.t()[None].expand(B, -1, -1).to(x.dtype), x), dim=1)
+        mask = torch.cat((mask[:, :1], mask), dim=1)
+    for block in text_net.transformer:
+        x, _ = transformer_encoder(x, mask, block)
+    return x, mask

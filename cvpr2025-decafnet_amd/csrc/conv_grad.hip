@@ -30,11 +30,30 @@
 // LayerNorm backward (k_ln_bwd): a wave owns a run of rows, keeps x and dOut of a row in registers (one read of each, one write of
 // dX), recomputes mean / rstd two-pass exactly like row_layernorm, masks by the recomputed output (out > 0) and accumulates
 // dw = sum dy xhat, db = sum dy per lane; workgroup partials, fixed-order final sum.
+//
+// k = 5 / stride 2 / padding 2 (the embedding convolutions of vid_net.stride > 1, video_net.py:62-70; T even, To = T / 2, no bias):
+//
+//   forward      Y[b,u,n]  = sum_{j<5} sum_c W[n,c,j] m[b,2u+j-2] X[b,2u+j-2,c]
+//   weight grad  dW[n,c,j] = sum_{b,u} dY[b,u,n] m X[b,2u+j-2,c]
+//   data grad    dX[b,t,c] = m[b,t] sum_{j = t (mod 2), 0 <= (t+2-j)/2 < To} sum_n dY[b,(t+2-j)/2,n] W[n,c,j]
+//
+// dcf_op_conv5s2_split is the forward's own path (launch_im2col5s2 into a scratch, then the split GEMM on K = 5 Cin).  The weight
+// gradient (k_wgrad5) is k_wgrad's scheme with the reduction over the OUTPUT rows: because T = 2 To, output row r of the flattened
+// batch reads input rows 2 r - 2 .. 2 r + 2, so a thread that stages output rows r .. r + 7 reads input rows 2 r - 2 .. 2 r + 16 of its
+// column once (19 loads, converted once) and writes five seam- and mask-gated vectors per plane.  LDS per workgroup: dY 2 planes x 64
+// columns x WG_PITCH halfs = 10 240 B, X 5 taps x 2 planes x 64 x WG_PITCH halfs = 51 200 B, 61 440 B in all (k = 3: 41 984 B with
+// the bias sums): LDS alone admits two workgroups per CU of 160 KiB where k = 3 has three, but the five accumulators and the 19-row
+// staging take 276 registers (no spills), one wave per SIMD: one workgroup per CU is resident; every 16-byte vector stays aligned
+// because the tap and plane strides are multiples of 64 * WG_PITCH halfs = 5 120 B and a row run starts at a multiple of 8 halfs.
+// The data gradient splits the input rows by parity: even rows 2 u take taps 4, 2, 0 of the output rows u - 1, u, u + 1 and odd rows
+// 2 u + 1 take taps 3, 1 of u, u + 1 -- two tap-3 row GEMMs on dY itself (one launch, count = 2), each writing every other row of dX
+// (row pitch 2 Cin); the odd one carries a zero image for its first tap, because the row GEMM has three taps: 6 taps of work for 5.
 #include <mutex>
 #include "../../include/decafnet_hip.h"
 #include "common.h"
 #include "conv_grad.h"
 #include "gemm.h"
+#include "rowops.h"
 
 namespace dcf {
 
@@ -208,6 +227,126 @@ __global__ __launch_bounds__(256) void k_wgrad(ConvGradArgs p) {
   }
 }
 
+// k = 5 / stride 2: the reduction runs over the output rows of the flattened batch (rows = B * To); output row r reads input rows
+// 2 r + j - 2 (T = 2 To).  flags (per OUTPUT row): bit1 = an output row to the left exists in the sequence (taps 0, 1 stay inside),
+// bit2 = one to the right (tap 4 stays inside).  mask (per INPUT row) may be null.
+__global__ __launch_bounds__(256) void k_wgrad5(ConvGradArgs p, const uint8_t* __restrict__ mask) {
+  constexpr int KT = 5, XN = 19;             // input rows 2 r0 - 2 .. 2 r0 + 16 for output rows r0 .. r0 + 7
+  __shared__ __attribute__((aligned(16))) _Float16 s_dy[2 * 64 * WG_PITCH];
+  __shared__ __attribute__((aligned(16))) _Float16 s_x[KT * 2 * 64 * WG_PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tiles_c = (p.Cin + 63) / 64;
+  const int tn = blockIdx.x / tiles_c, tc = blockIdx.x - tn * tiles_c;
+  const int slice = blockIdx.y;
+  const int r_begin = slice * p.slice_rows;
+  const int r_end = r_begin + p.slice_rows < p.rows ? r_begin + p.slice_rows : p.rows;
+  float inv;
+  const float s = cg_scale(*p.absmax, inv);
+  const int n_g = tn * 64 + lane, c_g = tc * 64 + lane;
+  const bool n_ok = n_g < p.N, c_ok = c_g < p.Cin;
+  const float* __restrict__ dyp = p.dY + n_g;
+  const float* __restrict__ xp = p.X + c_g;
+  const uint8_t* __restrict__ flags = p.flags;
+  const int N = p.N, Cin = p.Cin, rows = p.rows;
+  const int64_t rows_in = 2 * (int64_t)rows;
+
+  float dyv[8], xv[XN];
+  unsigned fl[8];
+  auto load = [&](int r0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int r = r0 + i;
+      const bool ok = r < r_end;
+      dyv[i] = (n_ok && ok) ? dyp[(int64_t)r * N] : 0.f;
+      fl[i] = ok ? (unsigned)flags[r] : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < XN; ++i) {
+      const int64_t q = 2 * (int64_t)r0 - 2 + i;
+      const bool ok = c_ok && q >= 0 && q < rows_in && (!mask || mask[q]);
+      xv[i] = ok ? xp[q * Cin] : 0.f;
+    }
+  };
+
+  const int h = lane >> 5, r32 = lane & 31;
+  const int wn = wave & 1, wc = wave >> 1;
+  const bool active = tn * 64 + wn * 32 < N && tc * 64 + wc * 32 < Cin;
+  f32x16 acc[KT];
+#pragma unroll
+  for (int j = 0; j < KT; ++j)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+
+  load(r_begin + wave * 8);
+  for (int r0 = r_begin; r0 < r_end; r0 += WG_ROWS) {
+    {
+      f16x8 dh, dl;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float v = dyv[i] * s;
+        const _Float16 hi = (_Float16)v;
+        dh[i] = hi;
+        dl[i] = (_Float16)(v - (float)hi);
+      }
+      *reinterpret_cast<f16x8*>(&s_dy[(0 * 64 + lane) * WG_PITCH + wave * 8]) = dh;
+      *reinterpret_cast<f16x8*>(&s_dy[(1 * 64 + lane) * WG_PITCH + wave * 8]) = dl;
+      _Float16 xh[XN], xl[XN];
+#pragma unroll
+      for (int i = 0; i < XN; ++i) {
+        const _Float16 hi = (_Float16)(xv[i] * WG_SX);
+        xh[i] = hi;
+        xl[i] = (_Float16)__builtin_fmaf(xv[i], WG_SX, -(float)hi);
+      }
+#pragma unroll
+      for (int j = 0; j < KT; ++j) {
+        f16x8 th, tl;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          // tap j of output row r0 + i reads input row 2 (r0 + i) + j - 2 = xv[2 i + j]: inside the sequence for j = 2, 3 always,
+          // for j = 0, 1 if an output row to the left exists, for j = 4 if one to the right does (the mask is in xv)
+          bool ok = true;
+          if (j < 2) ok = (fl[i] & 2u) != 0u;
+          if (j == 4) ok = (fl[i] & 4u) != 0u;
+          th[i] = ok ? xh[2 * i + j] : (_Float16)0.f;
+          tl[i] = ok ? xl[2 * i + j] : (_Float16)0.f;
+        }
+        *reinterpret_cast<f16x8*>(&s_x[((j * 2 + 0) * 64 + lane) * WG_PITCH + wave * 8]) = th;
+        *reinterpret_cast<f16x8*>(&s_x[((j * 2 + 1) * 64 + lane) * WG_PITCH + wave * 8]) = tl;
+      }
+    }
+    __syncthreads();
+    if (r0 + WG_ROWS < r_end) load(r0 + WG_ROWS + wave * 8);
+    if (active) {
+#pragma unroll
+      for (int ks = 0; ks < WG_ROWS / 16; ++ks) {
+        const int ko = ks * 16 + h * 8;
+        const f16x8 a_hi = *reinterpret_cast<const f16x8*>(&s_dy[(0 * 64 + wn * 32 + r32) * WG_PITCH + ko]);
+        const f16x8 a_lo = *reinterpret_cast<const f16x8*>(&s_dy[(1 * 64 + wn * 32 + r32) * WG_PITCH + ko]);
+#pragma unroll
+        for (int j = 0; j < KT; ++j) {
+          const f16x8 b_hi = *reinterpret_cast<const f16x8*>(&s_x[((j * 2 + 0) * 64 + wc * 32 + r32) * WG_PITCH + ko]);
+          const f16x8 b_lo = *reinterpret_cast<const f16x8*>(&s_x[((j * 2 + 1) * 64 + wc * 32 + r32) * WG_PITCH + ko]);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc[j], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  if (active) {
+    const int c = tc * 64 + wc * 32 + r32;
+#pragma unroll
+    for (int j = 0; j < KT; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int n = tn * 64 + wn * 32 + 4 * h + (e & 3) + 8 * (e >> 2);
+        p.part[(((int64_t)slice * N + n) * KT + j) * Cin + c] = acc[j][e];
+      }
+  }
+}
+
 // N = 1, 2: one wave per (64 channels, row slice); a lane owns a channel and slides a 3-row window of its column through registers
 template <int KT, int NO>
 __global__ __launch_bounds__(64) void k_wgrad_small(ConvGradArgs p) {
@@ -313,6 +452,24 @@ __global__ void k_permute_wT(const float* __restrict__ W, float* __restrict__ Wp
   if (i >= N * Cin * k) return;
   const int c = i / (k * N), rem = i - c * k * N, tap = rem / N, n = rem - tap * N;
   Wp[i] = W[((int64_t)n * Cin + c) * k + (k - 1 - tap)];
+}
+
+// k = 5 / stride 2, data gradient: the weight images of the two row GEMMs, Wp[c][tap][n] (tap 0, 1, 2 = output rows u - 1, u, u + 1).
+// parity 0 (input rows 2 u): W[n][c][4 - 2 tap]; parity 1 (rows 2 u + 1): W[n][c][5 - 2 tap], tap 0 has no weight and holds zeros.
+__global__ void k_permute_w5T(const float* __restrict__ W, float* __restrict__ Wp, int N, int Cin, int parity) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * Cin * 3) return;
+  const int c = i / (3 * N), rem = i - c * 3 * N, tap = rem / N, n = rem - tap * N;
+  const int j = 4 + parity - 2 * tap;
+  Wp[i] = j < 5 ? W[((int64_t)n * Cin + c) * 5 + j] : 0.f;
+}
+
+// forward: Wf[n][j][c] = W[n][c][j], the [N][tap][cin] rows of the forward GEMM
+__global__ void k_permute_w5(const float* __restrict__ W, float* __restrict__ Wf, int N, int Cin) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * Cin * 5) return;
+  const int n = i / (5 * Cin), rem = i - n * 5 * Cin, j = rem / Cin, c = rem - j * Cin;
+  Wf[i] = W[((int64_t)n * Cin + c) * 5 + j];
 }
 
 __global__ __launch_bounds__(256) void k_dx_finish(float* __restrict__ dX, const uint8_t* __restrict__ mask, const unsigned* __restrict__ absmax,
@@ -617,6 +774,130 @@ int dcf_op_conv_bwd_data(const float* dY, const uint8_t* mask, const float* W_oc
     hipLaunchKernelGGL(k_dx_finish, dim3(grid_for((int64_t)rows * (Cin / 4), 256, 8192)), dim3(256), 0, st, dX, mask, word, (int64_t)rows,
                        Cin / 4, status);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv_bwd_data: launch failed"); rc = -1; }
+  }
+  DCF_HIP(hipFreeAsync(dys, st)); DCF_HIP(hipFreeAsync(wp, st)); DCF_HIP(hipFreeAsync(planes, st)); DCF_HIP(hipFreeAsync(word, st));
+  DCF_HIP(hipFreeAsync(flags, st));
+  if (rc == 0) rc = cg_end(st);
+  return rc;
+}
+
+static int conv5s2_check(const char* what, int32_t B, int32_t T, int32_t Cin, int32_t N) {
+  DCF_CHECK(B > 0 && T > 0, "%s: empty batch", what);
+  DCF_CHECK(T % 2 == 0, "%s: T = %d must be even (stride 2)", what, T);
+  DCF_CHECK(Cin > 0 && Cin % 32 == 0, "%s: Cin = %d must be a positive multiple of 32", what, Cin);
+  DCF_CHECK(N > 0 && N % 32 == 0, "%s: N = %d must be a positive multiple of 32", what, N);
+  DCF_CHECK((int64_t)B * T < (1ll << 31) - 64, "%s: %lld rows (< 2^31)", what, (long long)B * T);
+  return 0;
+}
+
+int dcf_op_conv5s2_split(const float* X, const uint8_t* mask, const float* W_ock, float* Y, int32_t B, int32_t T, int32_t Cin,
+                         int32_t N, int32_t nterms, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  DCF_CHECK(X && W_ock && Y, "dcf_op_conv5s2_split: null argument");
+  if (conv5s2_check("dcf_op_conv5s2_split", B, T, Cin, N)) return -1;
+  DCF_CHECK(nterms == GEMM_F16X3 || nterms == GEMM_BF16X6, "dcf_op_conv5s2_split: nterms = %d (16 = f16x3, 6 = bf16x6)", nterms);
+  const int rows_in = B * T, rows = rows_in / 2, K = 5 * Cin;
+  float *col = nullptr, *wf = nullptr;
+  uint8_t* ones = nullptr;
+  unsigned short* planes = nullptr;
+  DCF_HIP(hipMallocAsync((void**)&col, (size_t)rows * K * sizeof(float), st));
+  DCF_HIP(hipMallocAsync((void**)&wf, (size_t)N * K * sizeof(float), st));
+  DCF_HIP(hipMallocAsync((void**)&planes, (size_t)3 * N * K * sizeof(unsigned short), st));
+  if (!mask) {
+    DCF_HIP(hipMallocAsync((void**)&ones, (size_t)rows_in, st));
+    DCF_HIP(hipMemsetAsync(ones, 1, (size_t)rows_in, st));
+  }
+  hipLaunchKernelGGL(k_permute_w5, dim3((N * K + 255) / 256), dim3(256), 0, st, W_ock, wf, N, Cin);
+  int rc = launch_im2col5s2(X, Cin, mask ? mask : ones, col, B, T, Cin, st);
+  if (rc == 0) rc = launch_split_planes(wf, planes, N, K, K, st, nterms);
+  if (rc == 0) {
+    GemmArgs g{};
+    g.A = col; g.lda = K; g.W = wf; g.ldw = 0; g.Ws = planes; g.C = Y; g.ldc = N; g.M = rows; g.N = N; g.K = K;
+    rc = launch_gemm_split(&g, 1, A_ROWS, nterms, st);
+  }
+  DCF_HIP(hipFreeAsync(col, st)); DCF_HIP(hipFreeAsync(wf, st)); DCF_HIP(hipFreeAsync(planes, st));
+  if (ones) DCF_HIP(hipFreeAsync(ones, st));
+  return rc;
+}
+
+int dcf_op_conv5s2_bwd_weight(const float* X, const uint8_t* mask, const float* dY, float* dW_ock, int32_t B, int32_t T, int32_t Cin,
+                              int32_t N, int32_t accumulate, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  DCF_CHECK(X && dY && dW_ock, "dcf_op_conv5s2_bwd_weight: null argument");
+  if (conv5s2_check("dcf_op_conv5s2_bwd_weight", B, T, Cin, N)) return -1;
+  const int To = T / 2, rows = B * To;
+  unsigned* status = nullptr;
+  if (cg_begin("dcf_op_conv5s2_bwd_weight", st, &status)) return -1;
+  ConvGradArgs a{};
+  a.X = X; a.dY = dY; a.rows = rows; a.Cin = Cin; a.N = N; a.k = 5;
+  const int per = (rows + CG_MAX_SLICES - 1) / CG_MAX_SLICES;
+  a.slice_rows = (per + WG_ROWS - 1) / WG_ROWS * WG_ROWS;
+  a.nslices = (rows + a.slice_rows - 1) / a.slice_rows;
+  const int64_t count = (int64_t)N * 5 * Cin;
+  float* part = nullptr;
+  uint8_t* flags = nullptr;
+  unsigned* word = nullptr;
+  DCF_HIP(hipMallocAsync((void**)&part, (size_t)a.nslices * count * sizeof(float), st));
+  DCF_HIP(hipMallocAsync((void**)&flags, (size_t)rows, st));
+  DCF_HIP(hipMallocAsync((void**)&word, sizeof(unsigned), st));
+  // per output row: does an output row to the left / right exist in its sequence (the input rows' mask is read by the kernel)
+  hipLaunchKernelGGL(k_seqflags, dim3((rows + 255) / 256), dim3(256), 0, st, (const uint8_t*)nullptr, flags, To, rows, 1);
+  int rc = launch_absmax(dY, (int64_t)rows * N, word, st);
+  a.flags = flags; a.absmax = word; a.part = part; a.dbpart = nullptr;
+  if (rc == 0) {
+    const dim3 grid(((N + 63) / 64) * ((Cin + 63) / 64), a.nslices);
+    hipLaunchKernelGGL(k_wgrad5, grid, dim3(256), 0, st, a, mask);
+    hipLaunchKernelGGL(k_cg_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part, a.nslices, count, (int)count, word,
+                       1.f / WG_SX, dW_ock, 5, Cin, accumulate, status);
+    if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv5s2_bwd_weight: launch failed"); rc = -1; }
+  }
+  DCF_HIP(hipFreeAsync(part, st)); DCF_HIP(hipFreeAsync(flags, st)); DCF_HIP(hipFreeAsync(word, st));
+  if (rc == 0) rc = cg_end(st);
+  return rc;
+}
+
+int dcf_op_conv5s2_bwd_data(const float* dY, const uint8_t* mask, const float* W_ock, float* dX, int32_t B, int32_t T, int32_t Cin,
+                            int32_t N, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  DCF_CHECK(dY && W_ock && dX, "dcf_op_conv5s2_bwd_data: null argument");
+  if (conv5s2_check("dcf_op_conv5s2_bwd_data", B, T, Cin, N)) return -1;
+  const int To = T / 2, rows = B * To, K = 3 * N;
+  unsigned* status = nullptr;
+  if (cg_begin("dcf_op_conv5s2_bwd_data", st, &status)) return -1;
+  uint8_t* flags = nullptr;
+  float *dys = nullptr, *wp = nullptr;
+  unsigned short* planes = nullptr;
+  unsigned* word = nullptr;
+  const size_t img = (size_t)Cin * K;
+  DCF_HIP(hipMallocAsync((void**)&flags, (size_t)rows, st));
+  DCF_HIP(hipMallocAsync((void**)&dys, (size_t)rows * N * sizeof(float), st));
+  DCF_HIP(hipMallocAsync((void**)&wp, 2 * img * sizeof(float), st));
+  DCF_HIP(hipMallocAsync((void**)&planes, 2 * 3 * img * sizeof(unsigned short), st));
+  DCF_HIP(hipMallocAsync((void**)&word, sizeof(unsigned), st));
+  // neighbour flags of the OUTPUT rows from the sequence ends alone: dY at a padded output row is a legitimate operand
+  hipLaunchKernelGGL(k_seqflags, dim3((rows + 255) / 256), dim3(256), 0, st, (const uint8_t*)nullptr, flags, To, rows, 1);
+  int rc = launch_absmax(dY, (int64_t)rows * N, word, st);
+  if (rc == 0) {
+    hipLaunchKernelGGL(k_scale_copy, dim3(grid_for((int64_t)rows * N, 1024, 4096)), dim3(256), 0, st, dY, dys, (int64_t)rows * N, word);
+    for (int par = 0; par < 2 && rc == 0; ++par) {
+      hipLaunchKernelGGL(k_permute_w5T, dim3((unsigned)((img + 255) / 256)), dim3(256), 0, st, W_ock, wp + par * img, N, Cin, par);
+      rc = launch_split_planes(wp + par * img, planes + par * 3 * img, Cin, K, K, st, GEMM_F16X3, status);
+    }
+  }
+  if (rc == 0) {
+    // input rows 2 u (parity 0) and 2 u + 1 (parity 1) of dX: row u of GEMM `par` lands at dX + (2 u + par) Cin
+    GemmArgs g[2] = {};
+    for (int par = 0; par < 2; ++par) {
+      g[par].A = dys; g[par].lda = N; g[par].W = wp + par * img; g[par].ldw = K; g[par].Ws = planes + par * 3 * img;
+      g[par].C = dX + (size_t)par * Cin; g[par].ldc = 2 * (int64_t)Cin; g[par].M = rows; g[par].N = Cin; g[par].K = K;
+      g[par].status = status; g[par].a_scale = 1.f; g[par].cin = N; g[par].nbr = flags;
+    }
+    rc = launch_gemm_split(g, 2, A_ROWS_TAP3, GEMM_F16X3, st);
+  }
+  if (rc == 0) {
+    hipLaunchKernelGGL(k_dx_finish, dim3(grid_for((int64_t)2 * rows * (Cin / 4), 256, 8192)), dim3(256), 0, st, dX, mask, word, (int64_t)2 * rows,
+                       Cin / 4, status);
+    if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv5s2_bwd_data: launch failed"); rc = -1; }
   }
   DCF_HIP(hipFreeAsync(dys, st)); DCF_HIP(hipFreeAsync(wp, st)); DCF_HIP(hipFreeAsync(planes, st)); DCF_HIP(hipFreeAsync(word, st));
   DCF_HIP(hipFreeAsync(flags, st));

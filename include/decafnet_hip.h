@@ -469,6 +469,24 @@ int dcf_op_conv_bwd_weight(const float* X, const uint8_t* mask, const float* dY,
                            int32_t Cin, int32_t N, int32_t k, int32_t accumulate, void* stream);
 int dcf_op_layernorm_bwd(const float* X, const float* w, const float* b, const float* dOut, float* dX, float* dw, float* db,
                          int32_t rows, int32_t C, int32_t relu, int32_t accumulate, void* stream);
+/* The k = 5 / stride 2 / padding 2 MaskedConv1D of vid_net.stride > 1 (video_net.py:62-70; dense, no bias) as a single operator and
+ * its two gradients (additions to ABI version 12), on token-major fp32 rows, T even, To = T / 2:
+ *   dcf_op_conv5s2_split      : Y[b,u,n]  = sum_{j<5} sum_c W[n,c,j] m[b,2u+j-2] X[b,2u+j-2,c]   (taps stay inside sequence b; Y (B*To, N)
+ *                               is not masked; the mask that goes on is m[b,2u], blocks.py:101-105) -- the forward's own path: the five
+ *                               taps gathered into rows, then the split-operand GEMM (nterms 16 = f16x3, 6 = bf16x6)
+ *   dcf_op_conv5s2_bwd_weight : dW[n,c,j] = sum_{b,u} dY[b,u,n] m[b,2u+j-2] X[b,2u+j-2,c]
+ *   dcf_op_conv5s2_bwd_data   : dX[b,t,c] = m[b,t] sum_{j = t (mod 2), 0 <= (t+2-j)/2 < To} sum_n dY[b,(t+2-j)/2,n] W[n,c,j]
+ * W_ock / dW_ock: PyTorch's (N, Cin, 5) layout.  mask (B*T bytes, the INPUT rows) NULL = every row valid.  Cin % 32 == 0, N % 32 == 0,
+ * T even; anything else fails with a message.  The gradients are f16x3 on the matrix cores with the device-side power-of-two scale of
+ * dY, fixed-order sums without floating-point atomics (bit-identical from run to run; a power of two on dY scales them by exactly
+ * that) and the sticky numerics word of dcf_op_conv_bwd_data / _weight: after a non-finite sum the NEXT call of any of these
+ * functions returns -1 once. */
+int dcf_op_conv5s2_split(const float* X, const uint8_t* mask, const float* W_ock, float* Y, int32_t B, int32_t T, int32_t Cin,
+                         int32_t N, int32_t nterms, void* stream);
+int dcf_op_conv5s2_bwd_data(const float* dY, const uint8_t* mask, const float* W_ock, float* dX, int32_t B, int32_t T, int32_t Cin,
+                            int32_t N, void* stream);
+int dcf_op_conv5s2_bwd_weight(const float* X, const uint8_t* mask, const float* dY, float* dW_ock, int32_t B, int32_t T, int32_t Cin,
+                              int32_t N, int32_t accumulate, void* stream);
 /* cross-attention core (libs/modeling/blocks.py:374-389): Q (B*T, C), K/V (B*Lk, C), kvmask (B*Lk) -> O (B*T, C) */
 int dcf_op_xattn(const float* Q, const float* K, const float* V, const uint8_t* kvmask, float* O, int32_t B, int32_t T,
                  int32_t Lk, int32_t C, int32_t heads, void* stream);
