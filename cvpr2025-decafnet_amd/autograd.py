@@ -35,9 +35,14 @@ the three outputs ``loss.PointObjective`` consumes, with a graph.  The refinemen
 dropout in training (tcn.py:5,13: 0.5), so these three take ``dropout = (seed, p, b0)``: the keep bits are those of the training
 forward (``model.enable_dropout``; csrc/dropout.h), recomputed in the backward.
 
+``vid_map`` needs no function of its own: it is ``masked_conv1d`` (k = 1) on the gated, concatenated input under the mask after the
+gate, and composed that way -- gate, ``vid_map``, ``text_transformer``, the first ``xattn_fusion``, ``video_transformer``,
+``fuse_and_predict``, ``loss.PointObjective`` -- the whole training step reproduces the reference's ``backward()`` on every parameter
+(tests/step_grad_ref.py ``run_step``, tests/test_gpu_step_grad.py).
+
 Without a backward yet: the gate (it has no parameters: its inputs are features the caller supplies, so it does not stand between these
-functions and a training step), ``vid_map`` on the gated input as one function, TextIdentity's attention pool (``text_transformer``
-refuses a TextIdentity) and global self-attention over more than 64 positions.
+functions and a training step), TextIdentity's attention pool (``text_transformer`` refuses a TextIdentity) and global self-attention
+over more than 64 positions.
 """
 import torch
 
