@@ -27,6 +27,17 @@ class DcfConfig(ctypes.Structure):
                                                       'scat', 'sfonly', 'text_kind', 'xattn_affine', 'vid_stride', 'pool_only', 'attn_mode')]
 
 
+class DcfOptimGroup(ctypes.Structure):
+    """dcf_optim_group: one parameter group's hyper-parameters of dcf_optim_adam_step (a host array, passed by value with the launch)"""
+    _fields_ = [(n, f32) for n in ('lr', 'weight_decay', 'b1', 'b2', 'one_minus_b1', 'one_minus_b2', 'eps', 'bc1', 'sqrt_bc2')] + [('mode', i32)]
+
+
+OPTIM_CHUNK = 4096            # DCF_OPTIM_CHUNK: elements per workgroup of the dcf_optim_* kernels
+OPTIM_MAX_GROUPS = 8          # DCF_OPTIM_MAX_GROUPS
+OPTIM_NO_GRAD = 1             # DCF_OPTIM_NO_GRAD
+OPTIM_MODES = {'adamw': 0, 'adam': 1}
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     'dcf_last_error': (ctypes.c_char_p, []),
@@ -120,6 +131,9 @@ SIGNATURES = {
     'dcf_op_enc_pre': (i32, [vp, ctypes.c_char_p, c_f32p, c_u8p, i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, vp]),
     'dcf_op_decoder': (i32, [vp, ctypes.c_char_p, c_f32p, c_u8p, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i32), vp]),
     'dcf_op_tcn': (i32, [vp, ctypes.c_char_p, c_f32p, c_u8p, i32, i32, i32, i32, c_f32p, vp]),
+    'dcf_optim_grad_norm': (i32, [vp, c_i32p, i32, i64, f32, c_f32p, c_f32p, vp]),
+    'dcf_optim_scale': (i32, [vp, c_i32p, i32, i64, c_f32p, vp]),
+    'dcf_optim_adam_step': (i32, [vp, c_i32p, i32, i64, vp, i32, c_f32p, i32, f32, vp]),
 }
 
 

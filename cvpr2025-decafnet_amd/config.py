@@ -68,6 +68,12 @@ def make_opt(D=1024, E=256, TE=256, text_in=300, n_levels=8, win=9, n_heads=4, s
         # the Trainer's objective (libs/core/opt.py:132-134, :147-157): read by loss.PointObjective / evaluator.calc_loss
         train=dict(center_sampling='radius', center_sampling_radius=1.5, loss_norm=160, loss_norm_momentum=0.9, loss_weight=1.0,
                    reg_loss='diou'),
+        # libs/core/opt.py:160-169: read by optim.make_optimizer / optim.make_scheduler.  epochs / warmup_epochs are the reference's
+        # train.epochs / train.warmup_epochs (opt.py:149-150) where its own post-processing puts them for make_scheduler (opt.py:467-468);
+        # train.TrainStep lets opt.train.epochs / warmup_epochs override them when set, reads opt.train.ema_beta with the Trainer's
+        # default of 0.999 (worker_v2.py:227) and adds itrs_per_epoch to a copy (worker_v2.py:252)
+        optimizer=dict(name='adamw', lr=1e-3, weight_decay=0.05, clip_grad_norm=1.0),
+        scheduler=dict(name='multistep', steps=(-1,), gamma=0.1, epochs=5, warmup_epochs=5),
         loss=dict(fc_a=0.5, fc_s=0.2),
         eval=dict(ranks=(1, 5), iou_threshs=(0.3, 0.5), pre_nms_thresh=0.001, pre_nms_topk=2000,
                   seg_len_thresh=0.1),

@@ -1,0 +1,134 @@
+"""One training iteration of the reference's Trainer (libs/worker_v2.py:318-325) as a public call.
+
+``training_forward``: the training-mode forward of PtTransformerEarlyFusionIterative (model.py:567-632) composed from the package's
+differentiable pieces, so that ``backward()`` works on what ``loss.PointObjective`` makes of its outputs.
+``TrainStep``: zero_grad, forward / objective / backward per micro-batch, the loss-norm update, the gradient norm and clip
+coefficient, the fused Adam / AdamW update with the EMA copy (``optim``), scheduler.step().  No host read anywhere in the step.
+
+Not here: the gradient all-reduce over ranks, data loading, logging, AMP, graph capture of the step, SGD.
+"""
+import copy
+
+import torch
+
+from . import _lib, autograd as A, loss as L, optim as O
+
+
+def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_masks, text_size=None, dropout=None):
+    """vid / shallow (bs, D, T) channel-major, vid_masks (bs, T) bool, tokens (B', C_t, Lq) channel-major, text_cls (B', D),
+    token_masks (B', 1, Lq) or (B', Lq), text_size: queries per video (None: one each), B' = sum(text_size), all on the GPU.
+    -> (fpn_logits1, fpn_logits2, fpn_offsets, fpn_masks) as ``model(..., eval=False)`` returns them, with an autograd graph to every
+    parameter of the model.  Per video the sidekick scores and the block top-k gate (dcf_op_sidekick / dcf_op_gate, not
+    differentiated: the gate is a 0 / 1 weight), the product and the concatenation with the shallow features, vid_map, the text
+    encoder, the first fusion, the video encoder, then the heads with the refinement stage (``autograd.fuse_and_predict``).
+    ``dropout``: the (seed, p, b0) of ``autograd.fuse_and_predict`` for the refinement stage's dropout, None for none."""
+    from . import modeling
+    if type(model) is not modeling.PtTransformerEarlyFusionIterative:
+        raise NotImplementedError(f'training_forward: {type(model).__name__} is not implemented (PtTransformerEarlyFusionIterative only)')
+    if model.scat or model.sfonly:
+        raise NotImplementedError('training_forward: opt.model.scat / sfonly are not implemented')
+    if model._dropout_rates() is not None:                          # ... and it refuses opt's own non-zero probabilities, as the forward does
+        raise NotImplementedError('training_forward: enable_dropout() covers the forward values only; pass `dropout` for the refinement stage')
+    if not vid.is_cuda:
+        raise RuntimeError('the training forward runs on the MI355X only: move the inputs to the GPU')
+    lib, st = _lib.lib(), _lib.current_stream()
+    bs, D, T = vid.shape
+    sizes = [1] * bs if text_size is None else [int(k) for k in text_size]
+    nq = sum(sizes)
+    if len(sizes) != bs or min(sizes) < 1 or tokens.size(0) != nq or text_cls.size(0) != nq:
+        raise ValueError(f'text_size {sizes} does not match {bs} videos, {tokens.size(0)} token rows and {text_cls.size(0)} text_cls rows')
+    gates, masks, q = [], [], 0
+    for b, k in enumerate(sizes):                                   # one video and its k queries per call
+        sh, cls = shallow[b].float().contiguous(), text_cls[q:q + k].float().contiguous()
+        vm = vid_masks[b].reshape(-1).to(torch.bool).contiguous()
+        correl = torch.empty(k, T, device=vid.device)
+        _lib.check(lib.dcf_op_sidekick(_lib.ptr(sh), _lib.ptr(cls), _lib.ptr(correl), D, T, k, int(model.norm), st), 'dcf_op_sidekick')
+        gate, mo = torch.empty(k, T, device=vid.device), torch.empty(k, T, dtype=torch.bool, device=vid.device)
+        _lib.check(lib.dcf_op_gate(_lib.ptr(correl), _lib.ptr(vm), _lib.ptr(gate), _lib.ptr(mo), T, k, model.sn, float(model.sratio),
+                                   int(model.msf), st), 'dcf_op_gate')
+        gates.append(gate), masks.append(mo)
+        q += k
+    gate, mask = torch.cat(gates), torch.cat(masks)
+    kv_size = torch.tensor(sizes, device=vid.device)
+    rep = lambda z: z.transpose(1, 2).contiguous().repeat_interleave(kv_size, dim=0)     # model.py:578-581: video b once per query
+    x = rep(vid) * gate[..., None]
+    if model.msf:
+        x = torch.cat([x, rep(shallow)], dim=2)
+    vid_map = A.masked_conv1d(x, mask, model.vid_map.conv.weight, model.vid_map.conv.bias)
+    text, text_mask = A.text_transformer(tokens.transpose(1, 2).contiguous(), token_masks.reshape(nq, -1), model.text_net)
+    fused, fmask = A.xattn_fusion(vid_map, mask, text, text_mask, model.fusion, kv_size)
+    fpn, fpn_masks = A.video_transformer(fused, fmask, model.vid_net)
+    extra = dict(text=text, text_mask=text_mask, kv_size=kv_size) if model.second_fusion else {}
+    if dropout is not None:
+        extra['dropout'] = dropout
+    return A.fuse_and_predict(fpn, fpn_masks, model, **extra)
+
+
+_BATCH_KEYS = ('vid', 'shallow', 'vid_masks', 'tokens', 'text_cls', 'token_masks', 'text_size')
+
+
+class TrainStep:
+    """What the Trainer owns for its iteration: the objective, the optimizer (``optim.make_optimizer``), the scheduler
+    (``optim.make_scheduler``), the EMA copy and the ``itr`` counter.  ``opt`` is the ``config.make_opt`` tree; ``itrs_per_epoch``
+    is what the Trainer takes from its data loader (worker_v2.py:252).  The model is on the GPU."""
+
+    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1):
+        self.model, self.opt = model, opt
+        self.objective = L.PointObjective(opt, world_size=world_size)
+        self.optimizer = O.make_optimizer(model, opt['optimizer'])
+        sched = copy.deepcopy(dict(opt['scheduler']))                       # opt.py:467-468, worker_v2.py:252, on a copy
+        sched.update({k: opt['train'][k] for k in ('epochs', 'warmup_epochs') if k in opt['train']}, itrs_per_epoch=int(itrs_per_epoch))
+        self.scheduler = O.make_scheduler(self.optimizer, sched)
+        self.clip_grad_norm = opt['optimizer']['clip_grad_norm']
+        self.ema = O.ModelEma(model, opt['train'].get('ema_beta', 0.999)).attach(self.optimizer)
+        self.epoch = self.itr = 0
+        self.last_coef = None                                               # the clip coefficient of the last step (a device tensor)
+        self._norm_table = O._Table()
+        self._params = list(model.parameters())
+
+    def step(self, batch, targets):
+        """``batch``: a dict with the arguments of ``training_forward`` (vid, shallow, vid_masks, tokens, text_cls, token_masks,
+        text_size), or a list of such dicts, one per micro-batch, with ``targets`` (B', 2) a tensor or a list alike.  The gradients of
+        the micro-batches accumulate before the one update (worker_v2.py:366-376).
+        -> {'cls', 'reg', 'total', 'grad_norm'}: device tensors, summed over the micro-batches.  ``p.grad`` keeps the UNCLIPPED
+        gradient: the clip coefficient is folded into the update."""
+        batches, targets = ([batch], [targets]) if isinstance(batch, dict) else (list(batch), list(targets))
+        if len(batches) != len(targets) or not batches:
+            raise ValueError(f'{len(batches)} micro-batches and {len(targets)} target tensors')
+        self.optimizer.zero_grad(set_to_none=True)
+        sums = {}
+        for mb, tg in zip(batches, targets):
+            out = training_forward(self.model, *(mb.get(k) for k in _BATCH_KEYS))
+            d = self.objective(out, tg)
+            d['total'].backward()
+            for k, v in d.items():
+                sums[k] = v.detach() if k not in sums else sums[k] + v.detach()
+        self.objective.update_norm(sums.pop('norm'))
+        norm, coef = O.grad_norm_and_coef(self._params, self.clip_grad_norm or 0.0, _table=self._norm_table)
+        self.last_coef = coef if self.clip_grad_norm else None
+        self.optimizer.step(clip_coef=self.last_coef)
+        if self.scheduler is not None:
+            self.scheduler.step()
+        self.itr += 1
+        sums['grad_norm'] = norm
+        return sums
+
+    def state(self):
+        """-> (model_ckpt, state_ckpt) with the keys of Trainer.checkpoint (worker_v2.py:680-689).  'loss_norm' is an addition
+        (the reference does not save its running normaliser) and costs a host read, like the checkpoint itself."""
+        snap = copy.deepcopy                                               # a snapshot: state_dict() hands out the live tensors
+        return ({'model': snap(self.model.state_dict()), 'model_ema': snap(self.ema.state_dict())},
+                {'optimizer': snap(self.optimizer.state_dict()),
+                 'scheduler': None if self.scheduler is None else snap(self.scheduler.state_dict()),
+                 'epoch': self.epoch, 'itr': self.itr, 'loss_norm': self.objective.loss_norm})
+
+    def load_state(self, model_ckpt, state_ckpt):
+        self.model.load_state_dict(model_ckpt['model'])
+        self.ema.load_state_dict(model_ckpt['model_ema'])
+        self.optimizer.load_state_dict(state_ckpt['optimizer'])
+        if self.scheduler is not None:
+            self.scheduler.load_state_dict(state_ckpt['scheduler'])
+        self.epoch, self.itr = state_ckpt['epoch'], state_ckpt['itr']
+        if 'loss_norm' in state_ckpt:
+            self.objective.loss_norm = state_ckpt['loss_norm']
+        return self

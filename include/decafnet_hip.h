@@ -648,6 +648,75 @@ int dcf_op_decoder(dcf_model* m, const char* prefix, float* X, const uint8_t* ma
 int dcf_op_tcn(dcf_model* m, const char* prefix, const float* x, const uint8_t* mask, int32_t B, int32_t T, int32_t n_in,
                int32_t n_layers, float* Y, void* stream);
 
+/* --------------------------------------------------------------------------------------------
+ * The training update (libs/worker_v2.py:320-325): clip_grad_norm_, Adam / AdamW .step() and the EMA copy as multi-tensor kernels
+ * over a DEVICE TABLE that the host builds (additions to ABI version 12).  fp32, no atomics, nothing waits on the host.
+ *
+ * The table: n_tensors rows of dcf_optim_row (64 bytes each, no padding), one per parameter tensor, in device memory.
+ *   p, g, exp_avg, exp_avg_sq, ema : device addresses of n contiguous fp32 each; ema may be NULL (no EMA copy of this tensor); g,
+ *                                    exp_avg and exp_avg_sq are not read when the row has DCF_OPTIM_NO_GRAD.  An address need only be
+ *                                    4-byte aligned: arrays on a 16-byte boundary move through 16-byte accesses, the others and the last
+ *                                    n % 4 elements one element at a time, with the same arithmetic.
+ *   n      : elements (>= 0)
+ *   group  : index into the groups of dcf_optim_adam_step
+ *   flags  : DCF_OPTIM_NO_GRAD = no gradient this step (torch's `grad is None`)
+ *   chunk0 : the PREFIX: the number of chunks of the rows before this one, chunk0[i+1] = chunk0[i] + ceil(n[i] / DCF_OPTIM_CHUNK)
+ * The chunk map: n_chunks int32 in device memory, chunk_map[c] = the row that owns chunk c (rows in ascending order, a row with
+ * n == 0 owns none).  One workgroup runs chunk c: it covers the elements [(c - chunk0) * DCF_OPTIM_CHUNK, + DCF_OPTIM_CHUNK) of its
+ * row, the last chunk of a row being short.  A chunk is DCF_OPTIM_CHUNK = 4096 elements.
+ *
+ * dcf_optim_grad_norm: the L2 norm of every gradient that is present, and torch's clip coefficient.
+ *   Each lane sums the squares of its own 16 elements in fp32; lanes, waves and chunks are added in fp64 in a fixed order (chunk
+ *   partials, then one workgroup over the partials), so the result has the same bits on every run.
+ *   *norm_out = (float) sqrt(sum);  *coef_out = min(1, max_norm / (norm + 1e-6)) in fp32, 1 for max_norm <= 0.  A NaN norm gives a NaN
+ *   coefficient (and an infinite one gives 0), as torch.nn.utils.clip_grad_norm_ does by default.  Either output may be NULL.
+ * dcf_optim_scale: g *= *scale for every gradient that is present (scale: one device float).
+ * dcf_optim_adam_step: one pass.  Per element of a row whose gradient is present, with the row's group h and c = coef ? *coef : 1:
+ *     g' = g c;   DCF_OPTIM_ADAMW: p *= 1 - lr wd;   DCF_OPTIM_ADAM: g' += wd p
+ *     m = b1 m + (1 - b1) g';   v = b2 v + (1 - b2) g'^2;   p -= (lr / bc1) (m / (sqrt(v) / sqrt_bc2 + eps))
+ *   every product, sum, quotient and root rounded once to fp32; 1 - b1 and 1 - b2 are the group's one_minus_b1 / one_minus_b2, taken in
+ *   double on the host (in fp32, 1 - 0.999f is off by 1.3e-5 of its value, and with it the whole second moment).  A row with DCF_OPTIM_NO_GRAD keeps p, exp_avg and exp_avg_sq bit for
+ *   bit.  Then, with_ema != 0 and ema != NULL, gradient or not:  ema = lerp(p_new, ema, beta) by torch's two-branch rule
+ *     beta < 0.5: p + beta (ema - p);   else: ema - (ema - p)(1 - beta)          (beta = 0: p's bits; beta = 1: ema untouched)
+ *   The stored gradients are not written.  `groups` is a HOST array of n_groups <= DCF_OPTIM_MAX_GROUPS records that travels by
+ *   value with the launch (a new learning rate needs no upload); bc1 = 1 - b1^t and sqrt_bc2 = sqrt(1 - b2^t) come from the host, in double.
+ * A null table, a negative count, more than DCF_OPTIM_MAX_GROUPS groups and an unknown mode fail with a message.
+ * ------------------------------------------------------------------------------------------ */
+#define DCF_OPTIM_CHUNK 4096
+#define DCF_OPTIM_MAX_GROUPS 8
+#define DCF_OPTIM_NO_GRAD 1
+#define DCF_OPTIM_ADAMW 0
+#define DCF_OPTIM_ADAM 1
+typedef struct dcf_optim_row {
+  void* p;
+  void* g;
+  void* exp_avg;
+  void* exp_avg_sq;
+  void* ema;
+  int64_t n;
+  int32_t group;
+  int32_t flags;
+  int64_t chunk0;
+} dcf_optim_row;
+typedef struct dcf_optim_group {
+  float lr;
+  float weight_decay;
+  float b1;
+  float b2;
+  float one_minus_b1;
+  float one_minus_b2;
+  float eps;
+  float bc1;
+  float sqrt_bc2;
+  int32_t mode;
+} dcf_optim_group;
+int dcf_optim_grad_norm(const dcf_optim_row* table, const int32_t* chunk_map, int32_t n_tensors, int64_t n_chunks, float max_norm,
+                        float* norm_out, float* coef_out, void* stream);
+int dcf_optim_scale(const dcf_optim_row* table, const int32_t* chunk_map, int32_t n_tensors, int64_t n_chunks, const float* scale,
+                    void* stream);
+int dcf_optim_adam_step(const dcf_optim_row* table, const int32_t* chunk_map, int32_t n_tensors, int64_t n_chunks,
+                        const dcf_optim_group* groups, int32_t n_groups, const float* coef, int32_t with_ema, float ema_beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
