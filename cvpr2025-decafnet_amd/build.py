@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libdecafnet_hip.so')
-SOURCES = ['engine.hip', 'dropout.hip', 'gemm.hip', 'gemm_bf16s.hip', 'ffn_chain.hip', 'head_chain.hip', 'dec_chain.hip', 'enc_chain.hip', 'rowops.hip', 'attn.hip', 'attn_grad.hip', 'score.hip', 'heads.hip', 'postproc.hip', 'loss.hip', 'objective.hip', 'conv_grad.hip', 'enc_grad.hip', 'xattn_grad.hip', 'refine_grad.hip', 'optim.hip', 'calib.hip']
+SOURCES = ['engine.hip', 'engine_model.hip', 'engine_blocks.hip', 'engine_hybrid.hip', 'ops_api.hip', 'dropout.hip', 'gemm.hip', 'gemm_bf16s.hip', 'ffn_chain.hip', 'head_chain.hip', 'dec_chain.hip', 'enc_chain.hip', 'rowops.hip', 'attn.hip', 'attn_grad.hip', 'score.hip', 'heads.hip', 'postproc.hip', 'loss.hip', 'objective.hip', 'conv_grad.hip', 'enc_grad.hip', 'xattn_grad.hip', 'refine_grad.hip', 'optim.hip', 'calib.hip']
 ARCH = 'gfx950'
 FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
 

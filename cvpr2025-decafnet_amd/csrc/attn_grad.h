@@ -16,8 +16,8 @@ struct LocalAttnGradArgs {
   int B, T, C, heads, window;                        // window odd, >= 1
 };
 
-// bytes of the row statistics the key-side gather reads (library-owned scratch, allocated and freed on the caller's stream)
-inline size_t local_attn_grad_stats_bytes(int64_t rows, int heads) { return (size_t)rows * heads * 4 * sizeof(float); }
+// floats of the row statistics the key-side gather reads (library-owned scratch, allocated and freed on the caller's stream)
+inline size_t local_attn_grad_stats_floats(int64_t rows, int heads) { return (size_t)rows * heads * 4; }
 
 int launch_local_attn_bwd(const LocalAttnGradArgs& a, hipStream_t st);
 

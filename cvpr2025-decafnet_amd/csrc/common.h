@@ -276,3 +276,38 @@ void set_error(const char* fmt, ...);
       return -1;                                                                   \
     }                                                                              \
   } while (0)
+
+// ---- stream-ordered scratch of one entry point ---------------------------------------------------
+// Owns what it allocates with hipMallocAsync on its stream: end(rc) frees everything in allocation order and passes rc on; what an
+// early return (DCF_HIP / DCF_CHECK in the middle of the entry point) would have leaked, the destructor frees.
+namespace dcf {
+class StreamScratch {
+ public:
+  explicit StreamScratch(hipStream_t st) : st_(st) {}
+  StreamScratch(const StreamScratch&) = delete;
+  StreamScratch& operator=(const StreamScratch&) = delete;
+  ~StreamScratch() { (void)end(-1); }
+  template <class T> int take(T** out, size_t count) {   // *out = `count` elements of T; left as it was on failure
+    DCF_CHECK(n_ < CAP, "internal: more than %d scratch allocations in one entry point", CAP);
+    void* p = nullptr;
+    const hipError_t e = hipMallocAsync(&p, count * sizeof(T), st_);
+    DCF_CHECK(e == hipSuccess, "hipMallocAsync of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
+    p_[n_++] = p;
+    *out = static_cast<T*>(p);
+    return 0;
+  }
+  int end(int rc) {                             // rc, or -1 with the error set where rc was 0 and a free failed
+    for (int i = 0; i < n_; ++i) {
+      const hipError_t e = hipFreeAsync(p_[i], st_);
+      if (e != hipSuccess && rc == 0) { set_error("hipFreeAsync failed: %s", hipGetErrorString(e)); rc = -1; }
+    }
+    n_ = 0;
+    return rc;
+  }
+ private:
+  static constexpr int CAP = 12;                // (dcf_op_head takes nine)
+  hipStream_t st_;
+  void* p_[CAP];
+  int n_ = 0;
+};
+}  // namespace dcf

@@ -696,13 +696,12 @@ int dcf_op_conv_bwd_weight(const float* X, const uint8_t* mask, const float* dY,
   }
   a.nslices = (rows + a.slice_rows - 1) / a.slice_rows;
   const int64_t count = (int64_t)N * k * Cin;
+  StreamScratch sc(st);
   float *part = nullptr, *dbpart = nullptr;
   uint8_t* flags = nullptr;
   unsigned* word = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&part, (size_t)a.nslices * count * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&dbpart, (size_t)a.nslices * N * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&flags, (size_t)rows, st));
-  DCF_HIP(hipMallocAsync((void**)&word, sizeof(unsigned), st));
+  if (sc.take(&part, (size_t)a.nslices * count) || sc.take(&dbpart, (size_t)a.nslices * N)) return -1;
+  if (sc.take(&flags, (size_t)rows) || sc.take(&word, 1)) return -1;
   hipLaunchKernelGGL(k_seqflags, dim3((rows + 255) / 256), dim3(256), 0, st, mask, flags, T, rows, 0);
   int rc = launch_absmax(dY, (int64_t)rows * N, word, st);
   a.flags = flags; a.absmax = word; a.part = part; a.dbpart = db ? dbpart : nullptr;
@@ -715,9 +714,8 @@ int dcf_op_conv_bwd_weight(const float* X, const uint8_t* mask, const float* dY,
                          accumulate, status);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv_bwd_weight: launch failed"); rc = -1; }
   }
-  DCF_HIP(hipFreeAsync(part, st)); DCF_HIP(hipFreeAsync(dbpart, st)); DCF_HIP(hipFreeAsync(flags, st)); DCF_HIP(hipFreeAsync(word, st));
-  if (rc == 0) rc = cg_end(st);
-  return rc;
+  rc = sc.end(rc);
+  return rc == 0 ? cg_end(st) : rc;
 }
 
 int dcf_op_conv_bwd_data(const float* dY, const uint8_t* mask, const float* W_ock, float* dX, int32_t B, int32_t T, int32_t Cin,
@@ -731,8 +729,9 @@ int dcf_op_conv_bwd_data(const float* dY, const uint8_t* mask, const float* W_oc
   const int rows = B * T;
   unsigned* status = nullptr;
   if (cg_begin("dcf_op_conv_bwd_data", st, &status)) return -1;
+  StreamScratch sc(st);
   uint8_t* flags = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&flags, (size_t)rows, st));
+  if (sc.take(&flags, (size_t)rows)) return -1;
   int rc = 0;
   if (N <= 2) {
     hipLaunchKernelGGL(k_seqflags, dim3((rows + 255) / 256), dim3(256), 0, st, mask, flags, T, rows, 0);
@@ -742,18 +741,15 @@ int dcf_op_conv_bwd_data(const float* dY, const uint8_t* mask, const float* W_oc
     else if (N == 1) hipLaunchKernelGGL((k_dgrad_small<1, 1>), grid, dim3(256), 0, st, dY, flags, W_ock, dX, (int64_t)rows, Cin);
     else hipLaunchKernelGGL((k_dgrad_small<1, 2>), grid, dim3(256), 0, st, dY, flags, W_ock, dX, (int64_t)rows, Cin);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv_bwd_data: launch failed"); rc = -1; }
-    DCF_HIP(hipFreeAsync(flags, st));
-    if (rc == 0) rc = cg_end(st);
-    return rc;
+    rc = sc.end(rc);
+    return rc == 0 ? cg_end(st) : rc;
   }
   const int K = k * N;
   float *dys = nullptr, *wp = nullptr;
   unsigned short* planes = nullptr;
   unsigned* word = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&dys, (size_t)rows * N * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&wp, (size_t)Cin * K * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&planes, (size_t)3 * Cin * K * sizeof(unsigned short), st));
-  DCF_HIP(hipMallocAsync((void**)&word, sizeof(unsigned), st));
+  if (sc.take(&dys, (size_t)rows * N) || sc.take(&wp, (size_t)Cin * K)) return -1;
+  if (sc.take(&planes, (size_t)3 * Cin * K) || sc.take(&word, 1)) return -1;
   // neighbour flags from the sequence ends alone: dY at a padded row is a legitimate operand
   hipLaunchKernelGGL(k_seqflags, dim3((rows + 255) / 256), dim3(256), 0, st, (const uint8_t*)nullptr, flags, T, rows, 1);
   rc = launch_absmax(dY, (int64_t)rows * N, word, st);
@@ -775,10 +771,8 @@ int dcf_op_conv_bwd_data(const float* dY, const uint8_t* mask, const float* W_oc
                        Cin / 4, status);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv_bwd_data: launch failed"); rc = -1; }
   }
-  DCF_HIP(hipFreeAsync(dys, st)); DCF_HIP(hipFreeAsync(wp, st)); DCF_HIP(hipFreeAsync(planes, st)); DCF_HIP(hipFreeAsync(word, st));
-  DCF_HIP(hipFreeAsync(flags, st));
-  if (rc == 0) rc = cg_end(st);
-  return rc;
+  rc = sc.end(rc);
+  return rc == 0 ? cg_end(st) : rc;
 }
 
 static int conv5s2_check(const char* what, int32_t B, int32_t T, int32_t Cin, int32_t N) {
@@ -797,14 +791,14 @@ int dcf_op_conv5s2_split(const float* X, const uint8_t* mask, const float* W_ock
   if (conv5s2_check("dcf_op_conv5s2_split", B, T, Cin, N)) return -1;
   DCF_CHECK(nterms == GEMM_F16X3 || nterms == GEMM_BF16X6, "dcf_op_conv5s2_split: nterms = %d (16 = f16x3, 6 = bf16x6)", nterms);
   const int rows_in = B * T, rows = rows_in / 2, K = 5 * Cin;
+  StreamScratch sc(st);
   float *col = nullptr, *wf = nullptr;
   uint8_t* ones = nullptr;
   unsigned short* planes = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&col, (size_t)rows * K * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&wf, (size_t)N * K * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&planes, (size_t)3 * N * K * sizeof(unsigned short), st));
+  if (sc.take(&col, (size_t)rows * K) || sc.take(&wf, (size_t)N * K)) return -1;
+  if (sc.take(&planes, (size_t)3 * N * K)) return -1;
   if (!mask) {
-    DCF_HIP(hipMallocAsync((void**)&ones, (size_t)rows_in, st));
+    if (sc.take(&ones, (size_t)rows_in)) return -1;
     DCF_HIP(hipMemsetAsync(ones, 1, (size_t)rows_in, st));
   }
   hipLaunchKernelGGL(k_permute_w5, dim3((N * K + 255) / 256), dim3(256), 0, st, W_ock, wf, N, Cin);
@@ -815,8 +809,7 @@ int dcf_op_conv5s2_split(const float* X, const uint8_t* mask, const float* W_ock
     g.A = col; g.lda = K; g.W = wf; g.ldw = 0; g.Ws = planes; g.C = Y; g.ldc = N; g.M = rows; g.N = N; g.K = K;
     rc = launch_gemm_split(&g, 1, A_ROWS, nterms, st);
   }
-  DCF_HIP(hipFreeAsync(col, st)); DCF_HIP(hipFreeAsync(wf, st)); DCF_HIP(hipFreeAsync(planes, st));
-  if (ones) DCF_HIP(hipFreeAsync(ones, st));
+  rc = sc.end(rc);
   return rc;
 }
 
@@ -834,12 +827,12 @@ int dcf_op_conv5s2_bwd_weight(const float* X, const uint8_t* mask, const float* 
   a.slice_rows = (per + WG_ROWS - 1) / WG_ROWS * WG_ROWS;
   a.nslices = (rows + a.slice_rows - 1) / a.slice_rows;
   const int64_t count = (int64_t)N * 5 * Cin;
+  StreamScratch sc(st);
   float* part = nullptr;
   uint8_t* flags = nullptr;
   unsigned* word = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&part, (size_t)a.nslices * count * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&flags, (size_t)rows, st));
-  DCF_HIP(hipMallocAsync((void**)&word, sizeof(unsigned), st));
+  if (sc.take(&part, (size_t)a.nslices * count) || sc.take(&flags, (size_t)rows)) return -1;
+  if (sc.take(&word, 1)) return -1;
   // per output row: does an output row to the left / right exist in its sequence (the input rows' mask is read by the kernel)
   hipLaunchKernelGGL(k_seqflags, dim3((rows + 255) / 256), dim3(256), 0, st, (const uint8_t*)nullptr, flags, To, rows, 1);
   int rc = launch_absmax(dY, (int64_t)rows * N, word, st);
@@ -851,9 +844,8 @@ int dcf_op_conv5s2_bwd_weight(const float* X, const uint8_t* mask, const float* 
                        1.f / WG_SX, dW_ock, 5, Cin, accumulate, status);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv5s2_bwd_weight: launch failed"); rc = -1; }
   }
-  DCF_HIP(hipFreeAsync(part, st)); DCF_HIP(hipFreeAsync(flags, st)); DCF_HIP(hipFreeAsync(word, st));
-  if (rc == 0) rc = cg_end(st);
-  return rc;
+  rc = sc.end(rc);
+  return rc == 0 ? cg_end(st) : rc;
 }
 
 int dcf_op_conv5s2_bwd_data(const float* dY, const uint8_t* mask, const float* W_ock, float* dX, int32_t B, int32_t T, int32_t Cin,
@@ -864,16 +856,15 @@ int dcf_op_conv5s2_bwd_data(const float* dY, const uint8_t* mask, const float* W
   const int To = T / 2, rows = B * To, K = 3 * N;
   unsigned* status = nullptr;
   if (cg_begin("dcf_op_conv5s2_bwd_data", st, &status)) return -1;
+  StreamScratch sc(st);
   uint8_t* flags = nullptr;
   float *dys = nullptr, *wp = nullptr;
   unsigned short* planes = nullptr;
   unsigned* word = nullptr;
   const size_t img = (size_t)Cin * K;
-  DCF_HIP(hipMallocAsync((void**)&flags, (size_t)rows, st));
-  DCF_HIP(hipMallocAsync((void**)&dys, (size_t)rows * N * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&wp, 2 * img * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&planes, 2 * 3 * img * sizeof(unsigned short), st));
-  DCF_HIP(hipMallocAsync((void**)&word, sizeof(unsigned), st));
+  if (sc.take(&flags, (size_t)rows) || sc.take(&dys, (size_t)rows * N)) return -1;
+  if (sc.take(&wp, 2 * img) || sc.take(&planes, 2 * 3 * img)) return -1;
+  if (sc.take(&word, 1)) return -1;
   // neighbour flags of the OUTPUT rows from the sequence ends alone: dY at a padded output row is a legitimate operand
   hipLaunchKernelGGL(k_seqflags, dim3((rows + 255) / 256), dim3(256), 0, st, (const uint8_t*)nullptr, flags, To, rows, 1);
   int rc = launch_absmax(dY, (int64_t)rows * N, word, st);
@@ -899,10 +890,8 @@ int dcf_op_conv5s2_bwd_data(const float* dY, const uint8_t* mask, const float* W
                        Cin / 4, status);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_conv5s2_bwd_data: launch failed"); rc = -1; }
   }
-  DCF_HIP(hipFreeAsync(dys, st)); DCF_HIP(hipFreeAsync(wp, st)); DCF_HIP(hipFreeAsync(planes, st)); DCF_HIP(hipFreeAsync(word, st));
-  DCF_HIP(hipFreeAsync(flags, st));
-  if (rc == 0) rc = cg_end(st);
-  return rc;
+  rc = sc.end(rc);
+  return rc == 0 ? cg_end(st) : rc;
 }
 
 int dcf_op_layernorm_bwd(const float* X, const float* w, const float* b, const float* dOut, float* dX, float* dw, float* db,
@@ -918,8 +907,9 @@ int dcf_op_layernorm_bwd(const float* X, const float* w, const float* b, const f
   a.X = X; a.w = w; a.b = b; a.dOut = dOut; a.dX = dX; a.rows = rows; a.C = C; a.relu = relu;
   a.rows_per_wave = (rows + 2047) / 2048;                      // <= 512 workgroups of four waves: a fixed function of `rows`
   const int nwg = (rows + 4 * a.rows_per_wave - 1) / (4 * a.rows_per_wave);
+  StreamScratch sc(st);
   float* part = nullptr;
-  if (dw || db) DCF_HIP(hipMallocAsync((void**)&part, (size_t)nwg * 2 * C * sizeof(float), st));
+  if ((dw || db) && sc.take(&part, (size_t)nwg * 2 * C)) return -1;
   a.part = part;
   int rc = launch_ln_bwd(a, nwg, st);
   if (rc == 0 && part) {
@@ -931,9 +921,8 @@ int dcf_op_layernorm_bwd(const float* X, const float* w, const float* b, const f
                          1, 1, accumulate, status);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_layernorm_bwd: launch failed"); rc = -1; }
   }
-  if (part) DCF_HIP(hipFreeAsync(part, st));
-  if (rc == 0) rc = cg_end(st);
-  return rc;
+  rc = sc.end(rc);
+  return rc == 0 ? cg_end(st) : rc;
 }
 
 }  // extern "C"

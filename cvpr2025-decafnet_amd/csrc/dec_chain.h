@@ -18,7 +18,7 @@ struct DecChainArgs {
   int64_t ldx;
   const uint8_t* mask;          // [B*T] row validity
   const float* ln_q_w; const float* ln_q_b;      // ln_xattn_q [256]
-  const float* dw;              // depthwise k3 weight [3][256] (engine.hip pack3)
+  const float* dw;              // depthwise k3 weight [3][256] (engine_model.hip pack3)
   const float* qn_w; const float* qn_b;          // xattn.q_norm [256]
   const unsigned short* Wq;     // chain image of xattn.xattn.query.weight (256 x 256), launch_split_chain1
   const float* bq;              // [256]

@@ -18,8 +18,8 @@ struct EncQkvArgs {
   int64_t ldx;
   const uint8_t* mask_in;       // [B*T_in]
   const float* ln_w; const float* ln_b;          // ln_attn [256]
-  const float* dw[3];           // depthwise k3 weights of q / k / v_conv, [3][256] each (engine.hip pack3)
-  // q / k / v_norm folded into the projections (engine.hip fold_ln): W' = W diag(g), s[n] = sum_k W'[n][k], c[n] = b[n] + sum_k beta[k] W[n][k]
+  const float* dw[3];           // depthwise k3 weights of q / k / v_conv, [3][256] each (engine_model.hip pack3)
+  // q / k / v_norm folded into the projections (engine_model.hip fold_ln): W' = W diag(g), s[n] = sum_k W'[n][k], c[n] = b[n] + sum_k beta[k] W[n][k]
   const unsigned short* W[3];   // chain images of the folded attn.attn.query / key / value.weight (256 x 256), launch_split_chain1
   const float* fs[3];           // [256] s
   const float* fc[3];           // [256] c

@@ -451,8 +451,9 @@ int dcf_op_dwconv3_bwd(const float* X, const uint8_t* mask, const float* W, cons
     a.rows_per_wave = (int)((rows_out + 4 * EG_MAX_WG - 1) / (4 * EG_MAX_WG));       // a fixed function of the row count
     const int nwg = (int)((rows_out + 4 * a.rows_per_wave - 1) / (4 * a.rows_per_wave));
     const int count = n * 3 * C;
+    StreamScratch sc(st);
     float* part = nullptr;
-    DCF_HIP(hipMallocAsync((void**)&part, (size_t)nwg * count * sizeof(float), st));
+    if (sc.take(&part, (size_t)nwg * count)) return -1;
     a.part = part;
     const dim3 grid(nwg, (C + 255) / 256);
     const size_t lds = (size_t)4 * n * 3 * 256 * sizeof(float);
@@ -461,7 +462,7 @@ int dcf_op_dwconv3_bwd(const float* X, const uint8_t* mask, const float* W, cons
     else hipLaunchKernelGGL(k_dw_bwd_w<3>, grid, dim3(256), lds, st, a);
     hipLaunchKernelGGL(k_eg_reduce, dim3((count + 255) / 256), dim3(256), 0, st, part, nwg, (int64_t)count, count, dW, 3, C, accumulate);
     EG_LAUNCHED("dcf_op_dwconv3_bwd");
-    DCF_HIP(hipFreeAsync(part, st));
+    rc = sc.end(rc);
   }
   return rc;
 }
@@ -474,20 +475,16 @@ static int pool_check(const char* what, int B, int T, int C) {
   return 0;
 }
 
-// xmin (B, C): the fill value of padded slots, on `st`; *out is freed by the caller (hipFreeAsync)
-static int pool_fill(const float* X, int B, int T, int C, float** out, hipStream_t st) {
+// xmin (B, C): the fill value of padded slots, on `st`; *out lives in the caller's scratch `sc`
+static int pool_fill(const float* X, int B, int T, int C, float** out, StreamScratch& sc, hipStream_t st) {
   int slice_rows = (T + EG_MIN_SLICES - 1) / EG_MIN_SLICES;
   slice_rows = slice_rows < 256 ? 256 : slice_rows;
   const int S = (T + slice_rows - 1) / slice_rows;
   float *part = nullptr, *xmin = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&part, (size_t)B * S * C * sizeof(float), st));
-  DCF_HIP(hipMallocAsync((void**)&xmin, (size_t)B * C * sizeof(float), st));
+  if (sc.take(&part, (size_t)B * S * C) || sc.take(&xmin, (size_t)B * C)) return -1;
   hipLaunchKernelGGL(k_colmin_part, dim3(B * S, (C + 255) / 256), dim3(256), 0, st, X, part, T, C, slice_rows, S);
   hipLaunchKernelGGL(k_colmin_final, dim3((B * C + 255) / 256), dim3(256), 0, st, (const float*)part, xmin, B, C, S);
-  const hipError_t e = hipGetLastError();
-  DCF_HIP(hipFreeAsync(part, st));
-  if (e != hipSuccess) {
-    (void)hipFreeAsync(xmin, st);
+  if (hipGetLastError() != hipSuccess) {
     set_error("masked max pooling: launch failed");
     return -1;
   }
@@ -500,14 +497,14 @@ int dcf_op_masked_maxpool(const float* X, const uint8_t* mask, float* Y, uint8_t
   DCF_CHECK(X && Y, "dcf_op_masked_maxpool: null argument");
   if (pool_check("dcf_op_masked_maxpool", B, T, C)) return -1;
   DCF_CHECK(aligned16(X) && aligned16(Y), "dcf_op_masked_maxpool: pointers must be 16-byte aligned");
+  StreamScratch sc(st);
   float* xmin = nullptr;                                 // without a mask no slot is padded: nothing to fill
-  if (mask && pool_fill(X, B, T, C, &xmin, st)) return -1;
+  if (mask && pool_fill(X, B, T, C, &xmin, sc, st)) return -1;
   int rc = 0;
   hipLaunchKernelGGL(k_pool_fwd, dim3(eg_grid((int64_t)B * (T / 2) * (C / 4), 256)), dim3(256), 0, st, X, mask, (const float*)xmin, Y, mask_out, B,
                      T, C);
   EG_LAUNCHED("dcf_op_masked_maxpool");
-  if (xmin) DCF_HIP(hipFreeAsync(xmin, st));
-  return rc;
+  return sc.end(rc);
 }
 
 int dcf_op_masked_maxpool_bwd(const float* X, const uint8_t* mask, const float* dY, float* dX, int32_t B, int32_t T, int32_t C,
@@ -516,14 +513,14 @@ int dcf_op_masked_maxpool_bwd(const float* X, const uint8_t* mask, const float* 
   DCF_CHECK(X && dY && dX, "dcf_op_masked_maxpool_bwd: null argument");
   if (pool_check("dcf_op_masked_maxpool_bwd", B, T, C)) return -1;
   DCF_CHECK(aligned16(X) && aligned16(dY) && aligned16(dX), "dcf_op_masked_maxpool_bwd: pointers must be 16-byte aligned");
+  StreamScratch sc(st);
   float* xmin = nullptr;
-  if (mask && pool_fill(X, B, T, C, &xmin, st)) return -1;
+  if (mask && pool_fill(X, B, T, C, &xmin, sc, st)) return -1;
   int rc = 0;
   hipLaunchKernelGGL(k_pool_bwd, dim3(eg_grid((int64_t)B * (T / 2) * (C / 4), 256)), dim3(256), 0, st, X, mask, (const float*)xmin, dY, dX, B, T,
                      C);
   EG_LAUNCHED("dcf_op_masked_maxpool_bwd");
-  if (xmin) DCF_HIP(hipFreeAsync(xmin, st));
-  return rc;
+  return sc.end(rc);
 }
 
 int dcf_op_gelu(const float* X, float* Y, int64_t n, void* stream) {
@@ -567,15 +564,15 @@ int dcf_op_layerscale_residual_bwd(const float* dY, const float* H, const uint8_
   a.dY = dY; a.H = H; a.mR = mR; a.mH = mH; a.ls = ls; a.dR = dR; a.dH = dH; a.rows = rows; a.C = C;
   a.rows_per_wave = (rows + 4 * EG_MAX_WG - 1) / (4 * EG_MAX_WG);                    // a fixed function of `rows`
   const int nwg = (rows + 4 * a.rows_per_wave - 1) / (4 * a.rows_per_wave);
+  StreamScratch sc(st);
   float* part = nullptr;
-  if (dls) DCF_HIP(hipMallocAsync((void**)&part, (size_t)nwg * C * sizeof(float), st));
+  if (dls && sc.take(&part, (size_t)nwg * C)) return -1;
   a.part = part;
   int rc = 0;
   hipLaunchKernelGGL(k_ls_bwd, dim3(nwg, (C + 255) / 256), dim3(256), 0, st, a);
   if (dls) hipLaunchKernelGGL(k_eg_reduce, dim3((C + 255) / 256), dim3(256), 0, st, (const float*)part, nwg, (int64_t)C, C, dls, 1, 1, accumulate);
   EG_LAUNCHED("dcf_op_layerscale_residual_bwd");
-  if (part) DCF_HIP(hipFreeAsync(part, st));
-  return rc;
+  return sc.end(rc);
 }
 
 }  // extern "C"

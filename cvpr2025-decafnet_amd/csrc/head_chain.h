@@ -31,7 +31,7 @@ bool head_chain_supports(int C, int NO);
 int launch_head_chain(const HeadChainArgs* a, int count, int C, hipStream_t stream);
 // halfs in the chain image of a (C, 3, C) k3 weight
 size_t head_chain_image_halfs(int C);
-// Wp: the packed fp32 weight [C out][3 taps][C in] (engine.hip pack3) -> img: fp16 hi / lo fragments in the order the kernel
+// Wp: the packed fp32 weight [C out][3 taps][C in] (engine_model.hip pack3) -> img: fp16 hi / lo fragments in the order the kernel
 // streams them; overflow (optional): bit 0 set if a weight leaves the scaled fp16 range
 int launch_split_chain3(const float* Wp, unsigned short* img, int C, hipStream_t stream, unsigned* overflow = nullptr);
 

@@ -85,8 +85,9 @@ static int run_loss(LossArgs a, float* sum_out, int32_t* count_out, hipStream_t 
     return 0;
   }
   const int blocks = (int)((a.n + LOSS_PER_BLOCK - 1) / LOSS_PER_BLOCK);
+  StreamScratch sc(st);
   char* scratch = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&scratch, (size_t)blocks * (sizeof(float) + sizeof(int)), st));
+  if (sc.take(&scratch, (size_t)blocks * (sizeof(float) + sizeof(int)))) return -1;
   a.part_sum = reinterpret_cast<float*>(scratch);
   a.part_cnt = reinterpret_cast<int*>(scratch + (size_t)blocks * sizeof(float));
   ProfScope prof(IOU ? "ctr_iou_loss" : "sigmoid_focal_loss", st, 0.0, (IOU ? 16.0 : 8.0) * (double)a.n);
@@ -96,9 +97,8 @@ static int run_loss(LossArgs a, float* sum_out, int32_t* count_out, hipStream_t 
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LOSS_NT), 0, st, (const float*)a.part_sum, (const int*)a.part_cnt, blocks, sum_out, (int*)count_out);
     e = hipGetLastError();
   }
-  DCF_HIP(hipFreeAsync(scratch, st));
   DCF_HIP(e);
-  return 0;
+  return sc.end(0);
 }
 
 // Gradient of the reduced loss with respect to `a`: elementwise, so no partials and no ordering question.  The upstream gradient

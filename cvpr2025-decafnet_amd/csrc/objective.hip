@@ -405,13 +405,12 @@ int dcf_point_objective(const float* logits1, const float* logits2, const float*
   a.eps = eps;
   a.kind = iou_kind;
   a.bpr = dcf::objective_blocks_per_row(a.rule.S);
+  dcf::StreamScratch sc(st);
   char* scratch = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&scratch, dcf::objective_scratch_bytes(nrows > 0 ? nrows : 1, a.rule.S), st));   // sized from (B', S) alone
+  if (sc.take(&scratch, dcf::objective_scratch_bytes(nrows > 0 ? nrows : 1, a.rule.S))) return -1;   // sized from (B', S) alone
   a.part = reinterpret_cast<float*>(scratch);
   float* rows = a.part + (size_t)(nrows > 0 ? nrows : 1) * a.bpr * 4;
-  const int rc = dcf::launch_objective(a, nrows, loss_norm_dev, world_size, loss_weight, rows, rows_out, out4, st);
-  DCF_HIP(hipFreeAsync(scratch, st));
-  return rc;
+  return sc.end(dcf::launch_objective(a, nrows, loss_norm_dev, world_size, loss_weight, rows, rows_out, out4, st));
 }
 
 int dcf_point_objective_grad(const float* logits1, const float* logits2, const float* offsets, const uint8_t* masks, const float* targets,
@@ -444,13 +443,12 @@ int dcf_point_objective_grad(const float* logits1, const float* logits2, const f
   a.bpr = dcf::objective_blocks_per_row(a.rule.S);
   dcf::ObjectiveGradArgs g{g_logits1, g_logits2, g_offsets, loss_norm_dev, grad_total_dev, grad_parts_dev, world_size, loss_weight, accumulate != 0};
   if (!rows_out && !out4) return dcf::launch_objective_grad(a, g, nrows, nullptr, nullptr, nullptr, st);
+  dcf::StreamScratch sc(st);
   char* scratch = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&scratch, dcf::objective_scratch_bytes(nrows > 0 ? nrows : 1, a.rule.S), st));
+  if (sc.take(&scratch, dcf::objective_scratch_bytes(nrows > 0 ? nrows : 1, a.rule.S))) return -1;
   a.part = reinterpret_cast<float*>(scratch);
   float* rows = a.part + (size_t)(nrows > 0 ? nrows : 1) * a.bpr * 4;
-  const int rc = dcf::launch_objective_grad(a, g, nrows, rows, rows_out, out4, st);
-  DCF_HIP(hipFreeAsync(scratch, st));
-  return rc;
+  return sc.end(dcf::launch_objective_grad(a, g, nrows, rows, rows_out, out4, st));
 }
 
 }  // extern "C"

@@ -146,8 +146,9 @@ int dcf_optim_grad_norm(const dcf_optim_row* table, const int32_t* chunk_map, in
   if (dcf::check_table("dcf_optim_grad_norm", table, chunk_map, n_tensors, n_chunks)) return -1;
   DCF_CHECK(norm_out || coef_out, "dcf_optim_grad_norm: no output");
   hipStream_t st = (hipStream_t)stream;
+  dcf::StreamScratch sc(st);
   double* partial = nullptr;
-  if (n_chunks > 0) DCF_HIP(hipMallocAsync((void**)&partial, (size_t)n_chunks * sizeof(double), st));
+  if (n_chunks > 0 && sc.take(&partial, (size_t)n_chunks)) return -1;
   hipError_t e = hipSuccess;
   {
     dcf::ProfScope prof("optim_grad_norm", st, 0.0, 4.0 * (double)n_chunks * DCF_OPTIM_CHUNK);
@@ -161,10 +162,8 @@ int dcf_optim_grad_norm(const dcf_optim_row* table, const int32_t* chunk_map, in
       e = hipGetLastError();
     }
   }
-  const hipError_t freed = partial ? hipFreeAsync(partial, st) : hipSuccess;
   DCF_HIP(e);                  // a launch error first: it is the cause, a failed release only follows from it
-  DCF_HIP(freed);
-  return 0;
+  return sc.end(0);
 }
 
 int dcf_optim_scale(const dcf_optim_row* table, const int32_t* chunk_map, int32_t n_tensors, int64_t n_chunks, const float* scale,

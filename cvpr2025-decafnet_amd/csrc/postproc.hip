@@ -643,13 +643,13 @@ int launch_nms(const NmsArgs& a, int nq, hipStream_t st) {
   }
   // more candidates than one workgroup's LDS holds: stream-ordered scratch, same kernel over global arrays
   const size_t per_q = (nms_big_scratch(a.n_max) + 255) & ~(size_t)255;
+  StreamScratch sc(st);
   unsigned char* scratch = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&scratch, per_q * nq, st));
+  if (sc.take(&scratch, per_q * nq)) return -1;
   hipLaunchKernelGGL(k_nms<true>, dim3(nq), dim3(NT), 0, st, a, scratch, per_q);
   const hipError_t e = hipGetLastError();
-  DCF_HIP(hipFreeAsync(scratch, st));
   DCF_HIP(e);
-  return 0;
+  return sc.end(0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -930,13 +930,13 @@ int launch_softnms(const SoftNmsArgs& a, int nq, hipStream_t st) {
     return 0;
   }
   const size_t per_q = (softnms_big_scratch(a.n_max) + 255) & ~(size_t)255;
+  StreamScratch sc(st);
   unsigned char* scratch = nullptr;
-  DCF_HIP(hipMallocAsync((void**)&scratch, per_q * nq, st));
+  if (sc.take(&scratch, per_q * nq)) return -1;
   hipLaunchKernelGGL((k_softnms<true, 1024>), dim3(nq), dim3(1024), 0, st, a, scratch, per_q);
   const hipError_t e = hipGetLastError();
-  DCF_HIP(hipFreeAsync(scratch, st));
   DCF_HIP(e);
-  return 0;
+  return sc.end(0);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -573,15 +573,9 @@ int dcf_op_refine_in_bwd(const float* logits1, const uint8_t* mask0, const float
   a.logits1 = logits1; a.mask0 = mask0; a.W = W_in; a.dH = dH;
   const int slices = (a.rows + RG_SLICE_ROWS - 1) / RG_SLICE_ROWS;                  // a fixed function of the row count
   const int per = RG_C * (L + 1);
-  if (dlogits1) DCF_HIP(hipMallocAsync((void**)&a.dU, (size_t)a.rows * L * sizeof(float), st));
-  if (dW_in || db_in) {
-    const hipError_t e = hipMallocAsync((void**)&a.part, (size_t)slices * per * sizeof(float), st);
-    if (e != hipSuccess) {
-      if (a.dU) (void)hipFreeAsync(a.dU, st);
-      set_error("dcf_op_refine_in_bwd: hipMallocAsync failed: %s", hipGetErrorString(e));
-      return -1;
-    }
-  }
+  StreamScratch sc(st);
+  if (dlogits1 && sc.take(&a.dU, (size_t)a.rows * L)) return -1;
+  if ((dW_in || db_in) && sc.take(&a.part, (size_t)slices * per)) return -1;
   int rc = 0;
   hipLaunchKernelGGL(k_refine_in_bwd, dim3(slices), dim3(256), 0, st, a);
   if (dlogits1) {
@@ -590,9 +584,7 @@ int dcf_op_refine_in_bwd(const float* logits1, const uint8_t* mask0, const float
   }
   if (a.part) hipLaunchKernelGGL(k_refine_in_reduce, dim3((per + 255) / 256), dim3(256), 0, st, (const float*)a.part, slices, L, dW_in, db_in, accumulate);
   if (hipGetLastError() != hipSuccess) { set_error("dcf_op_refine_in_bwd: launch failed"); rc = -1; }
-  if (a.dU) DCF_HIP(hipFreeAsync(a.dU, st));
-  if (a.part) DCF_HIP(hipFreeAsync(a.part, st));
-  return rc;
+  return sc.end(rc);
 }
 
 int dcf_op_tcn_layer(const float* X, const uint8_t* mask, const float* Wd, const float* bd, const float* Wp, const float* bp,
@@ -627,15 +619,9 @@ int dcf_op_tcn_layer_bwd(const float* X, const uint8_t* mask, const float* Wd, c
   a.dY = dY; a.dX = dX; a.want_wd = dWd != nullptr; a.want_wp = dWp != nullptr;
   if (p > 0.f ? rg_raise_lds<true>() : rg_raise_lds<false>()) return -1;
   const int slices = (a.rows + RG_SLICE_ROWS - 1) / RG_SLICE_ROWS;                  // a fixed function of the row count
-  if (dX) DCF_HIP(hipMallocAsync((void**)&a.dH, (size_t)a.rows * RG_C * sizeof(float), st));
-  if (want_part) {
-    const hipError_t e = hipMallocAsync((void**)&a.part, (size_t)slices * RG_P_N * sizeof(float), st);
-    if (e != hipSuccess) {
-      if (a.dH) (void)hipFreeAsync(a.dH, st);
-      set_error("dcf_op_tcn_layer_bwd: hipMallocAsync failed: %s", hipGetErrorString(e));
-      return -1;
-    }
-  }
+  StreamScratch sc(st);
+  if (dX && sc.take(&a.dH, (size_t)a.rows * RG_C)) return -1;
+  if (want_part && sc.take(&a.part, (size_t)slices * RG_P_N)) return -1;
   int rc = 0;
   const size_t lds = RG_LDS_BWD * sizeof(float);
   if (p > 0.f) hipLaunchKernelGGL(k_tcn_bwd1<true>, dim3(slices), dim3(256), lds, st, a);
@@ -646,9 +632,7 @@ int dcf_op_tcn_layer_bwd(const float* X, const uint8_t* mask, const float* Wd, c
     hipLaunchKernelGGL(k_rg_reduce, dim3((RG_P_N + 255) / 256), dim3(256), 0, st, (const float*)a.part, slices, o, accumulate);
   }
   if (hipGetLastError() != hipSuccess) { set_error("dcf_op_tcn_layer_bwd: launch failed"); rc = -1; }
-  if (a.dH) DCF_HIP(hipFreeAsync(a.dH, st));
-  if (a.part) DCF_HIP(hipFreeAsync(a.part, st));
-  return rc;
+  return sc.end(rc);
 }
 
 }  // extern "C"

@@ -343,16 +343,10 @@ int dcf_op_xattn_bwd(const float* Q, const float* K, const float* V, const uint8
   a.B = B; a.T = T; a.Lk = Lk; a.C = C; a.heads = heads;
   a.S = (T + XG_SLICE_ROWS - 1) / XG_SLICE_ROWS;                                     // a fixed function of T
   const int64_t per = (int64_t)Lk * C, total = (int64_t)B * per;
-  const size_t part_bytes = (size_t)total * a.S * sizeof(float);
-  if (dK) DCF_HIP(hipMallocAsync((void**)&a.partK, part_bytes, st));
-  if (dV) {
-    const hipError_t e = hipMallocAsync((void**)&a.partV, part_bytes, st);
-    if (e != hipSuccess) {
-      if (a.partK) (void)hipFreeAsync(a.partK, st);
-      set_error("dcf_op_xattn_bwd: hipMallocAsync failed: %s", hipGetErrorString(e));
-      return -1;
-    }
-  }
+  const size_t part_floats = (size_t)total * a.S;
+  StreamScratch sc(st);
+  if (dK && sc.take(&a.partK, part_floats)) return -1;
+  if (dV && sc.take(&a.partV, part_floats)) return -1;
   int rc = 0;
   switch (d) {
     case 16: rc = xg_launch<16>(a, st); break;
@@ -366,9 +360,7 @@ int dcf_op_xattn_bwd(const float* Q, const float* K, const float* V, const uint8
     if (dV) hipLaunchKernelGGL(k_xg_reduce, grid, dim3(256), 0, st, (const float*)a.partV, dV, a.S, per, total);
     if (hipGetLastError() != hipSuccess) { set_error("dcf_op_xattn_bwd: launch failed"); rc = -1; }
   }
-  if (a.partK) DCF_HIP(hipFreeAsync(a.partK, st));
-  if (a.partV) DCF_HIP(hipFreeAsync(a.partV, st));
-  return rc;
+  return sc.end(rc);
 }
 
 static int adaln_check(const char* what, int rows, int C) {

@@ -52,11 +52,23 @@ def device_disassembly(obj):
         return subprocess.run([OBJDUMP, '-d', parts[0]], check=True, capture_output=True, text=True).stdout
 
 
+# host-only translation units (dispatch and C entry points, no kernel): their objects carry no .hip_fatbin section.  Every other
+# object must have device code: one that lost it fails the gate instead of passing it unread.
+HOST_ONLY = {'engine_blocks.o', 'ops_api.o'}
+
+
+def has_device_code(obj):
+    fat = '.hip_fatbin' in subprocess.run([OBJDUMP, '-h', obj], check=True, capture_output=True, text=True).stdout
+    if fat == (os.path.basename(obj) in HOST_ONLY):
+        raise RuntimeError(f'{obj}: ' + ('listed as host-only but carries device code' if fat else 'no device code object'))
+    return fat
+
+
 def scan(objs=None):
     objs = objs or sorted(glob.glob(os.path.join(ROOT, 'cvpr2025-decafnet_amd', 'build', '*.o')))
     report = {}
     for o in objs:
-        txt = device_disassembly(o)
+        txt = device_disassembly(o) if has_device_code(o) else ''      # (a fat binary without a gfx950 part still raises)
         packed = len(re.findall(r'v_pk_[a-z]+_f32\b', txt))
         hits = [l.strip() for l in txt.split('\n') if 'op_sel:[' in l and is_bad(l)]
         # M0: the chain kernels' LDS-DMA requests write it and do not restore it (glds16), so nothing else may read or expect it
