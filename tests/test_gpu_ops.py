@@ -508,6 +508,10 @@ def test_xattn_core(L, B, T, Lk, C, heads):
                                             (3, 7, 256, 4, 9), (2, 1, 256, 4, 9), (2, 33, 64, 2, 19), (1, 150, 256, 4, 71),
                                             (2, 45, 1024, 16, 9)])
 def test_local_attn_core(L, B, T, C, heads, w):
+    _local_attn_vs_oracle(L, B, T, C, heads, w, torch.float32)
+
+
+def _local_attn_vs_oracle(L, B, T, C, heads, w, ref_dtype):
     pkg, lib = L
     g = torch.Generator().manual_seed(T * 3 + C)
     q, k, v = (torch.randn(B, T, C, generator=g) for _ in range(3))
@@ -517,13 +521,60 @@ def test_local_attn_core(L, B, T, C, heads, w):
     s = 1.0 / math.sqrt(math.sqrt(d))
 
     def split(z):
-        return z.view(B, T, heads, d).permute(0, 2, 1, 3).reshape(B * heads, T, d)
+        return z.to(ref_dtype).view(B, T, heads, d).permute(0, 2, 1, 3).reshape(B * heads, T, d)
 
     ref = R.banded_attention(split(q) * s, split(k) * s, split(v), mask, w)
     ref = ref.view(B, heads, T, d).permute(0, 2, 1, 3).reshape(B, T, C)
     O = torch.empty(B * T, C, device='cuda')
     pkg._lib.check(lib.dcf_op_local_attn(P(q.cuda()), P(k.cuda()), P(v.cuda()), P(mask.cuda()), P(O), B, T, C, heads, w, st()))
-    torch.testing.assert_close(O.cpu().view(B, T, C), ref, rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(O.cpu().view(B, T, C).to(ref_dtype), ref, rtol=1e-5, atol=1e-5)
+
+
+LA_EAGER_MAX_ROWS = 8192          # csrc/attn.hip local_attn_eager: launches of at most this many rows take the EAGER instantiation
+
+
+# window <= 9, one 256-channel chunk per row and MORE than 8192 rows: the two-row ring instantiation of k_local_attn with NCH == 1, the one
+# the large pyramid levels run in production (every case of test_local_attn_core with such a window has at most 8192 rows: EAGER).  The
+# last case has an odd T: the second row of a wave's pair is missing at each sequence end.
+@pytest.mark.parametrize('B,T,C,heads,w', [(1, 8300, 64, 2, 9), (120, 72, 128, 4, 5), (3, 2801, 256, 4, 9)])
+def test_local_attn_core_ring_instantiation(L, B, T, C, heads, w):
+    assert w <= 9 and C <= 256 and B * T > LA_EAGER_MAX_ROWS, 'this case would run the EAGER instantiation'
+    _local_attn_vs_oracle(L, B, T, C, heads, w, torch.float64)
+
+
+@pytest.mark.parametrize('C,heads', [(64, 2), (256, 4)])
+@pytest.mark.parametrize('w', [5, 9])
+def test_local_attn_eager_and_ring_give_the_same_bits(L, C, heads, w):
+    """csrc/attn.hip on the EAGER instantiation: "Same operations, same bits".  One sequence of 72 rows alone (B = 1: EAGER) and as element
+    0, a middle element and the last element of a batch of more than 8192 rows (the ring instantiation), the other elements holding
+    different data and masks of their own: the four results of that sequence are bit-identical."""
+    pkg, lib = L
+    T, B, at = 72, 120, (0, 60, 119)
+    assert T <= LA_EAGER_MAX_ROWS < B * T
+    g = torch.Generator().manual_seed(C + w)
+    q, k, v = (torch.randn(B, T, C, generator=g) for _ in range(3))
+    mask = torch.rand(B, T, generator=g) > 0.1
+    mask[:, 0] = True
+    for b in range(B):
+        mask[b, int(torch.randint(T // 2, T + 1, (1,), generator=g)):] = False
+    for b in at[1:]:
+        for z in (q, k, v, mask):
+            z[b] = z[at[0]]
+    assert not torch.equal(q[1], q[0]) and not torch.equal(mask[1], mask[0]) and bool(mask[0].any()) and not bool(mask[0].all())
+
+    def run(qs, ks, vs, ms):
+        n = qs.size(0)
+        O = torch.full((n * T, C), float('nan'), device='cuda')
+        pkg._lib.check(lib.dcf_op_local_attn(P(qs.contiguous().cuda()), P(ks.contiguous().cuda()), P(vs.contiguous().cuda()), P(ms.contiguous().cuda()),
+                                             P(O), n, T, C, heads, w, st()))
+        return O.cpu().view(n, T, C)
+
+    alone = run(q[:1], k[:1], v[:1], mask[:1])[0]
+    batch = run(q, k, v, mask)
+    assert bool(torch.isfinite(alone).all()) and bool(torch.isfinite(batch).all())
+    for b in at:
+        assert torch.equal(batch[b].view(torch.int32), alone.view(torch.int32)), \
+            f'element {b} of the batch (ring) differs from the sequence alone (EAGER) in {int((batch[b] != alone).sum())} values'
 
 
 @pytest.mark.parametrize('B,T,C,heads', [(2, 200, 128, 4), (1, 1000, 256, 4), (3, 64, 256, 4), (1, 37, 128, 4)])
