@@ -136,6 +136,18 @@ SIGNATURES = {
     'dcf_optim_adam_step': (i32, [vp, c_i32p, i32, i64, vp, i32, c_f32p, i32, f32, vp]),
 }
 
+# the training extension (include/decafnet_hip_train.h, dcf_train_ext_version): same shared object, a table of its own -- ABI 12 and
+# SIGNATURES above are frozen (tests/test_step_grad_drop_cpu.py checks this table against its header)
+_DROP = [i32, i32, i32, i32, i64, i32, f32]                 # B, T, C, b0, seed, site, p
+TRAIN_SIGNATURES = {
+    'dcf_train_ext_version': (i32, []),
+    'dcf_op_dropout': (i32, [c_f32p, c_f32p] + _DROP + [vp]),
+    'dcf_op_gelu_dropout': (i32, [c_f32p, c_f32p] + _DROP + [vp]),
+    'dcf_op_gelu_dropout_bwd': (i32, [c_f32p, c_f32p, c_f32p] + _DROP + [vp]),
+    'dcf_op_drop_residual': (i32, [c_f32p, c_u8p, c_f32p, c_u8p, c_f32p, c_f32p] + _DROP + [i32, f32, vp]),
+    'dcf_op_drop_residual_bwd': (i32, [c_f32p, c_f32p, c_u8p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p] + _DROP + [i32, f32, i32, vp]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
@@ -147,7 +159,7 @@ def lib():
             raise RuntimeError(f'{SO_PATH} is missing: build it with __graft_entry__.build() '
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

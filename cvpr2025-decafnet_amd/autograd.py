@@ -24,9 +24,17 @@ heads behind them train end to end with ``loss.PointObjective``.
 (csrc/conv_grad.hip).  ``video_transformer`` is VideoTransformer.forward (video_net.py:123-164: embd_fc, the embedding convolutions,
 the position encoding, the stem and the branch, ``pool_only`` included) and ``text_transformer`` TextTransformer.forward
 (text_net.py:158-188: embd_fc, the position encoding, the background token, the stride-0 blocks), both in their training branch.  With
-them every trainable parameter of the default model lies in a module that has a differentiable function here.  There is no dropout and no drop-path in any of these functions:
-they are the reference's blocks with every dropout probability at 0.  They demonstrate the operators, they are not the training
-forward: ``forward(..., eval=False)`` still returns plain tensors.
+them every trainable parameter of the default model lies in a module that has a differentiable function here.
+
+Dropout and drop-path.  ``layer_scale_residual``, ``ffn``, ``transformer_encoder`` (stride 1 / 2), ``transformer_decoder``,
+``xattn_fusion`` and ``video_transformer`` take ``drop``, a ``DropSpec``: the 64-bit key, the first sample's index ``b0`` in the
+reference's batch, ``proj_pdrop`` and ``path_pdrop``, and the site group / layer of the block (``DropSpec.at``; a stack numbers its
+layers itself).  The keep bits are those of the training forward (``model.enable_dropout``; csrc/dropout.h: Philox4x32-10 on
+(key, site, element)), so nothing is saved for the backward: it recomputes them (csrc/drop_grad.hip, include/decafnet_hip_train.h --
+``dropout``, ``gelu_dropout`` and the residual with both of its dropouts, dcf_op_dropout / dcf_op_gelu_dropout / dcf_op_drop_residual
+and their ``_bwd``).  ``drop=None``, or a spec whose two probabilities are 0, is the code path without dropout: the same operators, the
+same bits.  Attention-map dropout, channel dropout and dropout in the text encoder are not implemented.  ``forward(..., eval=False)``
+still returns plain tensors: the training forward with a graph is ``train.training_forward``.
 
 ``refine_in`` and ``tcn_layer`` are the forward / backward pairs of csrc/refine_grad.hip (dcf_op_refine_in, dcf_op_tcn_layer and their
 ``_bwd``): the stacking of the nearest-upsampled first-pass logits fused with refine.conv_1x1 (model.py:449-455) and one
@@ -44,6 +52,8 @@ Without a backward yet: the gate (it has no parameters: its inputs are features 
 functions and a training step), TextIdentity's attention pool (``text_transformer`` refuses a TextIdentity) and global self-attention
 over more than 64 positions.
 """
+from collections import namedtuple
+
 import torch
 
 from . import _lib
@@ -417,6 +427,127 @@ class _LayerScaleResidualFn(torch.autograd.Function):
         return gr, gh, gs.reshape(ctx.scale_shape) if gs is not None else None, None, None
 
 
+# site groups and subs of csrc/dropout.h (site = group << 16 | layer << 4 | sub)
+DROP_G_FUSION, DROP_G_STEM, DROP_G_BRANCH, DROP_G_REFINE = 1, 2, 3, 4
+DROP_PROJ, DROP_FFN_HID, DROP_FFN_OUT, DROP_PATH_ATTN, DROP_PATH_FFN, DROP_TCN = 0, 1, 2, 3, 4, 5
+
+
+class DropSpec(namedtuple('DropSpec', 'seed b0 proj_p path_p group layer', defaults=(0, 0.0, 0.0, 0, 0))):
+    """Dropout of one block: the 64-bit key ``seed`` (``model.last_dropout_seed``), ``b0`` the index of the first sequence in the
+    reference's batch, ``proj_p`` (proj_drop and the FFN's two dropouts) and ``path_p`` (drop-path), each in [0, 1), and the block's
+    site ``group`` (DROP_G_*) and ``layer``.  Immutable; ``at(group, layer)`` is the same spec at another block."""
+    __slots__ = ()
+
+    def __new__(cls, seed, b0=0, proj_p=0.0, path_p=0.0, group=0, layer=0):
+        proj_p, path_p = float(proj_p), float(path_p)
+        for name, p in (('proj_p', proj_p), ('path_p', path_p)):
+            if not 0.0 <= p < 1.0:
+                raise ValueError(f'DropSpec: {name} = {p} must lie in [0, 1)')
+        if int(b0) < 0 or not 0 <= int(group) < 1 << 15 or not 0 <= int(layer) < 1 << 12:
+            raise ValueError(f'DropSpec: b0 = {b0}, group = {group}, layer = {layer} out of range')
+        return super().__new__(cls, int(seed) & ((1 << 64) - 1), int(b0), proj_p, path_p, int(group), int(layer))
+
+    @property
+    def active(self):
+        return self.proj_p > 0.0 or self.path_p > 0.0
+
+    def at(self, group, layer):
+        return self._replace(group=int(group), layer=int(layer))
+
+    def site(self, sub):
+        return self.group << 16 | self.layer << 4 | sub
+
+    @property
+    def key(self):
+        """the key's 64 bits as the int64 the C ABI takes"""
+        return self.seed - (1 << 64) if self.seed >= 1 << 63 else self.seed
+
+
+def _active(drop, name):
+    """``drop`` if it drops anything, else None"""
+    if drop is None:
+        return None
+    if not isinstance(drop, DropSpec):
+        raise TypeError(f'{name}: drop must be an autograd.DropSpec or None, got {type(drop).__name__}')
+    return drop if drop.active else None
+
+
+class _DropoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, key, site, p, b0):
+        xd = _rows(x, 'dropout')
+        B, T, C = xd.shape
+        y = torch.empty_like(xd)
+        ctx.geom = (B, T, C, b0, key, site, p)
+        _lib.check(_lib.lib().dcf_op_dropout(_lib.ptr(xd), _lib.ptr(y), *ctx.geom, _lib.current_stream()), 'dcf_op_dropout')
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = gy.float().contiguous()
+        gx = torch.empty_like(gy)
+        _lib.check(_lib.lib().dcf_op_dropout(_lib.ptr(gy), _lib.ptr(gx), *ctx.geom, _lib.current_stream()), 'dcf_op_dropout')
+        return gx, None, None, None, None
+
+
+class _GeluDropoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, key, site, p, b0):
+        xd = _rows(x, 'gelu_dropout')
+        B, T, C = xd.shape
+        y = torch.empty_like(xd)
+        ctx.geom = (B, T, C, b0, key, site, p)
+        _lib.check(_lib.lib().dcf_op_gelu_dropout(_lib.ptr(xd), _lib.ptr(y), *ctx.geom, _lib.current_stream()), 'dcf_op_gelu_dropout')
+        ctx.save_for_backward(xd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        _lib.check(_lib.lib().dcf_op_gelu_dropout_bwd(_lib.ptr(x), _lib.ptr(gy.float().contiguous()), _lib.ptr(gx), *ctx.geom, _lib.current_stream()),
+                   'dcf_op_gelu_dropout_bwd')
+        return gx, None, None, None, None
+
+
+class _DropResidualFn(torch.autograd.Function):
+    """_LayerScaleResidualFn with the dropout of ``h`` and the drop-path of the branch"""
+
+    @staticmethod
+    def forward(ctx, r, h, scale, r_mask, h_mask, key, b0, drop_site, drop_p, path_site, path_p):
+        B, T, C = r.shape
+        rd, hd = _rows(r, 'layer_scale_residual'), _rows(h, 'layer_scale_residual')
+        if hd.shape != rd.shape or scale.numel() != C:
+            raise ValueError(f'layer_scale_residual: r {tuple(r.shape)}, h {tuple(h.shape)}, scale {tuple(scale.shape)} do not agree')
+        ls = scale.detach().float().reshape(C).contiguous()
+        mr, mh = _byte_mask(r_mask, B, T, 'layer_scale_residual'), _byte_mask(h_mask, B, T, 'layer_scale_residual')
+        if mr is not None and mh is not None:
+            if r_mask is not h_mask:
+                raise ValueError('layer_scale_residual: with dropout r_mask and h_mask, where both are given, are one tensor (a block has one mask)')
+            mh = mr
+        y = torch.empty_like(rd)
+        ctx.geom = (B, T, C, b0, key, drop_site, drop_p, path_site, path_p)
+        _lib.check(_lib.lib().dcf_op_drop_residual(_lib.ptr(rd), _lib.ptr(mr), _lib.ptr(hd), _lib.ptr(mh), _lib.ptr(ls), _lib.ptr(y), *ctx.geom,
+                                                   _lib.current_stream()), 'dcf_op_drop_residual')
+        ctx.save_for_backward(hd, ls, mr, mh)
+        ctx.scale_shape = scale.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        h, ls, mr, mh = ctx.saved_tensors
+        C = gy.size(2)
+        gy = gy.float().contiguous()
+        need_r, need_h, need_s = ctx.needs_input_grad[:3]
+        gr = torch.empty_like(gy) if need_r else None
+        gh = torch.empty_like(gy) if need_h else None
+        gs = torch.empty(C, dtype=torch.float32, device=gy.device) if need_s else None
+        if need_r or need_h or need_s:
+            _lib.check(_lib.lib().dcf_op_drop_residual_bwd(_lib.ptr(gy), _lib.ptr(h), _lib.ptr(mr), _lib.ptr(mh), _lib.ptr(ls), _lib.ptr(gr), _lib.ptr(gh),
+                                                           _lib.ptr(gs), *ctx.geom, 0, _lib.current_stream()), 'dcf_op_drop_residual_bwd')
+        return (gr, gh, gs.reshape(ctx.scale_shape) if gs is not None else None) + (None,) * 8
+
+
 def depthwise_conv1d(x, mask, weights, stride=1):
     """One to three depthwise MaskedConv1D (blocks.py:87-106 with groups = C: k = 3, padding 1, no bias, stride 1 or 2) sharing the
     token-major input ``x`` (B, T, C): ``conv_i(x * mask)``, not masked afterwards -> (tuple of (B, T / stride, C), ``mask[:, ::stride]``).
@@ -440,19 +571,44 @@ def gelu(x):
     return _GeluFn.apply(x)
 
 
-def layer_scale_residual(r, h, scale, r_mask=None, h_mask=None):
-    """A residual through LayerScale (blocks.py:670-682 with pdrop = 0): ``r * r_mask + scale * (h * h_mask)`` on token-major (B, T, C),
-    ``scale`` of C elements in any shape (the reference keeps (1, C, 1)); blocks.py:586 is ``r_mask = mask``, :589-590 ``h_mask = mask``."""
-    return _LayerScaleResidualFn.apply(r, h, scale, r_mask, h_mask)
+def dropout(x, drop, sub):
+    """nn.Dropout(drop.proj_p) at site ``sub`` of the block ``drop`` names, on token-major ``x`` (B, T, C) of the reference's (B, C, T)
+    tensor: kept values times 1 / (1 - p), dropped ones 0.  The backward is the same operator on the gradient."""
+    drop = _active(drop, 'dropout')
+    if drop is None or drop.proj_p == 0.0:
+        return x
+    return _DropoutFn.apply(x, drop.key, drop.site(sub), drop.proj_p, drop.b0)
 
 
-def ffn(x, ffn_module):
-    """FFN.forward (blocks.py:535-538, no dropout) on token-major ``x`` (B, T, C), with ``ffn_module`` a modeling.FFN:
+def gelu_dropout(x, drop, sub=DROP_FFN_HID):
+    """``dropout(gelu(x))`` of FFN.forward (blocks.py:535-536) in one pass, forward and backward, with the bits of the two operators in
+    a row; without an active ``drop`` it is ``gelu``."""
+    drop = _active(drop, 'gelu_dropout')
+    if drop is None or drop.proj_p == 0.0:
+        return gelu(x)
+    return _GeluDropoutFn.apply(x, drop.key, drop.site(sub), drop.proj_p, drop.b0)
+
+
+def layer_scale_residual(r, h, scale, r_mask=None, h_mask=None, drop=None, subs=(DROP_FFN_OUT, DROP_PATH_FFN)):
+    """A residual through LayerScale (blocks.py:670-682): ``r * r_mask + scale * (h * h_mask)`` on token-major (B, T, C),
+    ``scale`` of C elements in any shape (the reference keeps (1, C, 1)); blocks.py:586 is ``r_mask = mask``, :589-590 ``h_mask = mask``.
+    With ``drop``: ``r * r_mask + drop_path(scale * dropout(h * h_mask))``, the dropout of ``h`` at rate ``drop.proj_p`` and site
+    ``subs[0]``, the drop-path at rate ``drop.path_p`` and site ``subs[1]`` -- (DROP_PROJ, DROP_PATH_ATTN) for the attention branch,
+    (DROP_FFN_OUT, DROP_PATH_FFN), the FFN's last dropout, for the FFN branch."""
+    drop = _active(drop, 'layer_scale_residual')
+    if drop is None or h is None:
+        return _LayerScaleResidualFn.apply(r, h, scale, r_mask, h_mask)
+    return _DropResidualFn.apply(r, h, scale, r_mask, h_mask, drop.key, drop.b0, drop.site(subs[0]), drop.proj_p, drop.site(subs[1]), drop.path_p)
+
+
+def ffn(x, ffn_module, drop=None):
+    """FFN.forward (blocks.py:535-538) on token-major ``x`` (B, T, C), with ``ffn_module`` a modeling.FFN:
     proj(gelu(fc(x))), the two k = 1 convolutions unmasked (the reference's are plain nn.Conv1d).  Saved for the backward: ``x`` (by fc),
     the pre-activation fc(x) (by gelu, which recomputes Phi and phi from it) and gelu(fc(x)) (by proj, as the operand of its weight
-    gradient) -- two (B, T, 4 C) tensors per call."""
+    gradient) -- two (B, T, 4 C) tensors per call.  With ``drop`` the hidden tensor is ``gelu_dropout`` (site DROP_FFN_HID); the
+    dropout behind ``proj`` (:538, site DROP_FFN_OUT) is NOT applied here: it is part of the ``layer_scale_residual`` that follows."""
     h = masked_conv1d(x, None, ffn_module.fc.weight, ffn_module.fc.bias)
-    return masked_conv1d(gelu(h), None, ffn_module.proj.weight, ffn_module.proj.bias)
+    return masked_conv1d(gelu_dropout(h, drop), None, ffn_module.proj.weight, ffn_module.proj.bias)
 
 
 def conv_attn_layer(x, mask, layer):
@@ -473,16 +629,18 @@ def conv_attn_layer(x, mask, layer):
     return masked_mha(q, k, v, mask, layer.attn), mask
 
 
-def transformer_encoder(x, mask, block):
+def transformer_encoder(x, mask, block, drop=None, narrow_heads=False):
     """TransformerEncoder.forward (blocks.py:578-591) on token-major ``x`` (B, T, C), with ``block`` a modeling.TransformerEncoder of
     stride 1 or 2 and ``window_size > 0`` (a stem or pyramid block of the video encoder) -> (y (B, T / stride, C), ``mask[:, ::stride]``),
     or of stride 0 and ``window_size = 0`` (a block of the text encoder: no depthwise convolutions, q = k = v = ln_attn(x * mask) through
     the global branch of MaskedMHA, ``xattn_mha``; ``cross_attention``'s limits apply and are raised with its own message before
-    anything runs: at most 64 positions, head dimension 16 / 32 / 64 / 128) -> (y (B, T, C), mask).
+    anything runs: at most 64 positions, head dimension 16 / 32 / 64 / 128; ``narrow_heads=True``, which ``text_transformer`` passes,
+    also admits heads of 8 channels, which ``xattn_mha`` runs as zero-padded heads of 16) -> (y (B, T, C), mask).
     To the letter: the input is multiplied by the mask (:581); at stride 2 the skip is masked_max_pool1d of that (:584) but is masked
     with the convolution's mask ``mask[:, ::2]``, not with the pooled one (:586); the output is not masked, so padded rows hold
-    ``drop_path_attn.scale * attn.proj.bias``.  No attention / projection dropout and no
-    drop-path: the block with every dropout probability at 0."""
+    ``drop_path_attn.scale * attn.proj.bias``.  ``drop`` (stride 1 / 2 only; group DROP_G_STEM or DROP_G_BRANCH): proj_drop
+    (blocks.py:392, sub 0) and drop_path_attn (3) in the first residual, the FFN's dropouts (1, 2) and drop_path_ffn (4), on the
+    (B, C, T / stride) tensors of the reference.  No attention-map dropout."""
     if block.stride not in (0, 1, 2):
         raise ValueError(f'transformer_encoder: stride = {block.stride} (0: the text encoder, 1 or 2: the video encoder)')
     if (block.stride == 0) != (block.window_size == 0):
@@ -493,9 +651,12 @@ def transformer_encoder(x, mask, block):
         raise ValueError(f'transformer_encoder: T = {T} must be a multiple of the stride {block.stride}')
     if block.stride == 0:
         # the block is known to be unsupported before anything is launched: cross_attention's own message, with the block named
-        limit = _cross_attention_limit(T, C, block.attn.attn.n_heads)
+        limit = (_global_attention_limit if narrow_heads else _cross_attention_limit)(T, C, block.attn.attn.n_heads)
         if limit:
             raise ValueError(f'transformer_encoder: stride = 0 (global self-attention of the text encoder): {limit}')
+    drop = _active(drop, 'transformer_encoder')
+    if drop is not None and block.stride == 0:
+        raise ValueError('transformer_encoder: stride = 0 (the text encoder) takes no dropout')
     if mask is None:
         mask = torch.ones(B, T, dtype=torch.bool, device=x.device)
     x = _LayerScaleResidualFn.apply(x, None, None, mask, None)
@@ -506,9 +667,9 @@ def transformer_encoder(x, mask, block):
     else:
         skip = masked_max_pool1d(x, mask)[0] if block.stride == 2 else x
         h, mask = conv_attn_layer(channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias), mask, block.attn)
-    x = layer_scale_residual(skip, h, block.drop_path_attn.scale, r_mask=mask)
-    h = ffn(channel_layer_norm(x, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn)
-    return layer_scale_residual(x, h, block.drop_path_ffn.scale, h_mask=mask), mask
+    x = layer_scale_residual(skip, h, block.drop_path_attn.scale, r_mask=mask, drop=drop, subs=(DROP_PROJ, DROP_PATH_ATTN))
+    h = ffn(channel_layer_norm(x, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn, drop)
+    return layer_scale_residual(x, h, block.drop_path_ffn.scale, h_mask=mask, drop=drop), mask
 
 
 def _cross_attention_limit(Lk, C, n_heads):
@@ -518,6 +679,34 @@ def _cross_attention_limit(Lk, C, n_heads):
     if C % n_heads or C // n_heads not in (16, 32, 64, 128):
         return f'cross_attention: C = {C} on {n_heads} heads: the head dimension must be 16, 32, 64 or 128'
     return None
+
+
+_WIDE_HEAD = 16    # the narrowest head of cross_attention
+
+
+def _global_attention_limit(Lk, C, n_heads):
+    """``_cross_attention_limit`` for ``xattn_mha``, which also admits heads of 8 channels (run as heads of 16: ``_narrow_head_attention``)"""
+    if C % n_heads == 0 and C // n_heads == 8:
+        return _cross_attention_limit(Lk, n_heads * _WIDE_HEAD, n_heads)
+    return _cross_attention_limit(Lk, C, n_heads)
+
+
+def _narrow_head_attention(q, k, v, kv_mask, n_heads):
+    """``cross_attention`` for heads of d = 8 channels, narrower than the kernels' narrowest (16): every head is laid into the first d of
+    16 channels, the rest zero, which leaves q . k and the values untouched; the kernels scale q and k by 16^-1/4 each where the
+    reference has d^-1/4, so q and k are multiplied by (16 / d)^1/4 first.  The layout steps are torch's and differentiable; the
+    attention and its backward are the same HIP kernels.  The text encoder of a model with text_net heads of 8 channels is where
+    this occurs: at most 64 keys."""
+    B, T, C = q.shape
+    d = C // n_heads
+    gain = (_WIDE_HEAD / d) ** 0.25
+
+    def widen(z, g):
+        z = z.reshape(z.size(0), z.size(1), n_heads, d)
+        return torch.nn.functional.pad(z if g is None else z * g, (0, _WIDE_HEAD - d)).reshape(z.size(0), z.size(1), n_heads * _WIDE_HEAD)
+
+    o = cross_attention(widen(q, gain), widen(k, gain), widen(v, None), kv_mask, n_heads)
+    return o.reshape(B, T, n_heads, _WIDE_HEAD)[..., :d].reshape(B, T, C)
 
 
 class _CrossAttentionFn(torch.autograd.Function):
@@ -605,7 +794,8 @@ def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None):
     """MaskedMHA.forward in its global branch as the fusion calls it (blocks.py:327-356, :374-393; k = v = kv, no dropout) on token-major
     ``q_in`` (B, T, Cq) and ``kv_in`` (B', Lk, Ckv), with ``mha`` a modeling.MaskedMHA of ``window_size = 0``:
     proj(cross_attention(query(q_in), key(kv_in), value(kv_in))) -> (B', T, out_dim).  ``kv_size`` (B,): how many of the B' key
-    sequences belong to each query sequence; the PROJECTED query is repeated to match (:352-355)."""
+    sequences belong to each query sequence; the PROJECTED query is repeated to match (:352-355).  Heads of 8 channels, narrower than
+    ``cross_attention`` admits, run as zero-padded heads of 16 (``_narrow_head_attention``)."""
     if mha.window_size != 0:
         raise ValueError('xattn_mha: a MaskedMHA with window_size = 0 is required (the local branch is masked_mha)')
     q = masked_conv1d(q_in, None, mha.query.weight, mha.query.bias)
@@ -613,7 +803,8 @@ def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None):
     v = masked_conv1d(kv_in, None, mha.value.weight, mha.value.bias)
     if kv_size is not None and k.size(0) != q.size(0):
         q = _repeat(q, kv_size, k.size(0))
-    ctx = cross_attention(q, k, v, kv_mask, mha.n_heads)
+    narrow = q.size(2) % mha.n_heads == 0 and q.size(2) // mha.n_heads == 8
+    ctx = (_narrow_head_attention if narrow else cross_attention)(q, k, v, kv_mask, mha.n_heads)
     return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
 
 
@@ -630,13 +821,14 @@ def conv_xattn_layer(q, q_mask, kv, kv_mask, layer, kv_size=None):
     return out, q_mask
 
 
-def transformer_decoder(q, q_mask, kv, kv_mask, block, kv_size=None):
+def transformer_decoder(q, q_mask, kv, kv_mask, block, kv_size=None, drop=None):
     """TransformerDecoder.forward (blocks.py:632-650) on token-major ``q`` (B, T, E) and ``kv`` (B', Lk, TE), with ``block`` a
     modeling.TransformerDecoder -> (y (B', T, E), the query mask (B', T)).  To the letter: the input is multiplied by the mask (:635);
     the cross attention sees ln_xattn_q of that and ln_xattn_kv(kv); with ``kv_size`` the query residual is repeated to the B' text
     queries (:641-642); the residual is masked again, normalised without affine parameters ('adaln') or left as it is ('affine'), and
     modulated by the two halves of the cross-attention output (:643-645); the FFN branch is masked, the output is not, so padded rows
-    hold the shift.  No dropout and no drop-path."""
+    hold the shift.  ``drop`` (group DROP_G_FUSION): proj_drop on the (B', 2E, T) scale / shift tensor before the modulation (sub 0),
+    the FFN's dropouts (1, 2) and drop_path_ffn (4); the decoder has no drop_path_attn."""
     B, T, _ = q.shape
     q_mask = torch.ones(B, T, dtype=torch.bool, device=q.device) if q_mask is None else _mask_rows(q_mask, B, T)
     q = _LayerScaleResidualFn.apply(q, None, None, q_mask, None)
@@ -644,19 +836,24 @@ def transformer_decoder(q, q_mask, kv, kv_mask, block, kv_size=None):
                                channel_layer_norm(kv, block.ln_xattn_kv.weight, block.ln_xattn_kv.bias), kv_mask, block.xattn, kv_size)
     if kv_size is not None and q.size(0) != h.size(0):
         q = _repeat(q, kv_size, h.size(0))
-    q = adaln_modulate(q, mask, h, norm=block.xattn_mode == 'adaln')
-    h = ffn(channel_layer_norm(q, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn)
-    return layer_scale_residual(q, h, block.drop_path_ffn.scale, h_mask=mask), mask
+    drop = _active(drop, 'transformer_decoder')
+    q = adaln_modulate(q, mask, dropout(h, drop, DROP_PROJ), norm=block.xattn_mode == 'adaln')
+    h = ffn(channel_layer_norm(q, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn, drop)
+    return layer_scale_residual(q, h, block.drop_path_ffn.scale, h_mask=mask, drop=drop), mask
 
 
-def xattn_fusion(vid, vid_mask, text, text_mask, fusion, kv_size=None):
+def xattn_fusion(vid, vid_mask, text, text_mask, fusion, kv_size=None, drop=None):
     """XAttNFusion._forward (fusion.py:56-66) on token-major ``vid`` (B, T, E) and ``text`` (B', Lk, TE), with ``fusion`` a
     modeling.XAttNFusion: its decoder layers, ln_out, and the repeat by ``kv_size`` when no layer expanded the batch
-    -> (fused (B', T, E), mask (B', T))."""
+    -> (fused (B', T, E), mask (B', T)).  ``drop``: decoder layer i is layer i of group DROP_G_FUSION."""
     B, T, _ = vid.shape
     vid_mask = torch.ones(B, T, dtype=torch.bool, device=vid.device) if vid_mask is None else _mask_rows(vid_mask, B, T)
-    for layer in fusion.layers:
-        vid, vid_mask = transformer_decoder(vid, vid_mask, text, text_mask, layer, kv_size)
+    drop = _active(drop, 'xattn_fusion')
+    for i, layer in enumerate(fusion.layers):
+        if drop is None:
+            vid, vid_mask = transformer_decoder(vid, vid_mask, text, text_mask, layer, kv_size)
+        else:
+            vid, vid_mask = transformer_decoder(vid, vid_mask, text, text_mask, layer, kv_size, drop=drop.at(DROP_G_FUSION, i))
     vid = channel_layer_norm(vid, fusion.ln_out.weight, fusion.ln_out.bias)
     if kv_size is not None and vid.size(0) != text.size(0):
         vid, vid_mask = _repeat(vid, kv_size, text.size(0)), _repeat(vid_mask, kv_size, text.size(0))
@@ -849,12 +1046,13 @@ def _position_term(module, t, mask, name):
     return pe[None] * mask[..., None].to(torch.float32)
 
 
-def video_transformer(x, mask, vid_net):
+def video_transformer(x, mask, vid_net, drop=None):
     """VideoTransformer.forward (video_net.py:123-164, the training branch) on token-major ``x`` (B, T, in_dim), with ``vid_net`` a
     modeling.VideoTransformer -> (fpn, fpn_masks), tuples over the pyramid levels of (B, T_l, E) and (B, T_l) bool.  To the letter:
     the output of embd_fc is not masked (:133; the convolution behind it masks its input); each embedding convolution, k = 3 or
     k = 5 / stride 2, is followed by LayerNorm + ReLU; ``pe[:t] * mask`` is added under the mask of the shortened sequence; a
-    ``pool_only`` branch layer is one depthwise k = 3 convolution, stride 1 at the first level and 2 after it."""
+    ``pool_only`` branch layer is one depthwise k = 3 convolution, stride 1 at the first level and 2 after it.  ``drop``: stem layer i
+    is layer i of group DROP_G_STEM, the block of pyramid level l layer l of group DROP_G_BRANCH (a ``pool_only`` layer has none)."""
     B, T, _ = x.shape
     mask = torch.ones(B, T, dtype=torch.bool, device=x.device) if mask is None else _byte_mask(mask, B, T, 'video_transformer')
     x = masked_conv1d(x, mask, vid_net.embd_fc.conv.weight, vid_net.embd_fc.conv.bias)
@@ -867,14 +1065,15 @@ def video_transformer(x, mask, vid_net):
     pe = _position_term(vid_net, x.size(1), mask, 'video_transformer')
     if pe is not None:
         x = x + pe
-    for block in vid_net.stem:
-        x, mask = transformer_encoder(x, mask, block)
+    drop = _active(drop, 'video_transformer')
+    for i, block in enumerate(vid_net.stem):
+        x, mask = transformer_encoder(x, mask, block) if drop is None else transformer_encoder(x, mask, block, drop=drop.at(DROP_G_STEM, i))
     fpn, fpn_masks = [], []
-    for block in vid_net.branch:
+    for l, block in enumerate(vid_net.branch):
         if vid_net.pool_only:
             (x,), mask = depthwise_conv1d(x, mask, [block.conv.weight], block.stride)
         else:
-            x, mask = transformer_encoder(x, mask, block)
+            x, mask = transformer_encoder(x, mask, block) if drop is None else transformer_encoder(x, mask, block, drop=drop.at(DROP_G_BRANCH, l))
         fpn.append(x)
         fpn_masks.append(mask)
     return tuple(fpn), tuple(fpn_masks)
@@ -884,7 +1083,7 @@ def text_transformer(tokens, mask, text_net):
     """TextTransformer.forward (text_net.py:158-188, the training branch) on token-major ``tokens`` (B, L, in_dim), with ``text_net`` a
     modeling.TextTransformer -> ((B, L [+ 1], TE), mask (B, L [+ 1])).  To the letter: the background token is prepended to every
     sequence and the mask is extended by its own first column (:179-182); the gradient of ``bkgd_token`` is the sum over the batch.
-    The blocks are global self-attention: L [+ 1] <= 64."""
+    The blocks are global self-attention: L [+ 1] <= 64; heads of 16, 32, 64 or 128 channels, or of 8 (``xattn_mha``)."""
     if not hasattr(text_net, 'bkgd_token') or not hasattr(text_net, 'transformer') or hasattr(text_net, 'attn_pool'):
         raise ValueError(f'text_transformer: {type(text_net).__name__} is not differentiable yet (TextIdentity\'s attention pool has no '
                          f'backward); a modeling.TextTransformer is required')
@@ -898,5 +1097,5 @@ def text_transformer(tokens, mask, text_net):
         x = torch.cat((text_net.bkgd_token.t()[None].expand(B, -1, -1).to(x.dtype), x), dim=1)
         mask = torch.cat((mask[:, :1], mask), dim=1)
     for block in text_net.transformer:
-        x, _ = transformer_encoder(x, mask, block)
+        x, _ = transformer_encoder(x, mask, block, narrow_heads=True)
     return x, mask

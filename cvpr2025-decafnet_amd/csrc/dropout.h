@@ -58,6 +58,24 @@ struct DropSite {
   float p = 0.f, scale = 1.f;
 };
 
+// keep bits of the 4 x 4 block (positions t0 .. t0 + 3 of sequence bg, channels c0 .. c0 + 3): bit 4 i + cc = (t0 + i, c0 + cc)
+__device__ __forceinline__ unsigned block_keep(uint64_t seed, const DropSite& d, int64_t bg, int C, int T, int c0, int t0) {
+  if (d.p <= 0.f) return 0xffffu;
+  unsigned bits = 0;
+#pragma unroll
+  for (int cc = 0; cc < 4; ++cc) {
+    const uint64_t e0 = (uint64_t)((bg * C + c0 + cc) * (int64_t)T + t0);
+    if ((T & 3) == 0) {
+      const Philox4 v = drop_block(seed, d.site, e0 >> 2);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) bits |= (unsigned)drop_keep_word(philox_word(v, i), d.p) << (4 * i + cc);
+    } else {
+      for (int i = 0; i < 4 && t0 + i < T; ++i) bits |= (unsigned)drop_keep(seed, d.site, e0 + i, d.p) << (4 * i + cc);
+    }
+  }
+  return bits;
+}
+
 // dropout in place on rows [b][t] (T rows per sequence, C columns, pitch ld) of a (B', C, T) tensor of the reference; the
 // first row is sequence b0 of the reference's batch
 int launch_dropout(float* X, int64_t ld, int rows, int C, int T, int b0, uint64_t seed, const DropSite& d, hipStream_t st);

@@ -186,6 +186,10 @@ __global__ __launch_bounds__(256) void k_eg_reduce(const float* __restrict__ par
   out[o] = accumulate ? out[o] + sum : sum;
 }
 
+void launch_eg_reduce(const float* part, int nparts, int64_t stride, int count, float* out, int KT, int C, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(k_eg_reduce, dim3((count + 255) / 256), dim3(256), 0, st, part, nparts, stride, count, out, KT, C, accumulate);
+}
+
 // ------------------------------------------------------------------------------------------
 // masked max pooling (kernel 3, stride 2, padding 1)
 // ------------------------------------------------------------------------------------------
@@ -298,24 +302,6 @@ __global__ __launch_bounds__(256) void k_pool_bwd(const float* __restrict__ X, c
 // ------------------------------------------------------------------------------------------
 // GELU
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void gelu_terms(float x, float& Phi, float& xphi) {
-  const float p = 0.5f * erfcf(fabsf(x) * 0.70710678118654752440f);      // Phi(-|x|) in (0, 0.5]
-  Phi = x < 0.f ? p : 1.0f - p;
-  const float t = x * x, res = __builtin_fmaf(x, x, -t);                 // x^2 = t + res exactly
-  const float e = expf(-0.5f * t);
-  xphi = x * (0.39894228040143267794f * __builtin_fmaf(e, -0.5f * res, e));
-}
-__device__ __forceinline__ float gelu_exact(float x) {
-  float Phi, xphi;
-  gelu_terms(x, Phi, xphi);
-  return x * Phi;
-}
-__device__ __forceinline__ float gelu_slope(float x) {
-  float Phi, xphi;
-  gelu_terms(x, Phi, xphi);
-  return Phi + xphi;
-}
-
 __global__ __launch_bounds__(256) void k_gelu_fwd(const float* __restrict__ X, float* __restrict__ Y, int64_t n) {
   const int64_t n4 = n / 4;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {

@@ -5,6 +5,11 @@ differentiable pieces, so that ``backward()`` works on what ``loss.PointObjectiv
 ``TrainStep``: zero_grad, forward / objective / backward per micro-batch, the loss-norm update, the gradient norm and clip
 coefficient, the fused Adam / AdamW update with the EMA copy (``optim``), scheduler.step().  No host read anywhere in the step.
 
+Dropout: after ``model.enable_dropout()`` the forward applies opt's vid_net / fusion ``proj_pdrop`` and ``path_pdrop`` and the
+refinement TCN's rate on the counter-based stream of the library (csrc/dropout.h), one 64-bit key per forward, drawn on the CPU; the
+backward recomputes the keep bits from the key (``autograd.DropSpec``).  Not implemented, and refused as before: attention-map dropout
+(``attn_pdrop``), channel dropout (``cdrop``), dropout in the text encoder, ``second_fusion=True`` with dropout.
+
 Not here: the gradient all-reduce over ranks, data loading, logging, AMP, graph capture of the step, SGD.
 """
 import copy
@@ -14,21 +19,28 @@ import torch
 from . import _lib, autograd as A, loss as L, optim as O
 
 
-def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_masks, text_size=None, dropout=None):
+def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_masks, text_size=None, dropout=None, dropout_seed=None):
     """vid / shallow (bs, D, T) channel-major, vid_masks (bs, T) bool, tokens (B', C_t, Lq) channel-major, text_cls (B', D),
     token_masks (B', 1, Lq) or (B', Lq), text_size: queries per video (None: one each), B' = sum(text_size), all on the GPU.
     -> (fpn_logits1, fpn_logits2, fpn_offsets, fpn_masks) as ``model(..., eval=False)`` returns them, with an autograd graph to every
     parameter of the model.  Per video the sidekick scores and the block top-k gate (dcf_op_sidekick / dcf_op_gate, not
     differentiated: the gate is a 0 / 1 weight), the product and the concatenation with the shallow features, vid_map, the text
     encoder, the first fusion, the video encoder, then the heads with the refinement stage (``autograd.fuse_and_predict``).
-    ``dropout``: the (seed, p, b0) of ``autograd.fuse_and_predict`` for the refinement stage's dropout, None for none."""
+    ``dropout``: the (seed, p, b0) of ``autograd.fuse_and_predict`` for the refinement stage's dropout alone, None for none; only
+    for a model without ``enable_dropout()``.  With ``model.enable_dropout()`` the forward applies all five rates of
+    ``model._dropout_rates()`` with b0 = 0 under one 64-bit key: ``dropout_seed`` if given, else ``model._next_dropout_seed()``
+    (the CPU generator ``enable_dropout`` set up); the key is left in ``model.last_dropout_seed``."""
     from . import modeling
     if type(model) is not modeling.PtTransformerEarlyFusionIterative:
         raise NotImplementedError(f'training_forward: {type(model).__name__} is not implemented (PtTransformerEarlyFusionIterative only)')
     if model.scat or model.sfonly:
         raise NotImplementedError('training_forward: opt.model.scat / sfonly are not implemented')
-    if model._dropout_rates() is not None:                          # ... and it refuses opt's own non-zero probabilities, as the forward does
-        raise NotImplementedError('training_forward: enable_dropout() covers the forward values only; pass `dropout` for the refinement stage')
+    rates = model._dropout_rates()                                  # None without enable_dropout(); refuses what the forward refuses
+    if rates is None and dropout_seed is not None:
+        raise ValueError('training_forward: dropout_seed without model.enable_dropout()')
+    if rates is not None and dropout is not None:
+        raise ValueError('training_forward: `dropout` is the refinement stage alone on a model without enable_dropout(); this model\'s '
+                         'dropout is enabled and covers it')
     if not vid.is_cuda:
         raise RuntimeError('the training forward runs on the MI355X only: move the inputs to the GPU')
     lib, st = _lib.lib(), _lib.current_stream()
@@ -56,8 +68,15 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
         x = torch.cat([x, rep(shallow)], dim=2)
     vid_map = A.masked_conv1d(x, mask, model.vid_map.conv.weight, model.vid_map.conv.bias)
     text, text_mask = A.text_transformer(tokens.transpose(1, 2).contiguous(), token_masks.reshape(nq, -1), model.text_net)
-    fused, fmask = A.xattn_fusion(vid_map, mask, text, text_mask, model.fusion, kv_size)
-    fpn, fpn_masks = A.video_transformer(fused, fmask, model.vid_net)
+    vid_drop = fus_drop = None
+    if rates is not None:
+        seed = (model._next_dropout_seed() if dropout_seed is None else int(dropout_seed)) & ((1 << 64) - 1)
+        model.last_dropout_seed = seed
+        vid_drop, fus_drop = A.DropSpec(seed, 0, rates[0], rates[1]), A.DropSpec(seed, 0, rates[2], rates[3])
+        if rates[4] > 0.0:
+            dropout = (seed, rates[4], 0)
+    fused, fmask = A.xattn_fusion(vid_map, mask, text, text_mask, model.fusion, kv_size, **({} if fus_drop is None else {'drop': fus_drop}))
+    fpn, fpn_masks = A.video_transformer(fused, fmask, model.vid_net, **({} if vid_drop is None else {'drop': vid_drop}))
     extra = dict(text=text, text_mask=text_mask, kv_size=kv_size) if model.second_fusion else {}
     if dropout is not None:
         extra['dropout'] = dropout
@@ -115,12 +134,22 @@ class TrainStep:
 
     def state(self):
         """-> (model_ckpt, state_ckpt) with the keys of Trainer.checkpoint (worker_v2.py:680-689).  'loss_norm' is an addition
-        (the reference does not save its running normaliser) and costs a host read, like the checkpoint itself."""
+        (the reference does not save its running normaliser) and costs a host read, like the checkpoint itself.  'dropout_rng' is
+        another, present only when ``model.enable_dropout`` was given an int seed: the state of the private generator that hands out
+        the dropout keys, so that a resumed run draws the keys the uninterrupted one would."""
         snap = copy.deepcopy                                               # a snapshot: state_dict() hands out the live tensors
-        return ({'model': snap(self.model.state_dict()), 'model_ema': snap(self.ema.state_dict())},
-                {'optimizer': snap(self.optimizer.state_dict()),
+        state = {'optimizer': snap(self.optimizer.state_dict()),
                  'scheduler': None if self.scheduler is None else snap(self.scheduler.state_dict()),
-                 'epoch': self.epoch, 'itr': self.itr, 'loss_norm': self.objective.loss_norm})
+                 'epoch': self.epoch, 'itr': self.itr, 'loss_norm': self.objective.loss_norm}
+        gen = self._dropout_generator()
+        if gen is not None:
+            state['dropout_rng'] = gen.get_state().clone()
+        return {'model': snap(self.model.state_dict()), 'model_ema': snap(self.ema.state_dict())}, state
+
+    def _dropout_generator(self):
+        """the private CPU generator of ``model.enable_dropout(seed=<int>)``, or None"""
+        d = getattr(self.model, '_dropout', None)
+        return None if d is None else d[1]
 
     def load_state(self, model_ckpt, state_ckpt):
         self.model.load_state_dict(model_ckpt['model'])
@@ -131,4 +160,9 @@ class TrainStep:
         self.epoch, self.itr = state_ckpt['epoch'], state_ckpt['itr']
         if 'loss_norm' in state_ckpt:
             self.objective.loss_norm = state_ckpt['loss_norm']
+        if 'dropout_rng' in state_ckpt:
+            gen = self._dropout_generator()
+            if gen is None:
+                raise ValueError('load_state: the checkpoint carries a dropout generator state; call model.enable_dropout(seed=<int>) first')
+            gen.set_state(state_ckpt['dropout_rng'])
         return self
