@@ -9,9 +9,9 @@ Sub-modules: ``modeling`` (libs/modeling drop-in), ``nms`` (libs/nms drop-in), `
 ``eval.py`` / ``Evaluator`` on this package without editing it), ``loss`` (libs/modeling/loss.py forward values), ``autograd`` (differentiable MaskedConv1D / channel LayerNorm / window attention /
 cross attention / AdaLN modulation / depthwise convolution / max pooling / GELU / LayerScale residual, and heads, whole TransformerEncoder blocks, whole
 TransformerDecoder layers and the XAttNFusion stack composed of them: ``cross_attention``, ``adaln_modulate``, ``xattn_mha``, ``conv_xattn_layer``, ``transformer_decoder``, ``xattn_fusion``; the refinement stage ``refine_in``, ``tcn_layer``, ``tcn`` and ``fuse_and_predict``; the two backbones
-``video_transformer`` (with the k = 5 / stride-2 ``strided_masked_conv1d``) and ``text_transformer``), ``dist`` (T-sharding over ranks), ``build`` (hipcc driver),
+``video_transformer`` (with the k = 5 / stride-2 ``strided_masked_conv1d``) and ``text_transformer``), ``dist`` (T-sharding over ranks; the bucketed gradient all-reduce of data-parallel training), ``build`` (hipcc driver),
 ``_lib`` (ctypes binding of the C ABI), ``optim`` (the Trainer's update: gradient clipping, Adam / AdamW and the EMA copy as multi-tensor kernels,
-the reference's parameter groups and schedulers), ``train`` (the differentiable training forward and ``TrainStep``, one whole iteration).
+the reference's parameter groups and schedulers), ``train`` (the differentiable training forward and ``TrainStep``, one whole iteration; ``DataParallelTrainStep``, the same on every rank of a process group).
 """
 from . import config, synth  # noqa: F401
 

@@ -149,6 +149,14 @@ TRAIN_SIGNATURES = {
 }
 
 
+# the data-parallel extension (include/decafnet_hip_dist.h, dcf_dist_ext_version): same shared object, a third table -- the two above
+# are frozen (tests/test_grad_bucket_cpu.py checks this table against its header)
+DIST_SIGNATURES = {
+    'dcf_dist_ext_version': (i32, []),
+    'dcf_dist_pack_grads': (i32, [vp, c_i32p, i32, i64, f32, vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -159,7 +167,7 @@ def lib():
             raise RuntimeError(f'{SO_PATH} is missing: build it with __graft_entry__.build() '
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -26,11 +26,16 @@ Two granularities:
 
 The compute is injected through a small backend object so the same orchestration runs on the
 HIP model (``HipBackend``) and, in the CPU tests, on any callable with the same contract.
+
+4. **Data-parallel training** -- ``grad_bucket_plan`` / ``GradReducer`` / ``broadcast_module``: the gradients of a training step
+   packed into buckets of one flat arena by a HIP kernel (dcf_dist_pack_grads) and all-reduced while the backward still runs;
+   ``train.DataParallelTrainStep`` is the step built on them.
 """
 from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 
@@ -498,3 +503,224 @@ def hybrid_forward(backend, vid_w, shallow_w, mask_full, plan, rank, T, n_levels
     of = [tuple(x[q][None] for x in out_o) for q in range(nq)]
     mk = [tuple(x[q][None] for x in out_m) for q in range(nq)]
     return lg, of, mk
+
+
+# ---------------------------------------------------------------------------------------------
+# data-parallel training: bucketed gradient all-reduce (what DistributedDataParallel does for the reference's Trainer,
+# worker_v2.py:278-280)
+# ---------------------------------------------------------------------------------------------
+# DistributedDataParallel's bucket_cap_mb = 25: taken over as it stands, not measured here (profiles/grad_allreduce.md)
+DEFAULT_BUCKET_BYTES = 25 * 1024 * 1024
+
+
+def grad_bucket_plan(sizes: Sequence[int], bucket_bytes: int, align: int = 64) -> dict:
+    """Where every gradient lies in ONE flat fp32 arena, and which bucket it is reduced with.  ``sizes``: the element counts of
+    ``model.parameters()`` in that order.  The tensors are taken in REVERSE order (about the order in which a backward produces their
+    gradients) and fill buckets greedily up to ``bucket_bytes`` (padding counted); a tensor larger than that gets a bucket of its
+    own.  Every slice and every bucket starts at a multiple of ``align`` floats.
+    -> {'buckets': [{'start', 'end', 'params': [index], 'offsets': [first float of the slice in the arena]}], 'length': floats,
+    'align'}; a bucket is the arena's [start, end).  Pure arithmetic on the sizes: equal inputs give equal plans on every rank."""
+    sizes = [int(n) for n in sizes]
+    if min(sizes, default=0) < 0 or int(bucket_bytes) <= 0 or int(align) <= 0:
+        raise ValueError(f'grad_bucket_plan: sizes >= 0, bucket_bytes > 0 and align > 0 are expected (bucket_bytes {bucket_bytes}, align {align})')
+    align, cap = int(align), int(bucket_bytes) // 4
+    buckets, cur, end = [], None, 0
+    for i in reversed(range(len(sizes))):
+        padded = -(-sizes[i] // align) * align
+        if cur is not None and end - cur['start'] + padded > cap:
+            cur['end'] = end
+            cur = None
+        if cur is None:
+            cur = {'start': end, 'end': end, 'params': [], 'offsets': []}
+            buckets.append(cur)
+        cur['params'].append(i)
+        cur['offsets'].append(end)
+        end += padded
+    if cur is not None:
+        cur['end'] = end
+    return {'buckets': buckets, 'length': end, 'align': align}
+
+
+class _BucketSchedule:
+    """In which order the buckets of a plan are launched.  ``ready(i)`` reports the gradient of parameter i and returns the buckets to
+    launch now: bucket k goes out only when every parameter of it was reported AND buckets 0 .. k-1 went out, so that every rank issues
+    its collectives in the same order whatever order its backward ran in.  ``finish()`` returns the buckets not launched yet, in
+    index order (parameters that received no gradient); ``reset()`` re-arms."""
+
+    def __init__(self, plan):
+        self._bucket_of = {i: k for k, b in enumerate(plan['buckets']) for i in b['params']}
+        self._sizes = [len(b['params']) for b in plan['buckets']]
+        self.reset()
+
+    def reset(self):
+        self._pending, self._seen, self._next = list(self._sizes), set(), 0
+
+    def ready(self, param_index):
+        if param_index in self._seen:
+            return []
+        self._seen.add(param_index)
+        k = self._bucket_of[param_index]
+        if k < self._next:                     # after finish(): the bucket went out already
+            return []
+        self._pending[k] -= 1
+        out = []
+        while self._next < len(self._pending) and self._pending[self._next] == 0:
+            out.append(self._next)
+            self._next += 1
+        return out
+
+    def finish(self):
+        out = list(range(self._next, len(self._pending)))
+        self._next = len(self._pending)
+        return out
+
+
+def _group_info(group):
+    """(world size, backend) of a process group; (1, None) for None -- no group means one rank, whatever torch.distributed holds"""
+    if group is None:
+        return 1, None
+    import torch.distributed as dist
+    return dist.get_world_size(group), dist.get_backend(group)
+
+
+def _all_reduce_sum(t, group, backend, async_op=False):
+    """SUM over the ranks into ``t`` (a device tensor).  nccl (RCCL): on the device, ordered after the current stream; with async_op the
+    work handle is returned and ``wait()`` orders the then-current stream after the collective (no host wait).  gloo: staged through the
+    host and synchronous, like ``_gather_static`` -- the flow check of a one-GPU box, not a way to train."""
+    import torch.distributed as dist
+    if backend == 'gloo' and t.is_cuda:
+        h = t.cpu()
+        dist.all_reduce(h.view(-1), op=dist.ReduceOp.SUM, group=group)
+        t.copy_(h)
+        return None
+    return dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=async_op)
+
+
+class GradReducer:
+    """The gradient all-reduce of a data-parallel step, overlapped with the backward that produces the gradients.
+
+    Owns ONE flat fp32 arena on the parameters' device (``grad_bucket_plan``; allocated once, the padding zeroed once) and one device
+    table per bucket whose destinations, the slices, never change.  Between ``arm()`` and ``disarm()`` a post-accumulate-grad hook on
+    every parameter reports its gradient to the schedule; for every bucket the schedule hands out, the hook -- on autograd's device
+    thread, on the stream current there -- launches dcf_dist_pack_grads (slice = p.grad * (1 / world): the objective multiplied the
+    loss by the world size, DistributedDataParallel pre-divides the same way) and issues the bucket's all-reduce without waiting.
+    ``finalize()`` launches what is left (a parameter without a gradient on this rank is packed as zeros), orders the current stream
+    after the reduces and points every ``p.grad`` at its slice: from there ``optim.grad_norm_and_coef`` and ``AdamW.step`` run
+    unchanged, on addresses that no longer move from step to step.
+
+    Hence, unlike a single-rank step: after a data-parallel step EVERY parameter has a gradient, zero if nothing reached it, so it takes
+    weight decay and its Adam step count advances -- a rank cannot know without communication whether another rank had one
+    (DistributedDataParallel's buckets behave the same).
+
+    ``process_group``: a torch.distributed group, or None for one rank (pack only).  Parameters are fp32, contiguous, on one GPU;
+    those with requires_grad=False are left out."""
+
+    def __init__(self, params, process_group=None, bucket_bytes=DEFAULT_BUCKET_BYTES):
+        from . import _lib, optim
+        self._lib, self._optim = _lib, optim
+        self.params = [p for p in params if p.requires_grad]
+        if not self.params:
+            raise ValueError('GradReducer: no parameter requires a gradient')
+        self.device = self.params[0].device
+        for i, p in enumerate(self.params):
+            optim._check_tensor(p, f'parameter {i}')
+            optim._need_gpu(p, f'parameter {i}')
+            if p.device != self.device:
+                raise ValueError(f'parameter {i} is on {p.device}, the first on {self.device}: one device per reducer')
+        self.group = process_group
+        self.world, self.backend = _group_info(process_group)
+        self.plan = grad_bucket_plan([p.numel() for p in self.params], bucket_bytes)
+        self.arena = torch.zeros(max(self.plan['length'], 1), dtype=torch.float32, device=self.device)
+        self.offsets = [None] * len(self.params)
+        for b in self.plan['buckets']:
+            for i, off in zip(b['params'], b['offsets']):
+                self.offsets[i] = off
+        self.views = [self.arena[off:off + p.numel()].view(p.shape) for p, off in zip(self.params, self.offsets)]
+        self._tables = [optim._Table() for _ in self.plan['buckets']]
+        self._schedule = _BucketSchedule(self.plan)
+        self._handles, self._hooks = [], []
+        self.launched = []                               # the buckets of the current step in launch order (for tests and logs)
+
+    def arm(self):
+        """hooks on, schedule reset: the next backward reduces"""
+        self.disarm()
+        self._schedule.reset()
+        self._handles, self.launched = [], []
+        for i, p in enumerate(self.params):
+            self._hooks.append(p.register_post_accumulate_grad_hook(lambda _p, i=i: self._on_grad(i)))
+        return self
+
+    def disarm(self):
+        for h in self._hooks:
+            h.remove()
+        self._hooks = []
+        return self
+
+    def _on_grad(self, i):
+        for k in self._schedule.ready(i):
+            self._launch(k)
+
+    def _launch(self, k):
+        b = self.plan['buckets'][k]
+        rec = np.zeros(len(b['params']), dtype=self._optim._ROW)
+        base = self.arena.data_ptr()
+        for j, (i, off) in enumerate(zip(b['params'], b['offsets'])):
+            p, g = self.params[i], self.params[i].grad
+            rec['p'][j], rec['n'][j] = base + 4 * off, p.numel()
+            if g is None:
+                rec['flags'][j] = self._lib.OPTIM_NO_GRAD
+                continue
+            if g.dtype is not torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous():
+                self._optim._check_tensor(g, f'the gradient of parameter {i}')
+                raise ValueError(f'the gradient of parameter {i}: {tuple(g.shape)} on {g.device}, expected {tuple(p.shape)} on {self.device}')
+            rec['g'][j] = g.data_ptr()
+        with torch.cuda.device(self.device):
+            table = self._tables[k].update(rec, self.device)
+            self._lib.check(self._lib.lib().dcf_dist_pack_grads(*table.args(), 1.0 / self.world, self._lib.current_stream()),
+                            'dcf_dist_pack_grads')
+            self.launched.append(k)
+            if self.world > 1:
+                h = _all_reduce_sum(self.arena[b['start']:b['end']], self.group, self.backend, async_op=True)
+                if h is not None:
+                    self._handles.append(h)
+
+    def finalize(self):
+        """after the last backward: the buckets not launched yet, the wait for the reduces (stream order only: no host read of
+        device memory), ``p.grad`` = the slice for every parameter"""
+        for k in self._schedule.finish():
+            self._launch(k)
+        for h in self._handles:
+            h.wait()
+        self._handles = []
+        self._optim._mark_written([self.arena])
+        for p, v in zip(self.params, self.views):
+            p.grad = v
+        return self
+
+
+def broadcast_module(module, src=0, group=None):
+    """Every parameter and buffer of ``module`` from rank ``src`` (a global rank) to all ranks of ``group`` (None: nothing to do),
+    what DistributedDataParallel does at construction.  nccl moves device memory, gloo goes through the host.  What was written
+    counts as written for a bound engine (``optim._mark_written``)."""
+    world, backend = _group_info(group)
+    if world == 1:
+        return module
+    import torch.distributed as dist
+    from . import optim
+    written = []
+    with torch.no_grad():
+        for t in list(module.parameters()) + list(module.buffers()):
+            x = t.detach()
+            wire = x.to(torch.uint8) if x.dtype is torch.bool else x
+            staged = backend == 'gloo' and x.is_cuda
+            if staged:
+                wire = wire.cpu()
+            elif not wire.is_contiguous():
+                wire = wire.contiguous()
+            dist.broadcast(wire, src=src, group=group)
+            if dist.get_rank() != src:
+                if wire.data_ptr() != x.data_ptr():
+                    x.copy_(wire.to(x.dtype) if x.dtype is torch.bool else wire)
+                written.append(x)
+    optim._mark_written(written)
+    return module

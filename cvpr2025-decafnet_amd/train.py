@@ -10,13 +10,18 @@ refinement TCN's rate on the counter-based stream of the library (csrc/dropout.h
 backward recomputes the keep bits from the key (``autograd.DropSpec``).  Not implemented, and refused as before: attention-map dropout
 (``attn_pdrop``), channel dropout (``cdrop``), dropout in the text encoder, ``second_fusion=True`` with dropout.
 
-Not here: the gradient all-reduce over ranks, data loading, logging, AMP, graph capture of the step, SGD.
+``DataParallelTrainStep``: the same step on every rank of a process group, what the reference gets from wrapping its model in
+DistributedDataParallel (worker_v2.py:278-280): parameters broadcast from rank 0, the gradients packed into buckets by a HIP kernel
+and all-reduced under the last backward (``dist.GradReducer``), the loss norm summed over the ranks.
+
+Not here: data loading, logging, AMP, graph capture of the step, SGD, gradient compression, the detection of
+parameters that no rank used.
 """
 import copy
 
 import torch
 
-from . import _lib, autograd as A, loss as L, optim as O
+from . import _lib, autograd as A, dist as D, loss as L, optim as O
 
 
 def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_masks, text_size=None, dropout=None, dropout_seed=None):
@@ -116,13 +121,13 @@ class TrainStep:
             raise ValueError(f'{len(batches)} micro-batches and {len(targets)} target tensors')
         self.optimizer.zero_grad(set_to_none=True)
         sums = {}
-        for mb, tg in zip(batches, targets):
+        for i, (mb, tg) in enumerate(zip(batches, targets)):
             out = training_forward(self.model, *(mb.get(k) for k in _BATCH_KEYS))
             d = self.objective(out, tg)
-            d['total'].backward()
+            self._backward(d['total'], i == len(batches) - 1)
             for k, v in d.items():
                 sums[k] = v.detach() if k not in sums else sums[k] + v.detach()
-        self.objective.update_norm(sums.pop('norm'))
+        self.objective.update_norm(self._norm_over_ranks(sums.pop('norm')))
         norm, coef = O.grad_norm_and_coef(self._params, self.clip_grad_norm or 0.0, _table=self._norm_table)
         self.last_coef = coef if self.clip_grad_norm else None
         self.optimizer.step(clip_coef=self.last_coef)
@@ -131,6 +136,14 @@ class TrainStep:
         self.itr += 1
         sums['grad_norm'] = norm
         return sums
+
+    def _backward(self, total, last):
+        """the backward of one micro-batch; ``last``: no further one follows before the update"""
+        total.backward()
+
+    def _norm_over_ranks(self, norm):
+        """the step's norm summed over the ranks (worker_v2.py:379-380): one rank here"""
+        return norm
 
     def state(self):
         """-> (model_ckpt, state_ckpt) with the keys of Trainer.checkpoint (worker_v2.py:680-689).  'loss_norm' is an addition
@@ -166,3 +179,48 @@ class TrainStep:
                 raise ValueError('load_state: the checkpoint carries a dropout generator state; call model.enable_dropout(seed=<int>) first')
             gen.set_state(state_ckpt['dropout_rng'])
         return self
+
+
+class DataParallelTrainStep(TrainStep):
+    """``TrainStep`` on every rank of ``process_group`` (None: one rank), each rank on its own share of the batch: the reference's
+    Trainer with its model in DistributedDataParallel.  The world size comes from the group and reaches the objective as before.
+
+    Construction broadcasts the parameters and buffers of the model and of the EMA copy from rank 0.  ``step`` differs from
+    ``TrainStep.step`` in three places.  The earlier micro-batches accumulate locally (the reference's ``no_sync()``); only the LAST
+    backward runs with the reducer armed: bucket by bucket the accumulated gradients are packed times 1 / world into one flat arena
+    (dcf_dist_pack_grads) and all-reduced while the backward goes on, and afterwards every ``p.grad`` is its slice of the arena, the
+    gradient averaged over the ranks.  The step's norm is summed over the ranks with one all-reduce of the device scalar before the
+    loss-norm update.  The returned cls / reg / total stay rank-local (the reference logs rank 0 alone); grad_norm is the norm of the
+    averaged gradient, equal on all ranks.
+
+    A departure from the single-rank step: every parameter has a gradient after the reduce, zero if nothing reached it on any rank,
+    so it takes weight decay and its Adam step count advances (``dist.GradReducer``).
+
+    Dropout: the step does not touch the keys.  Ranks that should drop different elements pass different seeds, for example
+    ``model.enable_dropout(seed=seed + rank)``.
+
+    Backends: nccl (RCCL), one GPU per rank; gloo stages every bucket through the host and is a flow check for a one-GPU box."""
+
+    def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES):
+        self.group = process_group
+        self.world, self._backend = D._group_info(process_group)
+        super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch)
+        D.broadcast_module(model, 0, process_group)
+        D.broadcast_module(self.ema.module, 0, process_group)
+        self.reducer = D.GradReducer(self._params, process_group, bucket_bytes)
+
+    def _backward(self, total, last):
+        if not last:
+            return total.backward()
+        self.reducer.arm()
+        try:
+            total.backward()
+        finally:
+            self.reducer.disarm()
+        self.reducer.finalize()
+
+    def _norm_over_ranks(self, norm):
+        if self.world > 1:
+            norm = norm.clone()
+            D._all_reduce_sum(norm, self.group, self._backend)
+        return norm
