@@ -157,6 +157,14 @@ DIST_SIGNATURES = {
 }
 
 
+# the attention-gradient extension (include/decafnet_hip_attn.h, dcf_attn_ext_version): same shared object, a fourth table -- the
+# three above are frozen (tests/test_global_attn_grad_cpu.py checks this table against its header)
+ATTN_SIGNATURES = {
+    'dcf_attn_ext_version': (i32, []),
+    'dcf_op_global_attn_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -167,7 +175,8 @@ def lib():
             raise RuntimeError(f'{SO_PATH} is missing: build it with __graft_entry__.build() '
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
+                list(ATTN_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -10,12 +10,15 @@ other five are the forward / backward pairs of csrc/enc_grad.hip (dcf_op_dwconv3
 dcf_op_layerscale_residual and their ``_bwd``) and of csrc/xattn_grad.hip (dcf_op_adaln, dcf_op_adaln_bwd).  Everything runs on the
 current stream and without a host wait.  Tensors are token-major ``(B, T, C)`` fp32 on the GPU; there is no CPU path.
 
+``global_attention`` is the global self-attention core (``mha_win_size = 0``): the forward is dcf_op_local_attn with window = 0, the
+backward dcf_op_global_attn_bwd (csrc/global_attn_grad.hip, include/decafnet_hip_attn.h).
+
 ``conv_head`` runs one pyramid level through a ClsHead / RegHead (libs/modeling/head.py:53-64, :95-108), ``masked_mha`` the
-local-window MaskedMHA (blocks.py:348-373, :391-392), ``ffn`` the FFN (blocks.py:535-538), ``conv_attn_layer`` a ConvAttNLayer
-(blocks.py:462-473) and ``transformer_encoder`` a whole TransformerEncoder block (blocks.py:578-591): a block of the video encoder
-(stride 1 or 2, local window) or of the text encoder (stride 0, global self-attention through ``xattn_mha`` with q = k = v, at most 64
-positions); ``xattn_mha`` is MaskedMHA in its global cross-attention branch (blocks.py:327-356, :374-393), ``conv_xattn_layer`` a
-ConvXAttNLayer (blocks.py:513-520), ``transformer_decoder`` a whole TransformerDecoder layer (blocks.py:632-650, 'adaln' or 'affine')
+self-attention MaskedMHA, local window or global (blocks.py:348-393), ``ffn`` the FFN (blocks.py:535-538), ``conv_attn_layer`` a
+ConvAttNLayer (blocks.py:462-473) and ``transformer_encoder`` a whole TransformerEncoder block (blocks.py:578-591): a block of the
+video encoder (stride 1 or 2, local window or global) or of the text encoder (stride 0, global self-attention through ``xattn_mha``
+with q = k = v; more than 64 positions need heads of 32 or 64 channels); ``xattn_mha`` is MaskedMHA in its global cross-attention
+branch (blocks.py:327-356, :374-393), ``conv_xattn_layer`` a ConvXAttNLayer (blocks.py:513-520), ``transformer_decoder`` a whole TransformerDecoder layer (blocks.py:632-650, 'adaln' or 'affine')
 and ``xattn_fusion`` the XAttNFusion stack (fusion.py:56-66).  So the stem, every pyramid level, the text-conditioned fusion and the
 heads behind them train end to end with ``loss.PointObjective``.
 
@@ -49,8 +52,8 @@ gate, and composed that way -- gate, ``vid_map``, ``text_transformer``, the firs
 (tests/step_grad_ref.py ``run_step``, tests/test_gpu_step_grad.py).
 
 Without a backward yet: the gate (it has no parameters: its inputs are features the caller supplies, so it does not stand between these
-functions and a training step), TextIdentity's attention pool (``text_transformer`` refuses a TextIdentity) and global self-attention
-over more than 64 positions.
+functions and a training step), TextIdentity's attention pool (``text_transformer`` refuses a TextIdentity), cross-attention over more
+than 64 keys, and global self-attention on head dimensions other than 32 / 64 (over more than 64 positions in the text encoder).
 """
 from collections import namedtuple
 
@@ -208,7 +211,7 @@ class _WindowAttentionFn(torch.autograd.Function):
         if kd.shape != qd.shape or vd.shape != qd.shape:
             raise ValueError(f'window_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
         if window <= 0 or window % 2 == 0:
-            raise ValueError(f'window_attention: window = {window} must be odd and positive (global attention has no backward)')
+            raise ValueError(f'window_attention: window = {window} must be odd and positive (global attention is global_attention)')
         m = _mask_rows(mask, B, T)
         if m is None:
             m = torch.ones(B, T, dtype=torch.bool, device=qd.device)       # the forward core reads its mask unconditionally
@@ -230,6 +233,50 @@ class _WindowAttentionFn(torch.autograd.Function):
                                                         _lib.ptr(gv), B, T, C, ctx.n_heads, ctx.window, _lib.current_stream()),
                        'dcf_op_local_attn_bwd')
         return gq, gk, gv, None, None, None
+
+
+_GLOBAL_HEAD_DIMS = (32, 64)     # the head dimensions of k_global_attn and of its backward
+
+
+def _global_head_limit(C, n_heads):
+    """the message of the head-dimension limit of ``global_attention`` that (C channels on n_heads heads) breaks, or None"""
+    if n_heads <= 0 or C % n_heads or C // n_heads not in _GLOBAL_HEAD_DIMS:
+        return f'global attention: C = {C} on {n_heads} heads: the head dimension must be 32 or 64'
+    return None
+
+
+class _GlobalAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, mask, n_heads):
+        limit = _global_head_limit(q.size(-1), int(n_heads))
+        if limit:
+            raise ValueError(f'global_attention: {limit}')
+        qd, kd, vd = (_rows(z, 'global_attention') for z in (q, k, v))
+        B, T, C = qd.shape
+        if kd.shape != qd.shape or vd.shape != qd.shape:
+            raise ValueError(f'global_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
+        if C > 1024:
+            raise ValueError(f'global_attention: C = {C} (at most 1024)')
+        m = _byte_mask(mask, B, T, 'global_attention')
+        if m is None:
+            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)       # the forward core reads its mask unconditionally
+        o = torch.empty_like(qd)
+        _lib.check(_lib.lib().dcf_op_local_attn(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, C, int(n_heads), 0,
+                                                _lib.current_stream()), 'dcf_op_local_attn')
+        ctx.save_for_backward(qd, kd, vd, m)
+        ctx.n_heads = int(n_heads)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, m = ctx.saved_tensors
+        B, T, C = q.shape
+        go = go.float().contiguous()
+        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
+        if gq is not None or gk is not None or gv is not None:
+            _lib.check(_lib.lib().dcf_op_global_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
+                                                         _lib.ptr(gv), B, T, C, ctx.n_heads, _lib.current_stream()), 'dcf_op_global_attn_bwd')
+        return gq, gk, gv, None, None
 
 
 def masked_conv1d(x, mask, weight, bias=None, stride=1):
@@ -283,16 +330,33 @@ def window_attention(q, k, v, mask, n_heads, window):
     return _WindowAttentionFn.apply(q, k, v, mask, n_heads, window)
 
 
+def global_attention(q, k, v, mask, n_heads):
+    """The global self-attention core of MaskedMHA (blocks.py:374-389 with q, k and v of one sequence) on token-major ``q`` / ``k`` / ``v``
+    (B, T, C), heads concatenated along C: softmax over the valid keys of the sequence, d^-1/4 on q and on k, masked keys filled with
+    -inf -> (B, T, C).  ``mask``: (B, T) or (B, 1, T), None = all valid.  It masks keys only: a padded query row has an output and takes
+    a gradient like any other; a padded key takes none.  A sequence without a valid key gives zeros (the reference: NaN) and zero
+    gradients.  Any T, head dimension 32 or 64, C <= 1024 (dcf_op_local_attn with window = 0, dcf_op_global_attn_bwd)."""
+    return _GlobalAttentionFn.apply(q, k, v, mask, n_heads)
+
+
 def masked_mha(q_in, k_in, v_in, mask, mha):
-    """MaskedMHA.forward (blocks.py:327-373, :391-393; local branch, no dropout) on token-major inputs (B, T, C), with ``mha`` a
-    modeling.MaskedMHA of ``window_size > 0``: proj(window_attention(query(q_in), key(k_in), value(v_in))).  The four projections are
-    k = 1 convolutions that do not mask their input (the reference's are plain nn.Conv1d)."""
-    if mha.window_size <= 0:
-        raise ValueError('masked_mha: a MaskedMHA with window_size > 0 is required (global attention has no backward)')
+    """MaskedMHA.forward (blocks.py:327-393; self-attention, no dropout) on token-major inputs (B, T, C), with ``mha`` a
+    modeling.MaskedMHA: proj(window_attention(query(q_in), key(k_in), value(v_in))) for ``window_size > 0``, and
+    proj(global_attention(...)) for ``window_size = 0`` (head dimension 32 or 64).  The four projections are k = 1 convolutions that
+    do not mask their input (the reference's are plain nn.Conv1d)."""
+    if mha.window_size < 0:
+        raise ValueError(f'masked_mha: window_size = {mha.window_size} (odd and positive, or 0 for global attention)')
+    if mha.window_size == 0:
+        limit = _global_head_limit(mha.query.weight.size(0), mha.n_heads)
+        if limit:
+            raise ValueError(f'masked_mha: window_size = 0: {limit}')
     q = masked_conv1d(q_in, None, mha.query.weight, mha.query.bias)
     k = masked_conv1d(k_in, None, mha.key.weight, mha.key.bias)
     v = masked_conv1d(v_in, None, mha.value.weight, mha.value.bias)
-    ctx = window_attention(q, k, v, mask, mha.n_heads, mha.window_size)
+    if mha.window_size == 0:
+        ctx = global_attention(q, k, v, mask, mha.n_heads)
+    else:
+        ctx = window_attention(q, k, v, mask, mha.n_heads, mha.window_size)
     return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
 
 
@@ -613,12 +677,14 @@ def ffn(x, ffn_module, drop=None):
 
 def conv_attn_layer(x, mask, layer):
     """ConvAttNLayer.forward (blocks.py:462-473; no dropout) on token-major ``x`` (B, T, C), with ``layer`` a modeling.ConvAttNLayer of
-    stride 1 or 2 and ``window_size > 0``: q / k / v = {q,k,v}_norm({q,k,v}_conv(x, mask)), then the local MaskedMHA under the strided
-    mask -> ((B, T / stride, C), ``mask[:, ::stride]``)."""
+    stride 1 or 2: q / k / v = {q,k,v}_norm({q,k,v}_conv(x, mask)), then the MaskedMHA under the strided mask, local (``window_size > 0``)
+    or global (``window_size = 0``, head dimension 32 or 64) -> ((B, T / stride, C), ``mask[:, ::stride]``)."""
     if not hasattr(layer, 'q_conv'):
         raise ValueError('conv_attn_layer: stride 0 (no depthwise convolutions: the text encoder) has no backward here')
-    if layer.attn.window_size <= 0:
-        raise ValueError('conv_attn_layer: window_size = 0 (global attention) has no backward')
+    if layer.attn.window_size == 0:
+        limit = _global_head_limit(x.size(-1), layer.attn.n_heads)
+        if limit:
+            raise ValueError(f'conv_attn_layer: window_size = 0: {limit}')
     B, T, _ = x.shape
     if mask is None:
         mask = torch.ones(B, T, dtype=torch.bool, device=x.device)
@@ -631,11 +697,13 @@ def conv_attn_layer(x, mask, layer):
 
 def transformer_encoder(x, mask, block, drop=None, narrow_heads=False):
     """TransformerEncoder.forward (blocks.py:578-591) on token-major ``x`` (B, T, C), with ``block`` a modeling.TransformerEncoder of
-    stride 1 or 2 and ``window_size > 0`` (a stem or pyramid block of the video encoder) -> (y (B, T / stride, C), ``mask[:, ::stride]``),
-    or of stride 0 and ``window_size = 0`` (a block of the text encoder: no depthwise convolutions, q = k = v = ln_attn(x * mask) through
-    the global branch of MaskedMHA, ``xattn_mha``; ``cross_attention``'s limits apply and are raised with its own message before
-    anything runs: at most 64 positions, head dimension 16 / 32 / 64 / 128; ``narrow_heads=True``, which ``text_transformer`` passes,
-    also admits heads of 8 channels, which ``xattn_mha`` runs as zero-padded heads of 16) -> (y (B, T, C), mask).
+    stride 1 or 2 (a stem or pyramid block of the video encoder; local window, or ``window_size = 0``: global self-attention over the
+    clips, head dimension 32 or 64) -> (y (B, T / stride, C), ``mask[:, ::stride]``), or of stride 0 and ``window_size = 0`` (a block of
+    the text encoder: no depthwise convolutions, q = k = v = ln_attn(x * mask) through the global branch of MaskedMHA, ``xattn_mha``).  A
+    stride-0 block of at most 64 positions runs on ``cross_attention`` (head dimension 16 / 32 / 64 / 128; ``narrow_heads=True``, which
+    ``text_transformer`` passes, also admits heads of 8 channels, which ``xattn_mha`` runs as zero-padded heads of 16); a longer one runs
+    on ``global_attention`` and needs a head dimension of 32 or 64.  A limit is raised with its own message before anything runs
+    -> (y (B, T, C), mask).
     To the letter: the input is multiplied by the mask (:581); at stride 2 the skip is masked_max_pool1d of that (:584) but is masked
     with the convolution's mask ``mask[:, ::2]``, not with the pooled one (:586); the output is not masked, so padded rows hold
     ``drop_path_attn.scale * attn.proj.bias``.  ``drop`` (stride 1 / 2 only; group DROP_G_STEM or DROP_G_BRANCH): proj_drop
@@ -643,15 +711,22 @@ def transformer_encoder(x, mask, block, drop=None, narrow_heads=False):
     (B, C, T / stride) tensors of the reference.  No attention-map dropout."""
     if block.stride not in (0, 1, 2):
         raise ValueError(f'transformer_encoder: stride = {block.stride} (0: the text encoder, 1 or 2: the video encoder)')
-    if (block.stride == 0) != (block.window_size == 0):
-        raise ValueError(f'transformer_encoder: stride = {block.stride} with window_size = {block.window_size}: global attention (window_size = 0) '
-                         f'has a backward in the stride-0 blocks of the text encoder alone, and those have no local window')
+    if block.stride == 0 and block.window_size != 0:
+        raise ValueError(f'transformer_encoder: stride = 0 with window_size = {block.window_size}: the stride-0 blocks of the text encoder have '
+                         f'no local window')
     B, T, C = x.shape
+    if block.stride and block.window_size == 0:
+        # known to be unsupported before the device check and before anything is launched
+        limit = _global_head_limit(C, block.attn.attn.n_heads)
+        if limit:
+            raise ValueError(f'transformer_encoder: stride = {block.stride} with window_size = 0: {limit}')
     if block.stride and T % block.stride:
         raise ValueError(f'transformer_encoder: T = {T} must be a multiple of the stride {block.stride}')
     if block.stride == 0:
         # the block is known to be unsupported before anything is launched: cross_attention's own message, with the block named
         limit = (_global_attention_limit if narrow_heads else _cross_attention_limit)(T, C, block.attn.attn.n_heads)
+        if limit and T > 64 and _global_head_limit(C, block.attn.attn.n_heads) is None:
+            limit = None                                 # more than 64 positions on heads of 32 / 64 channels: global_attention
         if limit:
             raise ValueError(f'transformer_encoder: stride = 0 (global self-attention of the text encoder): {limit}')
     drop = _active(drop, 'transformer_encoder')
@@ -795,7 +870,9 @@ def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None):
     ``q_in`` (B, T, Cq) and ``kv_in`` (B', Lk, Ckv), with ``mha`` a modeling.MaskedMHA of ``window_size = 0``:
     proj(cross_attention(query(q_in), key(kv_in), value(kv_in))) -> (B', T, out_dim).  ``kv_size`` (B,): how many of the B' key
     sequences belong to each query sequence; the PROJECTED query is repeated to match (:352-355).  Heads of 8 channels, narrower than
-    ``cross_attention`` admits, run as zero-padded heads of 16 (``_narrow_head_attention``)."""
+    ``cross_attention`` admits, run as zero-padded heads of 16 (``_narrow_head_attention``).  Self-attention (``q_in is kv_in``, no
+    ``kv_size``) over more than 64 positions on heads of 32 or 64 channels runs on ``global_attention``, which has no limit on the
+    length; up to 64 positions nothing changes."""
     if mha.window_size != 0:
         raise ValueError('xattn_mha: a MaskedMHA with window_size = 0 is required (the local branch is masked_mha)')
     q = masked_conv1d(q_in, None, mha.query.weight, mha.query.bias)
@@ -804,7 +881,10 @@ def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None):
     if kv_size is not None and k.size(0) != q.size(0):
         q = _repeat(q, kv_size, k.size(0))
     narrow = q.size(2) % mha.n_heads == 0 and q.size(2) // mha.n_heads == 8
-    ctx = (_narrow_head_attention if narrow else cross_attention)(q, k, v, kv_mask, mha.n_heads)
+    if q_in is kv_in and kv_size is None and k.size(1) > 64 and _global_head_limit(q.size(2), mha.n_heads) is None:
+        ctx = global_attention(q, k, v, kv_mask, mha.n_heads)
+    else:
+        ctx = (_narrow_head_attention if narrow else cross_attention)(q, k, v, kv_mask, mha.n_heads)
     return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
 
 
@@ -1083,7 +1163,8 @@ def text_transformer(tokens, mask, text_net):
     """TextTransformer.forward (text_net.py:158-188, the training branch) on token-major ``tokens`` (B, L, in_dim), with ``text_net`` a
     modeling.TextTransformer -> ((B, L [+ 1], TE), mask (B, L [+ 1])).  To the letter: the background token is prepended to every
     sequence and the mask is extended by its own first column (:179-182); the gradient of ``bkgd_token`` is the sum over the batch.
-    The blocks are global self-attention: L [+ 1] <= 64; heads of 16, 32, 64 or 128 channels, or of 8 (``xattn_mha``)."""
+    The blocks are global self-attention: with L [+ 1] <= 64 positions heads of 16, 32, 64 or 128 channels, or of 8 (``xattn_mha``); longer
+    texts need heads of 32 or 64 channels (``global_attention``)."""
     if not hasattr(text_net, 'bkgd_token') or not hasattr(text_net, 'transformer') or hasattr(text_net, 'attn_pool'):
         raise ValueError(f'text_transformer: {type(text_net).__name__} is not differentiable yet (TextIdentity\'s attention pool has no '
                          f'backward); a modeling.TextTransformer is required')
