@@ -165,6 +165,16 @@ ATTN_SIGNATURES = {
 }
 
 
+# the training-front-end extension (include/decafnet_hip_front.h, dcf_front_ext_version): same shared object, a fifth table -- the
+# four above are frozen (tests/test_front_grad_cpu.py checks this table against its header).  ``nq`` is a HOST array of int32.
+FRONT_NO_SKIP = 1             # DCF_FRONT_NO_SKIP
+FRONT_SIGNATURES = {
+    'dcf_front_ext_version': (i32, []),
+    'dcf_op_vidmap_shared': (i32, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_i32p, c_f32p, i32, i32, i32, i32, i32, vp]),
+    'dcf_op_vidmap_shared_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, i32, vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -176,7 +186,7 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
-                list(ATTN_SIGNATURES.items()):
+                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

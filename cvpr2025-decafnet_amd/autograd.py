@@ -46,10 +46,15 @@ the three outputs ``loss.PointObjective`` consumes, with a graph.  The refinemen
 dropout in training (tcn.py:5,13: 0.5), so these three take ``dropout = (seed, p, b0)``: the keep bits are those of the training
 forward (``model.enable_dropout``; csrc/dropout.h), recomputed in the backward.
 
-``vid_map`` needs no function of its own: it is ``masked_conv1d`` (k = 1) on the gated, concatenated input under the mask after the
-gate, and composed that way -- gate, ``vid_map``, ``text_transformer``, the first ``xattn_fusion``, ``video_transformer``,
-``fuse_and_predict``, ``loss.PointObjective`` -- the whole training step reproduces the reference's ``backward()`` on every parameter
-(tests/step_grad_ref.py ``run_step``, tests/test_gpu_step_grad.py).
+``vid_map`` is ``masked_conv1d`` (k = 1) on the gated, concatenated input under the mask after the gate, and composed that way --
+gate, ``vid_map``, ``text_transformer``, the first ``xattn_fusion``, ``video_transformer``, ``fuse_and_predict``,
+``loss.PointObjective`` -- the whole training step reproduces the reference's ``backward()`` on every parameter
+(tests/step_grad_ref.py ``run_step``, tests/test_gpu_step_grad.py).  ``gated_vid_map`` is the same stage without that input tensor:
+dcf_op_vidmap_shared / dcf_op_vidmap_shared_bwd (csrc/front_grad.hip, include/decafnet_hip_front.h) compute ``W[:, :D] . vid`` and
+``W[:, D:2D] . shallow`` once per video, skip the 64-clip tiles that no query's gate keeps, combine them per query row, and form the
+weight gradient from per-video row sums of the upstream gradient against the channel-major features; the raw-score channel of
+``opt.model.scat`` is a rank-1 term.  It saves only its inputs and meets the same rule against the same reference
+(tests/test_gpu_front_grad.py); ``train.training_forward(front_end='shared')`` composes the step with it.
 
 Without a backward yet: the gate (it has no parameters: its inputs are features the caller supplies, so it does not stand between these
 functions and a training step), TextIdentity's attention pool (``text_transformer`` refuses a TextIdentity), cross-attention over more
@@ -291,6 +296,80 @@ def masked_conv1d(x, mask, weight, bias=None, stride=1):
     if bias is not None:
         raise ValueError('masked_conv1d: stride = 2 is the k = 5 embedding convolution, which has no bias')
     return _MaskedConv5s2Fn.apply(x, mask, weight)
+
+
+class _GatedVidMapFn(torch.autograd.Function):
+    """dcf_op_vidmap_shared / dcf_op_vidmap_shared_bwd (csrc/front_grad.hip).  Saves its inputs and nothing else."""
+
+    @staticmethod
+    def forward(ctx, vid, shallow, gate, mask, correl, sizes, weight, bias, skip):
+        nvid, D, T = vid.shape
+        E = weight.size(0)
+        nq = sum(sizes)
+        flags = 0 if skip else _lib.FRONT_NO_SKIP
+        y = torch.empty(nq, T, E, dtype=torch.float32, device=vid.device)
+        host_nq = torch.tensor(sizes, dtype=torch.int32)
+        w, b = weight.detach().float().reshape(E, -1).contiguous(), bias.detach().float().contiguous()
+        _lib.check(_lib.lib().dcf_op_vidmap_shared(_lib.ptr(vid), _lib.ptr(shallow), _lib.ptr(w), _lib.ptr(b), _lib.ptr(gate), _lib.ptr(mask),
+                                                   _lib.ptr(correl), _lib.ptr(host_nq), _lib.ptr(y), nvid, D, T, E, flags, _lib.current_stream()),
+                   'dcf_op_vidmap_shared')
+        ctx.save_for_backward(vid, gate, mask, *(z for z in (shallow, correl) if z is not None))
+        ctx.msf, ctx.scat, ctx.sizes, ctx.flags, ctx.wshape = shallow is not None, correl is not None, sizes, flags, tuple(weight.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        vid, gate, mask, *rest = ctx.saved_tensors
+        shallow = rest.pop(0) if ctx.msf else None
+        correl = rest.pop(0) if ctx.scat else None
+        nvid, D, T = vid.shape
+        E = ctx.wshape[0]
+        want_w, want_b = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        if not (want_w or want_b):
+            return (None,) * 9
+        # a bias whose weight is frozen still takes its sum from the same call: the same bits whether or not the weight asks
+        gy = gy.float().contiguous()
+        gw = torch.empty(ctx.wshape, dtype=torch.float32, device=vid.device)
+        gb = torch.empty(E, dtype=torch.float32, device=vid.device) if want_b else None
+        host_nq = torch.tensor(ctx.sizes, dtype=torch.int32)
+        _lib.check(_lib.lib().dcf_op_vidmap_shared_bwd(_lib.ptr(vid), _lib.ptr(shallow), _lib.ptr(gate), _lib.ptr(mask), _lib.ptr(correl),
+                                                       _lib.ptr(host_nq), _lib.ptr(gy), _lib.ptr(gw), _lib.ptr(gb), nvid, D, T, E, ctx.flags, 0,
+                                                       _lib.current_stream()), 'dcf_op_vidmap_shared_bwd')
+        return None, None, None, None, None, None, (gw if want_w else None), gb, None
+
+
+def gated_vid_map(vid, shallow, gate, mask, correl, text_size, weight, bias, skip=True):
+    """``vid_map`` of the training forward (model.py:567-583) on shared products: ``MaskedConv1D`` (k = 1) on the gated,
+    concatenated input without building it.  ``vid`` / ``shallow`` (nvid, D, T) channel-major as the batch holds them (``shallow``
+    None: no msf), ``gate`` (B', T) fp32 0 / 1 and ``mask`` (B', T) bool as dcf_op_gate returns them, ``correl`` (B', T) the raw
+    sidekick scores of dcf_op_sidekick (None: no scat), ``text_size`` the queries per video (B' = their sum, rows in (video, query)
+    order; None: one each), ``weight`` (E, Cin, 1) with Cin = D [+ D] [+ 1], ``bias`` (E,) -> (B', T, E).
+    ``W[:, :D] . vid`` and ``W[:, D:2D] . shallow`` are computed once per video, 64-clip tiles that no query of the video keeps not
+    at all (``skip=False`` computes them: a test switch, the same bits); the backward gives the weight and the bias their gradients
+    (include/decafnet_hip_front.h) and saves only its inputs.  The features, the gate and the scores are data: a feature tensor
+    that requires a gradient is refused."""
+    for name, z in (('vid', vid), ('shallow', shallow), ('gate', gate), ('correl', correl)):
+        if z is not None and z.requires_grad:
+            raise ValueError(f'gated_vid_map: `{name}` requires a gradient; the features, the gate and the scores are data (no gradient reaches them)')
+    if not (torch.is_tensor(vid) and vid.is_cuda and vid.dim() == 3):
+        raise RuntimeError('gated_vid_map: (nvid, D, T) features on the GPU are required (there is no CPU path)')
+    nvid, D, T = vid.shape
+    sizes = tuple([1] * nvid if text_size is None else [int(k) for k in text_size])
+    nq = sum(sizes)
+    cin = D * (2 if shallow is not None else 1) + (1 if correl is not None else 0)
+    if len(sizes) != nvid or min(sizes) < 1:
+        raise ValueError(f'gated_vid_map: text_size {list(sizes)} does not match {nvid} videos (one entry >= 1 per video)')
+    if weight.dim() != 3 or weight.size(1) != cin or weight.size(2) != 1 or bias is None or tuple(bias.shape) != (weight.size(0),):
+        raise ValueError(f'gated_vid_map: weight {tuple(weight.shape)} / bias on {cin} input channels (k = 1, with bias)')
+    if shallow is not None and tuple(shallow.shape) != (nvid, D, T):
+        raise ValueError(f'gated_vid_map: shallow {tuple(shallow.shape)} against vid {(nvid, D, T)}')
+    for name, z in (('gate', gate), ('mask', mask), ('correl', correl)):
+        if z is not None and tuple(z.shape) != (nq, T):
+            raise ValueError(f'gated_vid_map: {name} {tuple(z.shape)} is not ({nq}, {T})')
+    f = lambda z: None if z is None else z.detach().float().contiguous()
+    m = mask.detach()
+    m = (m if m.dtype == torch.bool else m != 0).contiguous()
+    return _GatedVidMapFn.apply(f(vid), f(shallow), f(gate), m, f(correl), sizes, weight, bias, bool(skip))
 
 
 def strided_masked_conv1d(x, mask, weight):

@@ -30,6 +30,22 @@ struct LnBwdArgs {
   int rows, C, relu, rows_per_wave;
 };
 
+// power-of-two operand scale of dY from the bits of max |dY|; inv = its exact inverse.  An all-zero or non-finite dY takes 1 (the
+// latter surfaces as a non-finite sum).
+__device__ __forceinline__ float cg_scale(unsigned bits, float& inv) {
+  const int e = (int)((bits >> 23) & 0xffu);
+  if (bits == 0u || e == 255) { inv = 1.f; return 1.f; }
+  int sf = 254 + CG_TARGET_EXP - e;              // biased exponent of 2^(CG_TARGET_EXP - (e - 127))
+  sf = sf < 1 ? 1 : (sf > 253 ? 253 : sf);
+  inv = __uint_as_float((unsigned)(254 - sf) << 23);
+  return __uint_as_float((unsigned)sf << 23);
+}
+
+// The sticky numerics word of the conv-gradient exports (conv_grad.hip): cg_begin fails with the message if an earlier call of the
+// process raised it and hands out the device word otherwise; cg_end queues its copy to the host mirror.  front_grad.hip shares it.
+int cg_begin(const char* what, hipStream_t st, unsigned** word);
+int cg_end(hipStream_t st);
+
 int launch_absmax(const float* x, int64_t n, unsigned* word, hipStream_t st);
 int launch_wgrad(const ConvGradArgs& a, hipStream_t st);
 int launch_ln_bwd(const LnBwdArgs& a, int nwg, hipStream_t st);

@@ -59,17 +59,6 @@ namespace dcf {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-// power-of-two operand scale of dY from the bits of max |dY| (conv_grad.h); inv = its exact inverse.  An all-zero or non-finite
-// dY takes 1 (the latter surfaces as a non-finite sum).
-__device__ __forceinline__ float cg_scale(unsigned bits, float& inv) {
-  const int e = (int)((bits >> 23) & 0xffu);
-  if (bits == 0u || e == 255) { inv = 1.f; return 1.f; }
-  int sf = 254 + CG_TARGET_EXP - e;              // biased exponent of 2^(CG_TARGET_EXP - (e - 127))
-  sf = sf < 1 ? 1 : (sf > 253 ? 253 : sf);
-  inv = __uint_as_float((unsigned)(254 - sf) << 23);
-  return __uint_as_float((unsigned)sf << 23);
-}
-
 __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, int64_t n, unsigned* __restrict__ word) {
   unsigned m = 0u;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -643,7 +632,7 @@ struct CgStatus {
 static CgStatus g_cg;
 static std::mutex g_cg_mu;
 
-static int cg_begin(const char* what, hipStream_t st, unsigned** word) {
+int cg_begin(const char* what, hipStream_t st, unsigned** word) {
   std::lock_guard<std::mutex> lk(g_cg_mu);
   if (!g_cg.dev) {
     unsigned* d = nullptr;
@@ -664,7 +653,7 @@ static int cg_begin(const char* what, hipStream_t st, unsigned** word) {
   *word = g_cg.dev;
   return 0;
 }
-static int cg_end(hipStream_t st) {
+int cg_end(hipStream_t st) {
   DCF_HIP(hipMemcpyAsync((void*)g_cg.host, g_cg.dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   return 0;
 }

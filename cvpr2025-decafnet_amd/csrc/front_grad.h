@@ -1,0 +1,25 @@
+// vid_map of the training step on shared products (front_grad.hip): the arguments of the weight-gradient kernel whose X operand is
+// channel-major.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace dcf {
+
+constexpr int FG_TILE = 64;             // clips per gate tile: the row tile of the forward's channel-major GEMM (GemmArgs::tile_skip)
+constexpr int FG_NQ_CHUNK = 64;         // videos whose query counts one table launch carries by value
+
+// dW[n][c] = sum_b sum_t R[b][t][n] X[b][c][t] for up to two (R, X) pairs (blockIdx.z): the expert half and the shallow half
+struct FrontWgradArgs {
+  const float* R[2];          // (nvid, T, N) token-major row sums of the upstream gradient
+  const float* X[2];          // (nvid, C, T) channel-major features
+  const unsigned* absmax[2];  // device word per pair: bits of max |R|
+  const uint8_t* skip[2];     // (nvid, ntiles) or nullptr: tile f of video b holds a clip some query keeps; 0 = no K step
+  float* part[2];             // (nslices, N, C) partial sums in the scaled domain
+  int nvid, T, N, C;
+  int slice_t, slices_per_video, ntiles;     // slice_t is a multiple of FG_TILE
+};
+
+int launch_front_wgrad(const FrontWgradArgs& a, int pairs, hipStream_t st);
+
+}  // namespace dcf

@@ -84,7 +84,7 @@ int launch_dwconv3(const float* X, int64_t ldx, const uint8_t* mask, const float
                    int C, hipStream_t st);
 int launch_vidmap_combine(const float* P1, const float* P2, const float* bias, const float* gate, const uint8_t* mask,
                           const float* w3, const float* correl, float* X, int T, int rows, int E, unsigned long long vmap,
-                          hipStream_t st);
+                          hipStream_t st, const int* vtab = nullptr);      // vtab: device table, video of batch element r / T (overrides vmap)
 int launch_ln(const LnArgs& a, hipStream_t st);
 int launch_dec_pre(const DecPreArgs& a, hipStream_t st);
 int launch_dec_mid(const float* Xa, const float* H, const float* ln_w, const float* ln_b, float* Q3, float* Xn, int rows,

@@ -16,6 +16,16 @@ and all-reduced under the last backward (``dist.GradReducer``), the loss norm su
 
 Not here: data loading, logging, AMP, graph capture of the step, SGD, gradient compression, the detection of
 parameters that no rank used.
+
+The front end.  ``training_forward(..., front_end='dense')`` makes the network's input as the reference does: the features of a video
+once per query, transposed, times the gate, concatenated with the shallow features, and ``masked_conv1d`` on that (B', T, Cin)
+tensor, which its backward keeps.  ``front_end='shared'`` is ``autograd.gated_vid_map`` (csrc/front_grad.hip,
+include/decafnet_hip_front.h): what the inference engine does -- ``W[:, :D] . vid`` and ``W[:, D:2D] . shallow`` once per video, the
+64-clip tiles that no query's gate keeps not at all, a row kernel per query -- with a weight gradient on the same shared products, so
+nothing of size B' T Cin exists in either direction.  'dense' stays the default (it is what tests/test_gpu_train_step.py pins bit
+for bit against ``run_step``).  ``opt.model.scat`` (the raw sidekick score as input channel 2 D + 1) trains through the shared
+path alone, whatever ``front_end`` says: the score channel is a rank-1 term there.  ``sfonly`` stays refused (the reference's
+training branch, model.py:606-612, never reads it), and so does ``cdrop``: a per-sample channel mask cannot share products.
 """
 import copy
 
@@ -24,7 +34,11 @@ import torch
 from . import _lib, autograd as A, dist as D, loss as L, optim as O
 
 
-def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_masks, text_size=None, dropout=None, dropout_seed=None):
+FRONT_ENDS = ('dense', 'shared')
+
+
+def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_masks, text_size=None, dropout=None, dropout_seed=None,
+                     front_end='dense'):
     """vid / shallow (bs, D, T) channel-major, vid_masks (bs, T) bool, tokens (B', C_t, Lq) channel-major, text_cls (B', D),
     token_masks (B', 1, Lq) or (B', Lq), text_size: queries per video (None: one each), B' = sum(text_size), all on the GPU.
     -> (fpn_logits1, fpn_logits2, fpn_offsets, fpn_masks) as ``model(..., eval=False)`` returns them, with an autograd graph to every
@@ -34,12 +48,21 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     ``dropout``: the (seed, p, b0) of ``autograd.fuse_and_predict`` for the refinement stage's dropout alone, None for none; only
     for a model without ``enable_dropout()``.  With ``model.enable_dropout()`` the forward applies all five rates of
     ``model._dropout_rates()`` with b0 = 0 under one 64-bit key: ``dropout_seed`` if given, else ``model._next_dropout_seed()``
-    (the CPU generator ``enable_dropout`` set up); the key is left in ``model.last_dropout_seed``."""
+    (the CPU generator ``enable_dropout`` set up); the key is left in ``model.last_dropout_seed``.
+    ``front_end``: how the input of the network is made of the features.  'dense' builds the reference's (B', T, Cin) tensor --
+    every video's features once per query, gated, concatenated -- and runs ``masked_conv1d`` on it.  'shared' is
+    ``autograd.gated_vid_map``: the products of ``vid_map`` with the features once per video, clips that no query's gate keeps not at
+    all, no (B', T, Cin) tensor in the forward or saved for the backward.  A model with ``opt.model.scat`` always takes the shared
+    path (its 2 D + 1 input channels do not fit the dense weight gradient), with the scores dcf_op_sidekick returns."""
     from . import modeling
+    if front_end not in FRONT_ENDS:
+        raise ValueError(f'training_forward: front_end = {front_end!r} (one of {FRONT_ENDS})')
     if type(model) is not modeling.PtTransformerEarlyFusionIterative:
         raise NotImplementedError(f'training_forward: {type(model).__name__} is not implemented (PtTransformerEarlyFusionIterative only)')
-    if model.scat or model.sfonly:
-        raise NotImplementedError('training_forward: opt.model.scat / sfonly are not implemented')
+    if model.sfonly:
+        raise NotImplementedError('training_forward: opt.model.sfonly is not implemented: the training branch of the reference '
+                                  '(model.py:606-612) never reads it')
+    shared = front_end == 'shared' or bool(model.scat)
     rates = model._dropout_rates()                                  # None without enable_dropout(); refuses what the forward refuses
     if rates is None and dropout_seed is not None:
         raise ValueError('training_forward: dropout_seed without model.enable_dropout()')
@@ -54,7 +77,7 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     nq = sum(sizes)
     if len(sizes) != bs or min(sizes) < 1 or tokens.size(0) != nq or text_cls.size(0) != nq:
         raise ValueError(f'text_size {sizes} does not match {bs} videos, {tokens.size(0)} token rows and {text_cls.size(0)} text_cls rows')
-    gates, masks, q = [], [], 0
+    gates, masks, correls, q = [], [], [], 0
     for b, k in enumerate(sizes):                                   # one video and its k queries per call
         sh, cls = shallow[b].float().contiguous(), text_cls[q:q + k].float().contiguous()
         vm = vid_masks[b].reshape(-1).to(torch.bool).contiguous()
@@ -63,15 +86,19 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
         gate, mo = torch.empty(k, T, device=vid.device), torch.empty(k, T, dtype=torch.bool, device=vid.device)
         _lib.check(lib.dcf_op_gate(_lib.ptr(correl), _lib.ptr(vm), _lib.ptr(gate), _lib.ptr(mo), T, k, model.sn, float(model.sratio),
                                    int(model.msf), st), 'dcf_op_gate')
-        gates.append(gate), masks.append(mo)
+        gates.append(gate), masks.append(mo), correls.append(correl)
         q += k
     gate, mask = torch.cat(gates), torch.cat(masks)
     kv_size = torch.tensor(sizes, device=vid.device)
-    rep = lambda z: z.transpose(1, 2).contiguous().repeat_interleave(kv_size, dim=0)     # model.py:578-581: video b once per query
-    x = rep(vid) * gate[..., None]
-    if model.msf:
-        x = torch.cat([x, rep(shallow)], dim=2)
-    vid_map = A.masked_conv1d(x, mask, model.vid_map.conv.weight, model.vid_map.conv.bias)
+    if shared:                                                      # the products once per video: nothing is repeated or transposed
+        vid_map = A.gated_vid_map(vid, shallow if model.msf else None, gate, mask, torch.cat(correls) if model.scat else None, sizes,
+                                  model.vid_map.conv.weight, model.vid_map.conv.bias)
+    else:
+        rep = lambda z: z.transpose(1, 2).contiguous().repeat_interleave(kv_size, dim=0)     # model.py:578-581: video b once per query
+        x = rep(vid) * gate[..., None]
+        if model.msf:
+            x = torch.cat([x, rep(shallow)], dim=2)
+        vid_map = A.masked_conv1d(x, mask, model.vid_map.conv.weight, model.vid_map.conv.bias)
     text, text_mask = A.text_transformer(tokens.transpose(1, 2).contiguous(), token_masks.reshape(nq, -1), model.text_net)
     vid_drop = fus_drop = None
     if rates is not None:
@@ -94,10 +121,13 @@ _BATCH_KEYS = ('vid', 'shallow', 'vid_masks', 'tokens', 'text_cls', 'token_masks
 class TrainStep:
     """What the Trainer owns for its iteration: the objective, the optimizer (``optim.make_optimizer``), the scheduler
     (``optim.make_scheduler``), the EMA copy and the ``itr`` counter.  ``opt`` is the ``config.make_opt`` tree; ``itrs_per_epoch``
-    is what the Trainer takes from its data loader (worker_v2.py:252).  The model is on the GPU."""
+    is what the Trainer takes from its data loader (worker_v2.py:252).  The model is on the GPU.  ``front_end``: 'dense' or 'shared',
+    handed to ``training_forward`` (a ``scat`` model takes the shared path either way)."""
 
-    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1):
-        self.model, self.opt = model, opt
+    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1, front_end='dense'):
+        if front_end not in FRONT_ENDS:
+            raise ValueError(f'TrainStep: front_end = {front_end!r} (one of {FRONT_ENDS})')
+        self.model, self.opt, self.front_end = model, opt, front_end
         self.objective = L.PointObjective(opt, world_size=world_size)
         self.optimizer = O.make_optimizer(model, opt['optimizer'])
         sched = copy.deepcopy(dict(opt['scheduler']))                       # opt.py:467-468, worker_v2.py:252, on a copy
@@ -122,7 +152,7 @@ class TrainStep:
         self.optimizer.zero_grad(set_to_none=True)
         sums = {}
         for i, (mb, tg) in enumerate(zip(batches, targets)):
-            out = training_forward(self.model, *(mb.get(k) for k in _BATCH_KEYS))
+            out = training_forward(self.model, *(mb.get(k) for k in _BATCH_KEYS), front_end=self.front_end)
             d = self.objective(out, tg)
             self._backward(d['total'], i == len(batches) - 1)
             for k, v in d.items():
@@ -201,10 +231,10 @@ class DataParallelTrainStep(TrainStep):
 
     Backends: nccl (RCCL), one GPU per rank; gloo stages every bucket through the host and is a flow check for a one-GPU box."""
 
-    def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES):
+    def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES, front_end='dense'):
         self.group = process_group
         self.world, self._backend = D._group_info(process_group)
-        super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch)
+        super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch, front_end=front_end)
         D.broadcast_module(model, 0, process_group)
         D.broadcast_module(self.ema.module, 0, process_group)
         self.reducer = D.GradReducer(self._params, process_group, bucket_bytes)
