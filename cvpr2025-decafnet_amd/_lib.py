@@ -175,6 +175,26 @@ FRONT_SIGNATURES = {
 }
 
 
+# the step-guard extension (include/decafnet_hip_guard.h, dcf_guard_ext_version): same shared object, a sixth table -- the five
+# above are frozen (tests/test_guard_cpu.py checks this table against its header)
+GUARD_APPLY, GUARD_SKIP = 0, 1    # DCF_GUARD_APPLY, DCF_GUARD_SKIP
+
+
+class DcfGuardState(ctypes.Structure):
+    """dcf_guard_state: the 48-byte device record of a step guard (``optim.StepGuard`` owns one)"""
+    _fields_ = [('verdict', i32), ('first_bad_row', i32), ('n_bad_rows', i32), ('reserved0', i32), ('applied', i64), ('skipped', i64),
+                ('last_skipped_attempt', i64), ('conv_flag', i32), ('reserved1', i32)]
+
+
+GUARD_SIGNATURES = {
+    'dcf_guard_ext_version': (i32, []),
+    'dcf_guard_grad_norm': (i32, [vp, c_i32p, i32, i64, f32, c_f32p, c_f32p, vp, vp]),
+    'dcf_guard_adam_step': (i32, [vp, c_i32p, i32, i64, vp, i32, c_f32p, vp, i32, f32, vp]),
+    'dcf_guard_arm': (i32, [vp, vp]),
+    'dcf_guard_disarm': (i32, [vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -186,7 +206,7 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
-                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()):
+                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -45,6 +45,12 @@ __device__ __forceinline__ float cg_scale(unsigned bits, float& inv) {
 // process raised it and hands out the device word otherwise; cg_end queues its copy to the host mirror.  front_grad.hip shares it.
 int cg_begin(const char* what, hipStream_t st, unsigned** word);
 int cg_end(hipStream_t st);
+// The word under a step guard (include/decafnet_hip_guard.h, optim_guard.hip).  While a guard is armed cg_begin never fails for the
+// word and cg_end leaves the host mirror alone; cg_guard_word hands the device word to the guarded norm of the armed state (nullptr
+// for any other state or when disarmed), whose final pass reads and clears it.  cg_guard_disarm queues the mirror copy on `st`.
+int cg_guard_arm(const void* state);
+int cg_guard_disarm(hipStream_t st);
+unsigned* cg_guard_word(const void* state);
 
 int launch_absmax(const float* x, int64_t n, unsigned* word, hipStream_t st);
 int launch_wgrad(const ConvGradArgs& a, hipStream_t st);

@@ -628,22 +628,28 @@ int launch_ln_bwd(const LnBwdArgs& a, int nwg, hipStream_t st) {
 struct CgStatus {
   unsigned* dev = nullptr;
   volatile unsigned* host = nullptr;
+  const void* guard = nullptr;          // the dcf_guard_state a step guard armed (include/decafnet_hip_guard.h), or nullptr
 };
 static CgStatus g_cg;
 static std::mutex g_cg_mu;
 
+static int cg_alloc() {                 // under g_cg_mu
+  if (g_cg.dev) return 0;
+  unsigned* d = nullptr;
+  void* h = nullptr;
+  DCF_HIP(hipMalloc((void**)&d, sizeof(unsigned)));
+  DCF_HIP(hipMemset(d, 0, sizeof(unsigned)));
+  DCF_HIP(hipHostMalloc(&h, sizeof(unsigned), hipHostMallocDefault));
+  *(volatile unsigned*)h = 0u;
+  g_cg.dev = d; g_cg.host = (volatile unsigned*)h;
+  return 0;
+}
+
 int cg_begin(const char* what, hipStream_t st, unsigned** word) {
   std::lock_guard<std::mutex> lk(g_cg_mu);
-  if (!g_cg.dev) {
-    unsigned* d = nullptr;
-    void* h = nullptr;
-    DCF_HIP(hipMalloc((void**)&d, sizeof(unsigned)));
-    DCF_HIP(hipMemset(d, 0, sizeof(unsigned)));
-    DCF_HIP(hipHostMalloc(&h, sizeof(unsigned), hipHostMallocDefault));
-    *(volatile unsigned*)h = 0u;
-    g_cg.dev = d; g_cg.host = (volatile unsigned*)h;
-  }
-  if (*g_cg.host) {
+  if (cg_alloc()) return -1;
+  // armed: the word stays on the device until the guarded norm reads and clears it there; no call fails for it
+  if (!g_cg.guard && *g_cg.host) {
     *g_cg.host = 0u;
     DCF_HIP(hipMemsetAsync(g_cg.dev, 0, sizeof(unsigned), st));
     set_error("%s: an earlier gradient call of this process produced a non-finite sum (inf / NaN in dY or X, |X| >= 4094 or "
@@ -654,8 +660,29 @@ int cg_begin(const char* what, hipStream_t st, unsigned** word) {
   return 0;
 }
 int cg_end(hipStream_t st) {
+  std::lock_guard<std::mutex> lk(g_cg_mu);
+  if (g_cg.guard) return 0;             // armed: the host mirror is not fed, so nothing stale is left in it when the guard disarms
   DCF_HIP(hipMemcpyAsync((void*)g_cg.host, g_cg.dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   return 0;
+}
+
+int cg_guard_arm(const void* state) {
+  std::lock_guard<std::mutex> lk(g_cg_mu);
+  if (cg_alloc()) return -1;
+  g_cg.guard = state;
+  return 0;
+}
+int cg_guard_disarm(hipStream_t st) {
+  std::lock_guard<std::mutex> lk(g_cg_mu);
+  if (!g_cg.guard) return 0;
+  g_cg.guard = nullptr;
+  // what was raised while armed and never consumed by a guarded norm surfaces at the next call, as it would have without the guard
+  DCF_HIP(hipMemcpyAsync((void*)g_cg.host, g_cg.dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  return 0;
+}
+unsigned* cg_guard_word(const void* state) {
+  std::lock_guard<std::mutex> lk(g_cg_mu);
+  return state && g_cg.guard == state ? g_cg.dev : nullptr;
 }
 
 }  // namespace dcf

@@ -71,4 +71,139 @@ __device__ __forceinline__ void store4(float* __restrict__ base, long long i, lo
 }
 __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The bodies of the table kernels, shared by optim.hip and optim_guard.hip (include/decafnet_hip_guard.h): one workgroup of OPT_NT
+// threads owns one chunk of DCF_OPTIM_CHUNK elements of one tensor, which it finds through the chunk map and the row's chunk prefix.
+struct OptimTable {
+  const dcf_optim_row* rows;
+  const int32_t* chunk_map;
+};
+
+// The sum of squares of the workgroup's chunk -> partial[blockIdx.x].  Lane t owns the elements [s * 1024 + 4 t, + 4) of the chunk for
+// s = 0 .. OPT_SWEEPS-1, in both the 16-byte and the scalar path: the lane's fp32 sum runs over the same elements in the same order
+// either way.  NULL_G: a row whose g is NULL counts as one without a gradient (the guarded export; the plain one reads the flag alone).
+template <bool NULL_G>
+__device__ __forceinline__ void optim_sumsq_chunk(OptimTable tb, double* __restrict__ partial) {
+  __shared__ double s_wave[OPT_NT / 64];
+  const dcf_optim_row r = tb.rows[__builtin_amdgcn_readfirstlane(tb.chunk_map[blockIdx.x])];
+  float acc = 0.f;
+  if (!(r.flags & DCF_OPTIM_NO_GRAD) && (!NULL_G || r.g != nullptr)) {
+    const float* g = static_cast<const float*>(r.g);
+    const bool al = aligned16(g);
+    const long long base = ((long long)blockIdx.x - r.chunk0) * DCF_OPTIM_CHUNK;
+#pragma unroll
+    for (int s = 0; s < OPT_SWEEPS; ++s) {
+      const long long i = base + s * OPT_STRIDE + threadIdx.x * OPT_VEC;
+      if (i < r.n) acc = sumsq4(acc, load4(g, i, r.n, al));
+    }
+  }
+  double d = (double)acc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) d += __shfl_xor(d, o);      // a butterfly: every lane ends with the same sum, in a fixed order
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < OPT_NT / 64; ++w) t += s_wave[w];
+    partial[blockIdx.x] = t;
+  }
+}
+
+// The sum of the chunk partials in one workgroup: thread t adds the partials t, t + NT, ... in order, then thread 0 adds the threads
+// in order.  The total is valid in thread 0 alone; s_sum holds OPT_NT doubles.
+__device__ __forceinline__ double optim_sum_partials(const double* __restrict__ partial, long long n_chunks, double* s_sum) {
+  double s = 0.0;
+  for (long long i = threadIdx.x; i < n_chunks; i += OPT_NT) s += partial[i];
+  s_sum[threadIdx.x] = s;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < OPT_NT; ++i) t += s_sum[i];
+  return t;
+}
+
+// the norm of a sum of squares and torch.nn.utils.clip_grad_norm_'s coefficient: clamp(max_norm / (norm + 1e-6), max = 1) in fp32; a
+// NaN passes the clamp as it does there
+__device__ __forceinline__ void optim_norm_coef(double sumsq, float max_norm, float& norm, float& coef) {
+  norm = (float)sqrt(sumsq);
+  coef = 1.f;
+  if (max_norm > 0.f) {
+    const float c = max_norm / (norm + 1e-6f);
+    coef = c > 1.f ? 1.f : c;
+  } else if (norm != norm) {
+    coef = norm;
+  }
+}
+
+// The Adam / AdamW update of the workgroup's chunk, with the EMA copy when EMA.  GATED (the guarded export): `gate` points to one
+// device word, the same for the whole grid; a non-zero word means return before anything is written.  Its load is issued with the
+// chunk map's and waited for only after the row is there, so the gate costs one scalar load and no latency of its own.
+template <bool EMA, bool GATED = false>
+__device__ __forceinline__ void optim_adam_chunk(OptimTable tb, const OptimGroups& hs, const float* __restrict__ coef_dev, float beta,
+                                                 const int32_t* __restrict__ gate = nullptr) {
+  const int32_t closed = GATED ? *gate : 0;
+  const dcf_optim_row r = tb.rows[__builtin_amdgcn_readfirstlane(tb.chunk_map[blockIdx.x])];
+  const bool has_g = !(r.flags & DCF_OPTIM_NO_GRAD);
+  const bool has_e = EMA && r.ema != nullptr;
+  if (GATED && closed != 0) return;
+  if (!has_g && !has_e) return;
+  float* p = static_cast<float*>(r.p);
+  const float* g = static_cast<const float*>(r.g);
+  float* m = static_cast<float*>(r.exp_avg);
+  float* v = static_cast<float*>(r.exp_avg_sq);
+  float* e = static_cast<float*>(r.ema);
+  const bool al_p = aligned16(p), al_g = aligned16(g), al_m = aligned16(m), al_v = aligned16(v), al_e = aligned16(e);
+  const dcf_optim_group h = hs.g[__builtin_amdgcn_readfirstlane(r.group) & (DCF_OPTIM_MAX_GROUPS - 1)];   // uniform: read from the kernel arguments
+  const float coef = coef_dev ? *coef_dev : 1.f;
+  const long long base = ((long long)blockIdx.x - r.chunk0) * DCF_OPTIM_CHUNK;
+#pragma unroll
+  for (int s = 0; s < OPT_SWEEPS; ++s) {
+    const long long i = base + s * OPT_STRIDE + threadIdx.x * OPT_VEC;
+    if (i >= r.n) break;
+    f32x4 xp = load4(p, i, r.n, al_p);
+    if (has_g) {
+      const f32x4 xg = load4(g, i, r.n, al_g);
+      f32x4 xm = load4(m, i, r.n, al_m);
+      f32x4 xv = load4(v, i, r.n, al_v);
+#pragma unroll
+      for (int j = 0; j < OPT_VEC; ++j) {
+        float ep = xp[j], em = xm[j], ev = xv[j];
+        adam_elem(ep, xg[j], em, ev, h, coef);
+        xp[j] = ep, xm[j] = em, xv[j] = ev;
+      }
+      store4(p, i, r.n, al_p, xp);
+      store4(m, i, r.n, al_m, xm);
+      store4(v, i, r.n, al_v, xv);
+    }
+    if (has_e) {
+      f32x4 xe = load4(e, i, r.n, al_e);
+#pragma unroll
+      for (int j = 0; j < OPT_VEC; ++j) xe[j] = ema_elem(xp[j], xe[j], beta);
+      store4(e, i, r.n, al_e, xe);
+    }
+  }
+}
+
+// the argument checks every table export starts with; -1 with the message set
+static inline int optim_check_table(const char* who, const dcf_optim_row* table, const int32_t* chunk_map, int32_t n_tensors, int64_t n_chunks) {
+  DCF_CHECK(n_tensors >= 0 && n_chunks >= 0, "%s: negative count (n_tensors %d, n_chunks %lld)", who, (int)n_tensors, (long long)n_chunks);
+  DCF_CHECK(n_chunks <= 0x7fffffffll, "%s: %lld chunks exceed one grid", who, (long long)n_chunks);
+  DCF_CHECK(n_chunks == 0 || (table && chunk_map), "%s: null table", who);
+  DCF_CHECK(n_chunks == 0 || n_tensors > 0, "%s: %lld chunks but no tensors", who, (long long)n_chunks);
+  return 0;
+}
+
+// the by-value group array of an Adam launch, checked; -1 with the message set
+static inline int optim_check_groups(const char* who, const dcf_optim_group* groups, int32_t n_groups, OptimGroups& hs) {
+  DCF_CHECK(n_groups >= 0, "%s: negative count (n_groups %d)", who, (int)n_groups);
+  DCF_CHECK(n_groups <= DCF_OPTIM_MAX_GROUPS, "%s: %d groups, at most %d", who, (int)n_groups, DCF_OPTIM_MAX_GROUPS);
+  DCF_CHECK(n_groups == 0 || groups, "%s: null groups", who);
+  hs = {};
+  for (int i = 0; i < n_groups; ++i) {
+    DCF_CHECK(groups[i].mode == DCF_OPTIM_ADAMW || groups[i].mode == DCF_OPTIM_ADAM, "%s: unknown mode %d in group %d", who,
+              (int)groups[i].mode, i);
+    hs.g[i] = groups[i];
+  }
+  return 0;
+}
+
 }  // namespace dcf

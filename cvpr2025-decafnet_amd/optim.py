@@ -1,6 +1,7 @@
 """The Trainer's parameter update (libs/worker_v2.py:318-325, :647-656; libs/modeling/optim.py) on the GPU's multi-tensor kernels.
 
     clip_grad_norm_ -> dcf_optim_grad_norm (+ dcf_optim_scale stand-alone, or the coefficient folded into the update)
+    StepGuard       -> dcf_guard_grad_norm / dcf_guard_adam_step: the same two launches, skipped on the device if a gradient is non-finite
     AdamW.step()    -> dcf_optim_adam_step: one launch over every parameter tensor, the decay / no-decay groups by value
     _ema_update()   -> the same launch (``attach_ema``)
     scheduler       -> LinearWarmupMultiStepLR / LinearWarmupCosineAnnealingLR: host arithmetic in double, a closed form per step
@@ -100,19 +101,94 @@ def _mark_written(tensors):
         torch.autograd.graph.increment_version(tensors)
 
 
-def _norm_launch(table, max_norm, device):
+def _norm_launch(table, max_norm, device, guard=None):
     out = torch.empty(2, dtype=torch.float32, device=device)
     lib = _lib.lib()
+    outs = (ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(out.data_ptr() + 4))
     with torch.cuda.device(device):
-        _lib.check(lib.dcf_optim_grad_norm(*table.args(), float(max_norm or 0.0), ctypes.c_void_p(out.data_ptr()),
-                                           ctypes.c_void_p(out.data_ptr() + 4), _lib.current_stream()), 'dcf_optim_grad_norm')
+        if guard is None:
+            _lib.check(lib.dcf_optim_grad_norm(*table.args(), float(max_norm or 0.0), *outs, _lib.current_stream()), 'dcf_optim_grad_norm')
+        else:
+            _lib.check(lib.dcf_guard_grad_norm(*table.args(), float(max_norm or 0.0), *outs, guard._on(device), _lib.current_stream()),
+                       'dcf_guard_grad_norm')
     return out[0], out[1]
 
 
-def grad_norm_and_coef(parameters, max_norm, _table=None):
+# dcf_guard_state as a packed numpy record (48 bytes)
+_GUARD = np.dtype([('verdict', '<i4'), ('first_bad_row', '<i4'), ('n_bad_rows', '<i4'), ('reserved0', '<i4'), ('applied', '<i8'),
+                   ('skipped', '<i8'), ('last_skipped_attempt', '<i8'), ('conv_flag', '<i4'), ('reserved1', '<i4')])
+assert _GUARD.itemsize == ctypes.sizeof(_lib.DcfGuardState) == 48
+
+
+class StepGuard:
+    """Owns one dcf_guard_state record on ``device`` (include/decafnet_hip_guard.h): the verdict of the last guarded norm and the
+    running counts of applied and skipped steps.  Hand it to ``grad_norm_and_coef(..., guard=g)`` and to ``AdamW.step(..., guard=g)``:
+    the norm decides on the GPU whether any gradient is non-finite, the update reads the decision there and writes nothing on a skip.
+    Neither call reads anything back.  ``arm()`` ... ``disarm()`` around the forward, the backward and the update keeps the
+    conv-gradient operators' sticky numerics word from failing the next call; the guarded norm turns it into a skip instead.
+    ``report()`` is the only host read, for logs and checkpoints."""
+
+    def __init__(self, device):
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError(f'StepGuard on {device}: the guarded update runs on the GPU only (there is no CPU path)')
+        self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        self._state = torch.empty(_GUARD.itemsize // 8, dtype=torch.int64, device=self.device)         # 8-byte aligned
+        self._rows = None                               # per row of the last guarded norm's table: the index into its `parameters`
+        self.armed = False
+        self.load_counters(0, 0)
+
+    def _on(self, device):
+        if device != self.device:
+            raise ValueError(f'the guard lives on {self.device}, the tensors on {device}: one device')
+        return ctypes.c_void_p(self._state.data_ptr())
+
+    def load_counters(self, applied, skipped):
+        """reset the record to `applied` applied and `skipped` skipped steps and nothing known about the last skip (stream-ordered)"""
+        rec = np.zeros(1, dtype=_GUARD)
+        rec['first_bad_row'], rec['last_skipped_attempt'], rec['applied'], rec['skipped'] = -1, -1, int(applied), int(skipped)
+        with torch.cuda.device(self.device):
+            self._state.copy_(torch.from_numpy(rec.view(np.int64).reshape(-1).copy()).pin_memory(), non_blocking=True)
+        return self
+
+    def arm(self):
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().dcf_guard_arm(self._on(self.device), _lib.current_stream()), 'dcf_guard_arm')
+        self.armed = True
+        return self
+
+    def disarm(self):
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().dcf_guard_disarm(_lib.current_stream()), 'dcf_guard_disarm')
+        self.armed = False
+        return self
+
+    def report(self, names=None):
+        """Reads the record back (THE host read: it waits for the stream).  -> {'applied', 'skipped', 'last_skipped_attempt' (attempts
+        count from 0; -1: none yet), 'first_bad', 'n_bad_rows', 'conv_flag', 'verdict'}.  'first_bad' is the first tensor with a
+        non-finite chunk sum at the last skipped attempt: its entry of ``names`` (aligned with the ``parameters`` the guarded norm was
+        given) if names are given, else its row in the norm's table (the tensors that had a gradient, in order); None if no step was
+        skipped yet or the conv-gradient word alone caused the skip.  'verdict' is that of the last norm (0 apply, 1 skip)."""
+        rec = self._state.cpu().numpy().view(_GUARD)[0]
+        row = int(rec['first_bad_row'])
+        first = None
+        if row >= 0:
+            first = row
+            if names is not None:
+                names = list(names)
+                i = self._rows[row] if self._rows is not None and row < len(self._rows) else row
+                first = names[i] if i < len(names) else row
+        return {'applied': int(rec['applied']), 'skipped': int(rec['skipped']), 'last_skipped_attempt': int(rec['last_skipped_attempt']),
+                'first_bad': first, 'n_bad_rows': int(rec['n_bad_rows']), 'conv_flag': int(rec['conv_flag']), 'verdict': int(rec['verdict'])}
+
+
+def grad_norm_and_coef(parameters, max_norm, _table=None, guard=None):
     """(total L2 norm of the gradients, min(1, max_norm / (norm + 1e-6))) as two 0-d device tensors, for the fused path:
     ``optimizer.step(clip_coef=coef)`` folds the coefficient into the update and leaves ``p.grad`` unscaled.  max_norm <= 0 or None
-    gives the coefficient 1.  The norm is summed in a fixed order: the same gradients give the same bits on every run."""
+    gives the coefficient 1.  The norm is summed in a fixed order: the same gradients give the same bits on every run.
+    ``guard``: a ``StepGuard``.  The norm then also decides, on the GPU, whether the step may be applied (dcf_guard_grad_norm): with
+    finite gradients norm and coefficient have the bits of the unguarded call; with a NaN, an inf or a chunk whose squares overflow
+    fp32 anywhere the coefficient is +0, the norm stays non-finite and the guard's verdict is skip.  One attempt is counted per call."""
     table = _CLIP_TABLE if _table is None else _table
     params = [parameters] if torch.is_tensor(parameters) else list(parameters)      # once: a generator is consumed by the first walk
     rec, device = _grad_records(params)
@@ -121,7 +197,9 @@ def grad_norm_and_coef(parameters, max_norm, _table=None):
             _need_gpu(p, f'parameter {i}')
         device = params[0].device if params else torch.device('cuda')
     table.update(rec, device)
-    return _norm_launch(table, max_norm, device)
+    if guard is not None:
+        guard._rows = [i for i, p in enumerate(params) if p.grad is not None]
+    return _norm_launch(table, max_norm, device, guard)
 
 
 def clip_grad_norm_(parameters, max_norm):
@@ -145,6 +223,9 @@ class AdamW(torch.optim.Optimizer):
 
     ``step(clip_coef=None)``: clip_coef is the one-element device tensor of ``grad_norm_and_coef`` (or None): the gradient is
     multiplied by it inside the update, ``p.grad`` itself keeps its values.  ``attach_ema`` makes the same launch move an EMA copy.
+    ``step(guard=g)``: the launch obeys the verdict of the ``StepGuard``'s last ``grad_norm_and_coef(..., guard=g)``: on a skip it
+    writes no byte of any parameter, moment or EMA tensor.  The host cannot know the verdict, so ``state[p]['step']`` advances
+    either way: the bias corrections follow the attempted steps.
     Parameters are fp32, contiguous and, when ``step`` runs, on the GPU."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, mode='adamw'):
@@ -234,7 +315,7 @@ class AdamW(torch.optim.Optimizer):
         return arr
 
     @torch.no_grad()
-    def step(self, closure=None, clip_coef=None):
+    def step(self, closure=None, clip_coef=None, guard=None):
         if closure is not None:
             raise NotImplementedError('step(closure) is not implemented')
         # One pass over the parameters gathers the table's columns as plain lists (this loop is the host cost of a step: a few calls
@@ -290,10 +371,15 @@ class AdamW(torch.optim.Optimizer):
             if clip_coef.numel() != 1 or clip_coef.device != device:
                 raise ValueError(f'clip_coef: one float32 on {device} is expected')
         self._table.update(rec, device)
+        ema = (int(bool(self._ema)), float(self._ema_beta or 0.0))
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().dcf_optim_adam_step(*self._table.args(), ctypes.cast(groups, ctypes.c_void_p), len(keys),
-                                                      _lib.ptr(clip_coef), int(bool(self._ema)), float(self._ema_beta or 0.0),
-                                                      _lib.current_stream()), 'dcf_optim_adam_step')
+            if guard is None:
+                _lib.check(_lib.lib().dcf_optim_adam_step(*self._table.args(), ctypes.cast(groups, ctypes.c_void_p), len(keys),
+                                                          _lib.ptr(clip_coef), *ema, _lib.current_stream()), 'dcf_optim_adam_step')
+            else:                                                # the verdict of the guard's last norm decides on the device
+                _lib.check(_lib.lib().dcf_guard_adam_step(*self._table.args(), ctypes.cast(groups, ctypes.c_void_p), len(keys),
+                                                          _lib.ptr(clip_coef), guard._on(device), *ema, _lib.current_stream()),
+                           'dcf_guard_adam_step')
         for st, t in counts:                                     # the update is enqueued: now the counts advance
             st['step'] = t
             written.append(st['exp_avg']), written.append(st['exp_avg_sq'])

@@ -14,6 +14,20 @@ backward recomputes the keep bits from the key (``autograd.DropSpec``).  Not imp
 DistributedDataParallel (worker_v2.py:278-280): parameters broadcast from rank 0, the gradients packed into buckets by a HIP kernel
 and all-reduced under the last backward (``dist.GradReducer``), the loss norm summed over the ranks.
 
+The guarded step.  ``TrainStep(..., skip_nonfinite=True)`` keeps one non-finite gradient from destroying the run, without a host read:
+the norm's final pass decides on the GPU (include/decafnet_hip_guard.h; a NaN, an inf, or finite elements whose squares overflow fp32
+in any tensor, or a non-finite sum reported by a conv-gradient operator), and the update kernel reads the verdict and returns.  On
+a skip the parameters, both moments and the EMA copy keep their bits; ``p.grad`` keeps the offending gradient for inspection; the
+returned ``grad_norm`` is the non-finite norm and ``last_coef`` is 0.  What a skip does NOT hold back: the loss-norm update (a count
+of positive points, always finite), ``scheduler.step()``, ``itr``, and Adam's step count -- the count lives on the host and the
+verdict is not read back, so the bias corrections follow ATTEMPTED steps.  ``torch.cuda.amp.GradScaler`` holds the count back; here,
+after s skips among t attempts, each correction is 1 - b^t where 1 - b^(t-s) belongs, a factor (1 - b^t) / (1 - b^(t-s)) between
+the two, and the step is (1 - b1^(t-s)) / (1 - b1^t) * sqrt((1 - b2^t) / (1 - b2^(t-s))) of what it would be.  For betas
+(0.9, 0.999) and one skip that is 0.74 at t = 2, 1.009 at t = 50, 1.0003 at t = 1000 and 1.000007 at t = 5000: negligible past the
+warm-up, and nothing accumulates, since the moments themselves are untouched.  With finite gradients the guarded step computes the
+bits of the unguarded one.  ``guard.report(names)`` is the one host read (applied, skipped,
+the last skipped attempt, the first offending parameter); ``state()`` carries the two counters under 'guard'.
+
 Not here: data loading, logging, AMP, graph capture of the step, SGD, gradient compression, the detection of
 parameters that no rank used.
 
@@ -122,12 +136,16 @@ class TrainStep:
     """What the Trainer owns for its iteration: the objective, the optimizer (``optim.make_optimizer``), the scheduler
     (``optim.make_scheduler``), the EMA copy and the ``itr`` counter.  ``opt`` is the ``config.make_opt`` tree; ``itrs_per_epoch``
     is what the Trainer takes from its data loader (worker_v2.py:252).  The model is on the GPU.  ``front_end``: 'dense' or 'shared',
-    handed to ``training_forward`` (a ``scat`` model takes the shared path either way)."""
+    handed to ``training_forward`` (a ``scat`` model takes the shared path either way).  ``skip_nonfinite=True``: the step owns an
+    ``optim.StepGuard`` (``self.guard``), armed around forward, backward and update; a step whose gradients are not all finite is
+    skipped on the GPU (module docstring).  ``False`` -- the default -- launches exactly what it launched before the option existed."""
 
-    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1, front_end='dense'):
+    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1, front_end='dense', skip_nonfinite=False):
         if front_end not in FRONT_ENDS:
             raise ValueError(f'TrainStep: front_end = {front_end!r} (one of {FRONT_ENDS})')
-        self.model, self.opt, self.front_end = model, opt, front_end
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f'TrainStep: skip_nonfinite = {skip_nonfinite!r} (True or False)')
+        self.model, self.opt, self.front_end, self.skip_nonfinite = model, opt, front_end, skip_nonfinite
         self.objective = L.PointObjective(opt, world_size=world_size)
         self.optimizer = O.make_optimizer(model, opt['optimizer'])
         sched = copy.deepcopy(dict(opt['scheduler']))                       # opt.py:467-468, worker_v2.py:252, on a copy
@@ -139,6 +157,15 @@ class TrainStep:
         self.last_coef = None                                               # the clip coefficient of the last step (a device tensor)
         self._norm_table = O._Table()
         self._params = list(model.parameters())
+        self.guard, self._guard_counters = None, (0, 0)                     # the StepGuard of skip_nonfinite, made once the model is on the GPU
+        self._ensure_guard()
+
+    def _ensure_guard(self):
+        """the step guard of ``skip_nonfinite=True``, or None: without the option, and while the model is not on the GPU (the forward
+        refuses that below, as it does without the option)"""
+        if self.guard is None and self.skip_nonfinite and self._params and self._params[0].is_cuda:
+            self.guard = O.StepGuard(self._params[0].device).load_counters(*self._guard_counters)
+        return self.guard
 
     def step(self, batch, targets):
         """``batch``: a dict with the arguments of ``training_forward`` (vid, shallow, vid_masks, tokens, text_cls, token_masks,
@@ -149,6 +176,16 @@ class TrainStep:
         batches, targets = ([batch], [targets]) if isinstance(batch, dict) else (list(batch), list(targets))
         if len(batches) != len(targets) or not batches:
             raise ValueError(f'{len(batches)} micro-batches and {len(targets)} target tensors')
+        guard = self._ensure_guard()
+        if guard is None:
+            return self._step(batches, targets, None)
+        guard.arm()                                        # a non-finite sum in a conv gradient becomes a skip, not a failed next call
+        try:
+            return self._step(batches, targets, guard)
+        finally:
+            guard.disarm()
+
+    def _step(self, batches, targets, guard):
         self.optimizer.zero_grad(set_to_none=True)
         sums = {}
         for i, (mb, tg) in enumerate(zip(batches, targets)):
@@ -158,9 +195,9 @@ class TrainStep:
             for k, v in d.items():
                 sums[k] = v.detach() if k not in sums else sums[k] + v.detach()
         self.objective.update_norm(self._norm_over_ranks(sums.pop('norm')))
-        norm, coef = O.grad_norm_and_coef(self._params, self.clip_grad_norm or 0.0, _table=self._norm_table)
+        norm, coef = O.grad_norm_and_coef(self._params, self.clip_grad_norm or 0.0, _table=self._norm_table, guard=guard)
         self.last_coef = coef if self.clip_grad_norm else None
-        self.optimizer.step(clip_coef=self.last_coef)
+        self.optimizer.step(clip_coef=self.last_coef, guard=guard)
         if self.scheduler is not None:
             self.scheduler.step()
         self.itr += 1
@@ -187,6 +224,10 @@ class TrainStep:
         gen = self._dropout_generator()
         if gen is not None:
             state['dropout_rng'] = gen.get_state().clone()
+        if self.skip_nonfinite:                                            # the guard's two counters: a host read, like the rest
+            rep = None if self.guard is None else self.guard.report()
+            a, k = self._guard_counters if rep is None else (rep['applied'], rep['skipped'])
+            state['guard'] = {'applied': a, 'skipped': k}
         return {'model': snap(self.model.state_dict()), 'model_ema': snap(self.ema.state_dict())}, state
 
     def _dropout_generator(self):
@@ -208,6 +249,10 @@ class TrainStep:
             if gen is None:
                 raise ValueError('load_state: the checkpoint carries a dropout generator state; call model.enable_dropout(seed=<int>) first')
             gen.set_state(state_ckpt['dropout_rng'])
+        if self.skip_nonfinite and 'guard' in state_ckpt:
+            self._guard_counters = (int(state_ckpt['guard']['applied']), int(state_ckpt['guard']['skipped']))
+            if self._ensure_guard() is not None:
+                self.guard.load_counters(*self._guard_counters)
         return self
 
 
@@ -229,12 +274,20 @@ class DataParallelTrainStep(TrainStep):
     Dropout: the step does not touch the keys.  Ranks that should drop different elements pass different seeds, for example
     ``model.enable_dropout(seed=seed + rank)``.
 
+    ``skip_nonfinite=True``: every rank owns a guard and decides for itself, with no further collective.  The verdict is taken from
+    the norm of the AVERAGED gradient, which has the same bits on every rank, and a NaN or inf in one rank's share is one in the sum:
+    all ranks skip the same steps and their parameters stay equal.  The conv-gradient word is rank-local; a non-finite sum it reports
+    sits in a gradient of that rank and so in the average, except where a later mask multiplies it away -- then that rank alone would
+    skip and the ranks would part.  Equal ``skipped`` counts in ``guard.report()`` of all ranks show that it has not happened.
+
     Backends: nccl (RCCL), one GPU per rank; gloo stages every bucket through the host and is a flow check for a one-GPU box."""
 
-    def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES, front_end='dense'):
+    def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES, front_end='dense',
+                 skip_nonfinite=False):
         self.group = process_group
         self.world, self._backend = D._group_info(process_group)
-        super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch, front_end=front_end)
+        super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch, front_end=front_end,
+                         skip_nonfinite=skip_nonfinite)
         D.broadcast_module(model, 0, process_group)
         D.broadcast_module(self.ema.module, 0, process_group)
         self.reducer = D.GradReducer(self._params, process_group, bucket_bytes)
