@@ -195,6 +195,16 @@ GUARD_SIGNATURES = {
 }
 
 
+# the step-count extension (include/decafnet_hip_clock.h, dcf_clock_ext_version): same shared object, a seventh table -- the six
+# above are frozen (tests/test_clock_cpu.py checks this table against its header).  ``groups``, ``bc_tables`` and ``bc_len`` are HOST
+# arrays; ``steps`` is int64 in device memory.
+CLOCK_MAX_TABLE = 1 << 22     # the longest bias-correction table optim.AdamW(device_count=True) builds
+CLOCK_SIGNATURES = {
+    'dcf_clock_ext_version': (i32, []),
+    'dcf_clock_adam_step': (i32, [vp, c_i32p, i32, i64, vp, i32, vp, c_i32p, c_i64p, c_f32p, vp, i32, f32, vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -206,7 +216,7 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
-                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()):
+                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(CLOCK_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -134,25 +134,19 @@ __device__ __forceinline__ void optim_norm_coef(double sumsq, float max_norm, fl
   }
 }
 
-// The Adam / AdamW update of the workgroup's chunk, with the EMA copy when EMA.  GATED (the guarded export): `gate` points to one
-// device word, the same for the whole grid; a non-zero word means return before anything is written.  Its load is issued with the
-// chunk map's and waited for only after the row is there, so the gate costs one scalar load and no latency of its own.
-template <bool EMA, bool GATED = false>
-__device__ __forceinline__ void optim_adam_chunk(OptimTable tb, const OptimGroups& hs, const float* __restrict__ coef_dev, float beta,
-                                                 const int32_t* __restrict__ gate = nullptr) {
-  const int32_t closed = GATED ? *gate : 0;
-  const dcf_optim_row r = tb.rows[__builtin_amdgcn_readfirstlane(tb.chunk_map[blockIdx.x])];
-  const bool has_g = !(r.flags & DCF_OPTIM_NO_GRAD);
-  const bool has_e = EMA && r.ema != nullptr;
-  if (GATED && closed != 0) return;
-  if (!has_g && !has_e) return;
+// The sweeps of the workgroup's chunk of row r: the Adam / AdamW update where has_g, the EMA copy where has_e.  Shared by every update
+// kernel (optim.hip, optim_guard.hip, optim_clock.hip).  `group_of()` yields the row's group record, uniform over the workgroup; it is
+// a callable so that the record is read where it always was, after the addresses are looked at.
+template <bool EMA, class GroupOf>
+__device__ __forceinline__ void optim_adam_sweeps(const dcf_optim_row& r, bool has_g, bool has_e, GroupOf group_of,
+                                                  const float* __restrict__ coef_dev, float beta) {
   float* p = static_cast<float*>(r.p);
   const float* g = static_cast<const float*>(r.g);
   float* m = static_cast<float*>(r.exp_avg);
   float* v = static_cast<float*>(r.exp_avg_sq);
   float* e = static_cast<float*>(r.ema);
   const bool al_p = aligned16(p), al_g = aligned16(g), al_m = aligned16(m), al_v = aligned16(v), al_e = aligned16(e);
-  const dcf_optim_group h = hs.g[__builtin_amdgcn_readfirstlane(r.group) & (DCF_OPTIM_MAX_GROUPS - 1)];   // uniform: read from the kernel arguments
+  const dcf_optim_group h = group_of();
   const float coef = coef_dev ? *coef_dev : 1.f;
   const long long base = ((long long)blockIdx.x - r.chunk0) * DCF_OPTIM_CHUNK;
 #pragma unroll
@@ -181,6 +175,24 @@ __device__ __forceinline__ void optim_adam_chunk(OptimTable tb, const OptimGroup
       store4(e, i, r.n, al_e, xe);
     }
   }
+}
+
+// The Adam / AdamW update of the workgroup's chunk, with the EMA copy when EMA.  GATED (the guarded export): `gate` points to one
+// device word, the same for the whole grid; a non-zero word means return before anything is written.  Its load is issued with the
+// chunk map's and waited for only after the row is there, so the gate costs one scalar load and no latency of its own.
+template <bool EMA, bool GATED = false>
+__device__ __forceinline__ void optim_adam_chunk(OptimTable tb, const OptimGroups& hs, const float* __restrict__ coef_dev, float beta,
+                                                 const int32_t* __restrict__ gate = nullptr) {
+  const int32_t closed = GATED ? *gate : 0;
+  const dcf_optim_row r = tb.rows[__builtin_amdgcn_readfirstlane(tb.chunk_map[blockIdx.x])];
+  const bool has_g = !(r.flags & DCF_OPTIM_NO_GRAD);
+  const bool has_e = EMA && r.ema != nullptr;
+  if (GATED && closed != 0) return;
+  if (!has_g && !has_e) return;
+  optim_adam_sweeps<EMA>(
+      r, has_g, has_e,
+      [&] { return hs.g[__builtin_amdgcn_readfirstlane(r.group) & (DCF_OPTIM_MAX_GROUPS - 1)]; },   // uniform: read from the kernel arguments
+      coef_dev, beta);
 }
 
 // the argument checks every table export starts with; -1 with the message set

@@ -3,6 +3,7 @@
     clip_grad_norm_ -> dcf_optim_grad_norm (+ dcf_optim_scale stand-alone, or the coefficient folded into the update)
     StepGuard       -> dcf_guard_grad_norm / dcf_guard_adam_step: the same two launches, skipped on the device if a gradient is non-finite
     AdamW.step()    -> dcf_optim_adam_step: one launch over every parameter tensor, the decay / no-decay groups by value
+    device_count    -> dcf_clock_adam_step: the same launch with Adam's step counts and bias corrections read on the device
     _ema_update()   -> the same launch (``attach_ema``)
     scheduler       -> LinearWarmupMultiStepLR / LinearWarmupCosineAnnealingLR: host arithmetic in double, a closed form per step
 
@@ -182,6 +183,34 @@ class StepGuard:
                 'first_bad': first, 'n_bad_rows': int(rec['n_bad_rows']), 'conv_flag': int(rec['conv_flag']), 'verdict': int(rec['verdict'])}
 
 
+def bias_correction_table(b1, b2, max_len=_lib.CLOCK_MAX_TABLE):
+    """The bias corrections of Adam for the step counts t = 1, 2, ... as a float32 array (n, 2): row t - 1 holds 1 - b1^t and
+    sqrt(1 - b2^t), computed in double exactly as ``AdamW._group_array`` computes the pair it passes by value, then rounded to fp32
+    as a C float assignment rounds.  The last row is the first whose two floats are both 1.0: from there on the corrections do not
+    change, and dcf_clock_adam_step (include/decafnet_hip_clock.h) takes 1.0 for every count past the end.  Betas so close to 1 that
+    this takes more than ``max_len`` rows are refused."""
+    b1, b2 = float(b1), float(b2)
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f'bias_correction_table: betas ({b1}, {b2}) must lie in [0, 1)')
+    # 1 - x rounds to 1.0f once x <= 2^-25, sqrt(1 - x) no later: the length is about 25 ln 2 / -ln b.  Estimated first, so that a
+    # hopeless pair is refused at once and not after max_len powers.
+    b = max(b1, b2)
+    too_long = ValueError(f'betas ({b1}, {b2}): the bias corrections reach 1.0 in fp32 only after more than {max_len} steps; '
+                          f'device_count=True keeps a table of them and takes at most that many')
+    if b > 0.0 and 25.0 * math.log(2.0) / -math.log(b) > 1.01 * max_len:
+        raise too_long
+    one = np.float32(1.0)
+    rows, t = [], 0
+    while True:
+        t += 1
+        if t > max_len:
+            raise too_long
+        pair = (np.float32(1.0 - b1 ** t), np.float32(math.sqrt(1.0 - b2 ** t)))
+        rows.append(pair)
+        if pair[0] == one and pair[1] == one:
+            return np.array(rows, dtype=np.float32).reshape(-1, 2)
+
+
 def grad_norm_and_coef(parameters, max_norm, _table=None, guard=None):
     """(total L2 norm of the gradients, min(1, max_norm / (norm + 1e-6))) as two 0-d device tensors, for the fused path:
     ``optimizer.step(clip_coef=coef)`` folds the coefficient into the update and leaves ``p.grad`` unscaled.  max_norm <= 0 or None
@@ -226,11 +255,24 @@ class AdamW(torch.optim.Optimizer):
     ``step(guard=g)``: the launch obeys the verdict of the ``StepGuard``'s last ``grad_norm_and_coef(..., guard=g)``: on a skip it
     writes no byte of any parameter, moment or EMA tensor.  The host cannot know the verdict, so ``state[p]['step']`` advances
     either way: the bias corrections follow the attempted steps.
+
+    ``device_count=True`` (include/decafnet_hip_clock.h, dcf_clock_adam_step) moves the step counts to the GPU: one int64 tensor holds
+    the count of every parameter of every group in table order, made at the first step and laid out again when a group is added.  The
+    launch reads a row's count t - 1, takes 1 - b1^t and sqrt(1 - b2^t) from a table that ``bias_correction_table`` built on the host
+    from the very doubles the default path rounds (one table per distinct betas, uploaded once), and a second tiny kernel advances the
+    counts of the rows that had a gradient -- under a guard only where the update was applied, so the corrections follow APPLIED
+    steps as with ``torch.cuda.amp.GradScaler``.  Finite gradients give the bits of the default path.  ``state[p]['step']`` is not
+    read by ``step()`` and goes stale between checkpoints; ``state_dict()`` reads the counts back (a host read, like the checkpoint
+    itself) and hands out torch's format, ``load_state_dict()`` uploads them: a state dict moves freely between the two settings
+    and torch.optim.AdamW.  Every parameter may have a count of its own: the limit of 8 (group, count) pairs per launch is gone, the
+    limit of 8 parameter groups stays.  ``False`` -- the default -- launches exactly what it launched before the option existed.
     Parameters are fp32, contiguous and, when ``step`` runs, on the GPU."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, mode='adamw'):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, mode='adamw', device_count=False):
         if mode not in _lib.OPTIM_MODES:
             raise ValueError(f"mode must be 'adamw' or 'adam' (got {mode!r})")
+        if not isinstance(device_count, bool):
+            raise ValueError(f'device_count = {device_count!r} (True or False)')
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not all(0.0 <= b < 1.0 for b in betas):
             raise ValueError(f'invalid hyper-parameters: lr {lr}, betas {betas}, eps {eps}, weight_decay {weight_decay}')
         # torch's own group keys (torch/optim/adam.py), so that a state dict is interchangeable; the switches this class does not
@@ -240,6 +282,11 @@ class AdamW(torch.optim.Optimizer):
         self._table = _Table()
         self._ema, self._ema_beta = {}, None
         self._decoupled = mode == 'adamw'            # for groups loaded from a state dict that lacks torch's decoupled_weight_decay key
+        # device_count: the counts on the device in the order of `_layout` (None: not laid out yet; `_host_counts` {parameter: count}
+        # then holds what was loaded or read back last), the uploaded tables by betas, and the launch's two host arrays
+        self.device_count = device_count
+        self._steps = self._layout = None
+        self._host_counts, self._bc, self._bc_args = {}, {}, (None, None, None)
         super().__init__(params, defaults)
 
     def add_param_group(self, param_group):
@@ -314,6 +361,39 @@ class AdamW(torch.optim.Optimizer):
             h.mode = _lib.OPTIM_MODES['adamw' if group.get('decoupled_weight_decay', self._decoupled) else 'adam']
         return arr
 
+    # ---- device_count=True: the counts and the bias-correction tables on the device
+    def _counts_on_host(self):
+        """-> {parameter: count}.  Reads the device counts back if there are any (a host read: it waits for the stream)."""
+        if self._steps is not None:
+            self._host_counts = dict(zip(self._layout, self._steps.cpu().tolist()))
+        return self._host_counts
+
+    def _lay_counts(self, flat, device):
+        """the int64 count tensor for the parameters `flat` (table order) on `device`: the known counts, 0 for a new parameter;
+        uploaded stream-ordered from pinned memory"""
+        known = self._counts_on_host()
+        host = torch.tensor([int(known.get(p, 0)) for p in flat], dtype=torch.int64)
+        with torch.cuda.device(device):
+            self._steps = host.pin_memory().to(device, non_blocking=True)
+        self._layout = list(flat)
+
+    def _clock_args(self, device):
+        """(groups, bc_tables, bc_len) of dcf_clock_adam_step: one record and one table per PARAMETER group"""
+        n = len(self.param_groups)
+        if n > _lib.OPTIM_MAX_GROUPS:
+            raise NotImplementedError(f'{n} parameter groups; one launch takes {_lib.OPTIM_MAX_GROUPS}')
+        groups = self._group_array({(g, 1): g for g in range(n)})       # bc1 / sqrt_bc2 of these records are ignored by the export
+        betas = tuple((float(g['betas'][0]), float(g['betas'][1]), device) for g in self.param_groups)
+        if self._bc_args[0] != betas:
+            for key in betas:
+                if key not in self._bc:
+                    tab = bias_correction_table(key[0], key[1])
+                    with torch.cuda.device(device):
+                        self._bc[key] = (torch.from_numpy(tab.reshape(-1).copy()).pin_memory().to(device, non_blocking=True), len(tab))
+            self._bc_args = (betas, (ctypes.c_void_p * n)(*[self._bc[k][0].data_ptr() for k in betas]),
+                             (ctypes.c_int32 * n)(*[self._bc[k][1] for k in betas]))
+        return groups, self._bc_args[1], self._bc_args[2]
+
     @torch.no_grad()
     def step(self, closure=None, clip_coef=None, guard=None):
         if closure is not None:
@@ -324,8 +404,11 @@ class AdamW(torch.optim.Optimizer):
         f32, state, ema_of = torch.float32, self.state, self._ema
         cp, cg, cm, cv, ce, cn, ck, cf = [], [], [], [], [], [], [], []
         keys, device, counts, written = {}, None, [], []
+        on_device, flat = self.device_count, []
         for g, group in enumerate(self.param_groups):
             for i, p in enumerate(group['params']):
+                if on_device:
+                    flat.append(p)
                 if device is None:
                     _need_gpu(p, self._name(g, i, p))
                     device = p.device
@@ -347,11 +430,15 @@ class AdamW(torch.optim.Optimizer):
                     for t, what in ((grad, 'the gradient'), (m, 'exp_avg'), (v, 'exp_avg_sq')):
                         if t.dtype is not f32 or t.device != device or t.shape != p.shape or not t.is_contiguous():
                             self._bad(g, i, p, t, what, device)
-                    t = float(st['step']) + 1
-                    counts.append((st, t))                       # committed below, once nothing can raise any more
                     written.append(p)
                     cg.append(grad.data_ptr()), cm.append(m.data_ptr()), cv.append(v.data_ptr()), cf.append(0)
-                    ck.append(keys.setdefault((g, t), len(keys)))
+                    if on_device:                                # the count is the device's: the row names its parameter group alone
+                        counts.append((st, None))
+                        ck.append(g)
+                    else:
+                        t = float(st['step']) + 1
+                        counts.append((st, t))                   # committed below, once nothing can raise any more
+                        ck.append(keys.setdefault((g, t), len(keys)))
                 e = ema_of.get(p) if ema_of else None
                 if e is None:
                     ce.append(0)
@@ -362,7 +449,10 @@ class AdamW(torch.optim.Optimizer):
                     written.append(e)
         if device is None:
             return None
-        groups = self._group_array(keys)
+        if on_device:
+            groups, bc_tables, bc_len = self._clock_args(device)
+        else:
+            groups = self._group_array(keys)
         rec = np.zeros(len(cp), dtype=_ROW)
         for name, col in (('p', cp), ('g', cg), ('exp_avg', cm), ('exp_avg_sq', cv), ('ema', ce), ('n', cn), ('group', ck), ('flags', cf)):
             rec[name] = col
@@ -372,8 +462,17 @@ class AdamW(torch.optim.Optimizer):
                 raise ValueError(f'clip_coef: one float32 on {device} is expected')
         self._table.update(rec, device)
         ema = (int(bool(self._ema)), float(self._ema_beta or 0.0))
+        if on_device and (self._steps is None or self._steps.device != device or len(flat) != len(self._layout)
+                          or not all(a is b for a, b in zip(flat, self._layout))):
+            self._lay_counts(flat, device)
         with torch.cuda.device(device):
-            if guard is None:
+            if on_device:                                        # the counts advance on the device, where the update is applied
+                _lib.check(_lib.lib().dcf_clock_adam_step(*self._table.args(), ctypes.cast(groups, ctypes.c_void_p), len(self.param_groups),
+                                                          ctypes.cast(bc_tables, ctypes.c_void_p), ctypes.cast(bc_len, ctypes.c_void_p),
+                                                          _lib.ptr(self._steps), _lib.ptr(clip_coef),
+                                                          None if guard is None else guard._on(device), *ema, _lib.current_stream()),
+                           'dcf_clock_adam_step')
+            elif guard is None:
                 _lib.check(_lib.lib().dcf_optim_adam_step(*self._table.args(), ctypes.cast(groups, ctypes.c_void_p), len(keys),
                                                           _lib.ptr(clip_coef), *ema, _lib.current_stream()), 'dcf_optim_adam_step')
             else:                                                # the verdict of the guard's last norm decides on the device
@@ -381,13 +480,19 @@ class AdamW(torch.optim.Optimizer):
                                                           _lib.ptr(clip_coef), guard._on(device), *ema, _lib.current_stream()),
                            'dcf_guard_adam_step')
         for st, t in counts:                                     # the update is enqueued: now the counts advance
-            st['step'] = t
+            if t is not None:
+                st['step'] = t
             written.append(st['exp_avg']), written.append(st['exp_avg_sq'])
         _mark_written(written)
         return None
 
     def state_dict(self):
         """torch's format: state[i] = {step (a one-element fp32 tensor on the CPU, as torch.optim.AdamW keeps it), exp_avg, exp_avg_sq}"""
+        if self.device_count:                                    # the one host read: state[p]['step'] is brought up to date here alone
+            known = self._counts_on_host()
+            for p, st in self.state.items():
+                if st:
+                    st['step'] = float(known.get(p, 0))
         sd = super().state_dict()
         sd['state'] = {k: {**v, 'step': v['step'] if torch.is_tensor(v['step']) else torch.tensor(float(v['step']), dtype=torch.float32)}
                        for k, v in sd['state'].items()}
@@ -398,6 +503,12 @@ class AdamW(torch.optim.Optimizer):
         for st in self.state.values():
             if 'step' in st:
                 st['step'] = float(st['step'])
+        if self.device_count:                                    # the loaded counts replace the device's, for every parameter
+            self._steps = self._layout = None
+            self._host_counts = {p: int(st['step']) for p, st in self.state.items() if 'step' in st}
+            flat = [p for g in self.param_groups for p in g['params']]
+            if flat and flat[0].is_cuda:                         # else the first step uploads them
+                self._lay_counts(flat, flat[0].device)
 
 
 class ModelEma:
@@ -467,8 +578,9 @@ def split_decay(model):
     return sorted(decay), sorted(no_decay)
 
 
-def make_optimizer(model, opt):
-    """libs/modeling/optim.py:66-239 for ``opt = opt['optimizer']``: {name: 'adamw' | 'adam', lr, weight_decay}"""
+def make_optimizer(model, opt, device_count=False):
+    """libs/modeling/optim.py:66-239 for ``opt = opt['optimizer']``: {name: 'adamw' | 'adam', lr, weight_decay}.  ``device_count``:
+    the option of ``AdamW`` -- the step counts on the GPU."""
     name = opt['name']
     if name not in ('adamw', 'adam'):
         raise NotImplementedError(f"optimizer {name!r} is not implemented ('adamw' and 'adam' are)" if name == 'sgd'
@@ -479,7 +591,7 @@ def make_optimizer(model, opt):
         _check_tensor(named[n], f'parameter {n!r}')
     groups = [{'params': [named[n] for n in decay], 'weight_decay': opt['weight_decay'], 'lr': opt['lr']},
               {'params': [named[n] for n in no_decay], 'weight_decay': 0.0, 'lr': opt['lr']}]
-    return AdamW(groups, lr=opt['lr'], betas=(0.9, 0.999), weight_decay=opt.get('weight_decay', 0), mode=name)
+    return AdamW(groups, lr=opt['lr'], betas=(0.9, 0.999), weight_decay=opt.get('weight_decay', 0), mode=name, device_count=device_count)
 
 
 class _ClosedFormLR(torch.optim.lr_scheduler.LRScheduler):

@@ -28,6 +28,15 @@ warm-up, and nothing accumulates, since the moments themselves are untouched.  W
 bits of the unguarded one.  ``guard.report(names)`` is the one host read (applied, skipped,
 the last skipped attempt, the first offending parameter); ``state()`` carries the two counters under 'guard'.
 
+Adam's count on the device.  ``TrainStep(..., device_count=True)`` removes that departure: the optimizer keeps the step count of
+every parameter in device memory (``optim.AdamW(device_count=True)``, include/decafnet_hip_clock.h), the update reads it there and a
+second tiny kernel advances it -- under the guard only when the step was applied.  After a skip the next update then has the bias
+corrections of the count that was actually reached, as with ``GradScaler``.  The option works with or without ``skip_nonfinite``;
+on finite batches it computes the bits of the default step.  ``scheduler.step()``, ``itr`` and the loss-norm update still follow
+ATTEMPTS, which is what a torch loop with ``GradScaler`` does too (``scaler.step`` may skip the optimizer, the loop still calls
+``scheduler.step()``).  ``state()`` / ``load_state()`` need no new key: the counts travel in the optimizer's state dict, in torch's
+format, and a checkpoint moves freely between the two settings.
+
 Not here: data loading, logging, AMP, graph capture of the step, SGD, gradient compression, the detection of
 parameters that no rank used.
 
@@ -138,16 +147,21 @@ class TrainStep:
     is what the Trainer takes from its data loader (worker_v2.py:252).  The model is on the GPU.  ``front_end``: 'dense' or 'shared',
     handed to ``training_forward`` (a ``scat`` model takes the shared path either way).  ``skip_nonfinite=True``: the step owns an
     ``optim.StepGuard`` (``self.guard``), armed around forward, backward and update; a step whose gradients are not all finite is
-    skipped on the GPU (module docstring).  ``False`` -- the default -- launches exactly what it launched before the option existed."""
+    skipped on the GPU (module docstring).  ``False`` -- the default -- launches exactly what it launched before the option existed.
+    ``device_count=True``: Adam's step counts live on the GPU and advance on applied steps only (module docstring); the scheduler,
+    ``itr`` and the loss-norm update still follow attempts.  ``False`` -- the default -- changes nothing."""
 
-    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1, front_end='dense', skip_nonfinite=False):
+    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1, front_end='dense', skip_nonfinite=False, device_count=False):
         if front_end not in FRONT_ENDS:
             raise ValueError(f'TrainStep: front_end = {front_end!r} (one of {FRONT_ENDS})')
         if not isinstance(skip_nonfinite, bool):
             raise ValueError(f'TrainStep: skip_nonfinite = {skip_nonfinite!r} (True or False)')
+        if not isinstance(device_count, bool):
+            raise ValueError(f'TrainStep: device_count = {device_count!r} (True or False)')
         self.model, self.opt, self.front_end, self.skip_nonfinite = model, opt, front_end, skip_nonfinite
+        self.device_count = device_count
         self.objective = L.PointObjective(opt, world_size=world_size)
-        self.optimizer = O.make_optimizer(model, opt['optimizer'])
+        self.optimizer = O.make_optimizer(model, opt['optimizer'], device_count=device_count)
         sched = copy.deepcopy(dict(opt['scheduler']))                       # opt.py:467-468, worker_v2.py:252, on a copy
         sched.update({k: opt['train'][k] for k in ('epochs', 'warmup_epochs') if k in opt['train']}, itrs_per_epoch=int(itrs_per_epoch))
         self.scheduler = O.make_scheduler(self.optimizer, sched)
@@ -280,14 +294,16 @@ class DataParallelTrainStep(TrainStep):
     sits in a gradient of that rank and so in the average, except where a later mask multiplies it away -- then that rank alone would
     skip and the ranks would part.  Equal ``skipped`` counts in ``guard.report()`` of all ranks show that it has not happened.
 
+    ``device_count=True``: as in ``TrainStep``; every rank keeps its own counts, which agree as long as the verdicts do.
+
     Backends: nccl (RCCL), one GPU per rank; gloo stages every bucket through the host and is a flow check for a one-GPU box."""
 
     def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES, front_end='dense',
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, device_count=False):
         self.group = process_group
         self.world, self._backend = D._group_info(process_group)
         super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch, front_end=front_end,
-                         skip_nonfinite=skip_nonfinite)
+                         skip_nonfinite=skip_nonfinite, device_count=device_count)
         D.broadcast_module(model, 0, process_group)
         D.broadcast_module(self.ema.module, 0, process_group)
         self.reducer = D.GradReducer(self._params, process_group, bucket_bytes)
