@@ -106,7 +106,8 @@ __global__ __launch_bounds__(256) void k_xattn_valu(XAttnArgs p) {
 //   as 64-byte pieces), O goes registers -> global as float4 (4 consecutive channels per lane).
 // Arithmetic: v_mfma_f32_16x16x16_f16 on x = hi + lo (two fp16 values, 22 significant bits; below |x| = 2^-14 the
 // absolute representation error is <= 2^-25), products hi*lo + lo*hi + hi*hi accumulated in fp32 -- the operand split of
-// the dense convolutions (gemm_bf16s.hip) without its scaling: q, k are O(1) after the d^-1/4 scale, p is in [0, 1].
+// the dense convolutions (gemm_bf16s.hip) without its scaling: q, k are O(1) after the d^-1/4 scale, p is in [0, 1]; v alone
+// gets a power-of-two plane scale when it is small (max |v| < 2^-2 over the workgroup's keys, see the staging below).
 // Measured error against the fp32 reference: that of an fp32 FMA chain (tests/test_gpu_ops.py: 1e-5 at E = 1024).
 // Why not the exact fp32 MFMA (v_mfma_f32_16x16x4_f32, the round-1 kernel): it retires 4 k per 32 cycles -- 64 of them per
 // 16 rows x 64 channels x 33 keys = 2 048 cycles for 8 KiB of q / ctx traffic, 30 us of pure MFMA issue per SIMD at
@@ -191,6 +192,33 @@ __global__ __launch_bounds__(256) void k_xattn_mfma(XAttnArgs p) {
   // the first row groups' q are requested BEFORE the K / V staging: the staging's own round trips then overlap them
 #pragma unroll
   for (int a = 0; a < QA; ++a) fetch_q(blockIdx.x + a * gridDim.x, qn_[a]);
+  // The planes of V carry a power-of-two scale vs, taken from max |v| over this (query, head)'s MFMA keys and taken out of the context
+  // accumulator again.  q, k and p feed or leave a softmax and stay unscaled; the representation error of v reaches the output
+  // undamped, and below |v| = 2^-14 unscaled planes have an absolute floor of 2^-25.  max |v| >= 2^-2 (masked keys count):
+  // vs = 1, the unscaled planes and their bits.  Below that vs lifts max |v| into [8, 16), the activation scale of the GEMMs.
+  // Cost: a second read of the V slice (the staging below finds it in cache) and two barriers per workgroup.
+  float vs = 1.f, vinv = 1.f;
+  if constexpr (NKT > 0) {
+    // the word sits behind everything else in the dynamic LDS (the launcher adds its 16 bytes): a static __shared__ variable would be
+    // placed in front and move the planes off their 8- / 16-byte alignment (measured: 64 -> 187 us at BASELINE config 2)
+    unsigned& vmax_s = *reinterpret_cast<unsigned*>(Os + (OSTAGE ? 4 * 16 * D * (int)sizeof(float) : 0));
+    if (tid == 0) vmax_s = 0u;
+    __syncthreads();
+    const int nk = Lk < KT16 ? Lk : KT16;
+    float vm = 0.f;
+    for (int i = tid; i < nk * (D / 4); i += 256) {
+      const f32x4 vv = *reinterpret_cast<const f32x4*>(p.V + ((size_t)b * Lk + i / (D / 4)) * C + (size_t)head * D + (i % (D / 4)) * 4);
+      vm = fmaxf(vm, fmaxf(fmaxf(fabsf(vv.x), fabsf(vv.y)), fmaxf(fabsf(vv.z), fabsf(vv.w))));   // (a NaN is dropped: track() reports it)
+    }
+    atomicMax(&vmax_s, __float_as_uint(vm));       // non-negative floats order as their bits
+    __syncthreads();
+    const float vmax = __uint_as_float(vmax_s);
+    if (vmax < 0.25f && vmax >= 0x1p-100f) {       // (smaller still: nothing a power of two in fp32 range could lift)
+      const int e = (int)(__float_as_uint(vmax) >> 23) - 127;
+      vs = __uint_as_float((unsigned)(127 + 3 - e) << 23);
+      vinv = __uint_as_float((unsigned)(127 - 3 + e) << 23);
+    }
+  }
   for (int i = tid; i < (KT16 + REM) * (D / 4); i += 256) {
     const int key = i / (D / 4), c4 = i % (D / 4);
     f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
@@ -205,7 +233,7 @@ __global__ __launch_bounds__(256) void k_xattn_mfma(XAttnArgs p) {
       split4(kv, hi, lo);
       *reinterpret_cast<xh4*>(Kh + key * KP + c4 * 4) = hi;
       *reinterpret_cast<xh4*>(Kl + key * KP + c4 * 4) = lo;
-      split4(vv, hi, lo);
+      split4(vv * vs, hi, lo);
 #pragma unroll
       for (int e = 0; e < 4; ++e) { Vh[(c4 * 4 + e) * VP + key] = hi[e]; Vl[(c4 * 4 + e) * VP + key] = lo[e]; }
     } else {
@@ -312,6 +340,10 @@ __global__ __launch_bounds__(256) void k_xattn_mfma(XAttnArgs p) {
         const xh4 vl = *reinterpret_cast<const xh4*>(Vl + (16 * ct + r) * VP + 16 * kt + 4 * g);
 #pragma unroll
         for (int t = 0; t < QT; ++t) o[t] = single ? __builtin_amdgcn_mfma_f32_16x16x16f16(vh, ph[t][kt], o[t], 0, 0, 0) : mma3(vh, vl, ph[t][kt], pl[t][kt], o[t]);
+      }
+      if constexpr (NKT > 0) {
+#pragma unroll
+        for (int t = 0; t < QT; ++t) o[t] *= vinv;      // out of the planes' scale before the fp32 trailing keys come in
       }
 #pragma unroll
       for (int j = 0; j < REM; ++j) {
@@ -548,7 +580,7 @@ static int launch_xattn_mfma(const XAttnArgs& a, hipStream_t st) {
   // two fp16 planes of K [16 nkt][D + 4] and of V^T [D][16 nkt + 4], fp32 rows of the trailing keys (K and V), the key mask
   // (+ the staged context tile of the d = 64 / 128 instantiations: [4 waves][16 rows][D] fp32 behind the mask, 16-byte aligned)
   const size_t lds = (size_t)2 * 2 * (16 * nkt * (D + 4) + D * (16 * nkt + 4)) + ((size_t)2 * (rem > 0 ? rem : 1) * D + ((16 * nkt + rem + 3) & ~3)) * sizeof(float) +
-                     ((D16 == 4 || D16 == 8) ? (size_t)4 * 16 * D * sizeof(float) : 0);
+                     ((D16 == 4 || D16 == 8) ? (size_t)4 * 16 * D * sizeof(float) : 0) + 16;      // + the max |v| word (16-byte slot)
   DCF_CHECK(lds <= 160 * 1024, "xattn: K / V planes of %d keys x %d channels (+ the staged context tile) need %zu bytes of LDS (> 160 KiB)", a.Lk, D, lds);
   // (above the 64 KiB a launch gets by default the kernel's limit is raised first: d = 128 with the staged context tile, d = 256)
 #define XL(NKT_, REM_) do { \

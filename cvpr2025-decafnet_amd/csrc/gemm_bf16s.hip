@@ -46,7 +46,10 @@ constexpr int ROWB = 80;           // bytes per (plane, row): 64 data + 16 pad
 // feature files use 1, i.e. |a| < 65504), weights by 2^8 -- and the accumulators un-scaled by 2^-12
 // in the epilogue: |a| < 4094 and |w| < 255.9 convert without overflow, the low planes stay normal fp16 numbers for
 // |a| >= 2^-7 / |w| >= 2^-11, and below that the absolute representation error is <= 2^-29 / 2^-33 (an fp32 ulp of 1.0
-// is 2^-23).  Out-of-range operands give inf/NaN accumulators: the epilogue raises the sticky status word the caller
+// is 2^-23; the a_scale = 1 launches: |a| < 65504, normal low planes from 2^-3 and a floor of 2^-25).  fp16 subnormals survive
+// the convert and the matrix cores: below the envelope the kernels equal the exact-plane emulation within the error of an fp32
+// chain (tests/f16x3_ref.py; tests/test_operand_range_cpu.py pins these numbers, tests/test_gpu_operand_range.py the kernels;
+// measured ratios in profiles/operand_range.md).  Out-of-range operands give inf/NaN accumulators: the epilogue raises the sticky status word the caller
 // passes in GemmArgs::status instead of letting a later ReLU / max swallow them.  Weights are range-checked once when
 // they are split (the model falls back to bf16x6 if they do not fit).
 constexpr int T_F16 = 16;          // `nterms` code of this mode (6 and 3 are the bf16 modes)

@@ -391,7 +391,11 @@ int64_t dcf_profile_report(char* buf, int64_t cap);
  * act: 0 none, 1 exact GELU, 2 ReLU. */
 int dcf_op_linear(const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N, int32_t K,
                   int32_t act, void* stream);
-/* same through the bf16-split MFMA GEMM (gemm_bf16s.hip); nterms = 6 (fp32 accurate) or 3 */
+/* same through the split-operand MFMA GEMM (gemm_bf16s.hip); nterms = 16 (f16x3, the forward's default) or 6 (bf16x6).
+ * Operand envelope of f16x3 (planes scaled by 2^4 / 2^8): 22-bit operands for 2^-7 <= |a| < 4094 and 2^-11 <= |w| < 255.9; below that
+ * an absolute representation floor of 2^-29 (a) / 2^-33 (w), fp16 subnormals kept; beyond it non-finite results and the sticky
+ * numerics word where the caller has one.  bf16x6 has fp32's exponent range and commutes with a power of two on A bit for bit.
+ * Pinned by tests/test_operand_range_cpu.py (the numbers) and tests/test_gpu_operand_range.py (the kernels). */
 int dcf_op_linear_split(const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N, int32_t K,
                         int32_t act, int32_t nterms, void* stream);
 /* same with A given channel-major (K, M) -- the reference's (C, T) layout */
@@ -423,7 +427,9 @@ int dcf_op_linear_ln_carry(const float* A, const float* W1, const float* b1, con
 int dcf_op_ffn(const float* X, const float* ln_w, const float* ln_b, const float* W1, const float* b1, const float* W2, const float* b2,
                const float* ls, const uint8_t* mask, float* C, float* stats_out, int32_t M, int32_t E, int32_t chain, void* stream);
 
-/* same product on the bf16-split matrix-core path (how vid_map runs); needs M % 4 == 0, N % 128 == 0, K % 32 == 0 */
+/* same product on the split-operand matrix-core path (how vid_map runs); needs M % 4 == 0, N % 128 == 0, K % 32 == 0.  The operand
+ * envelope of dcf_op_linear_split (activation scale 2^4).  Inside the forward this product runs on UNSCALED planes of the raw
+ * features: |feature| < 65504, 22 bits from 2^-3 on, an absolute floor of 2^-25 below (the input envelope). */
 int dcf_op_linear_cm_split(const float* A_cm, const float* W, const float* bias, float* C, int32_t M, int32_t N, int32_t K,
                            int32_t nterms, void* stream);
 /* A prediction head (libs/modeling/head.py:53-64 ClsHead, :95-103 RegHead) on B sequences of T token-major rows (B*T, C):
@@ -439,7 +445,7 @@ int dcf_op_head(const float* X, const uint8_t* mask, const float* W1, const floa
 int dcf_op_conv3(const float* X, const uint8_t* mask, const float* W_ock, float* Y, int32_t B, int32_t T, int32_t Cin,
                  int32_t N, void* stream);
 /* the same convolution on the split-operand matrix-core path the forward uses (nterms 16 = f16x3, 6 = bf16x6); Cin % 32 == 0.
- * ABI version 4. */
+ * The operand envelope of dcf_op_linear_split.  ABI version 4. */
 int dcf_op_conv3_split(const float* X, const uint8_t* mask, const float* W_ock, float* Y, int32_t B, int32_t T, int32_t Cin,
                        int32_t N, int32_t nterms, void* stream);
 /* channel LayerNorm (libs/modeling/blocks.py:125-131) per row; w/b may be NULL. */
@@ -487,7 +493,11 @@ int dcf_op_conv5s2_bwd_data(const float* dY, const uint8_t* mask, const float* W
                             int32_t N, void* stream);
 int dcf_op_conv5s2_bwd_weight(const float* X, const uint8_t* mask, const float* dY, float* dW_ock, int32_t B, int32_t T, int32_t Cin,
                               int32_t N, int32_t accumulate, void* stream);
-/* cross-attention core (libs/modeling/blocks.py:374-389): Q (B*T, C), K/V (B*Lk, C), kvmask (B*Lk) -> O (B*T, C) */
+/* cross-attention core (libs/modeling/blocks.py:374-389): Q (B*T, C), K/V (B*Lk, C), kvmask (B*Lk) -> O (B*T, C).  Two fp16 planes
+ * per operand: |x| <= 65504.  q d^-1/4, k d^-1/4 and the probabilities are unscaled (22 bits from 2^-3 on, an absolute floor of
+ * 2^-25 below): they feed or leave a softmax.  The floor of v would reach the output, so where max |v| over the MFMA keys of a
+ * (batch, head) is below 2^-2 its planes carry the power of two that lifts that maximum into [8, 16) (floor: 2^-28 max |v|);
+ * a larger v runs on unscaled planes. */
 int dcf_op_xattn(const float* Q, const float* K, const float* V, const uint8_t* kvmask, float* O, int32_t B, int32_t T,
                  int32_t Lk, int32_t C, int32_t heads, void* stream);
 /* sliding-window attention core (blocks.py:204-325,357-373): Q/K/V (B*T, C), mask (B*T) -> O; window = 0: global attention over

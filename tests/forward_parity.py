@@ -85,14 +85,19 @@ def pool(parts, select=None):
     return torch.cat([t.double().reshape(-1) for t in flat])
 
 
-def check(tag, got, y64, y32):
-    """the rule on one pooled output kind; prints the FWERR line, asserts, returns e_gpu / bound"""
+def rule(got, y64, y32):
+    """the rule's figures for one pooled output kind, nothing asserted: (max |y64|, e_ref, e_gpu, bound, e_gpu / bound)"""
     got, y64, y32 = got.detach().cpu().double(), y64.detach().double(), y32.detach().double()
-    assert got.shape == y64.shape == y32.shape, (tag, got.shape, y64.shape, y32.shape)
-    assert bool(torch.isfinite(got).all()), tag
     e_ref, e_gpu, top = float((y32 - y64).abs().max()), float((got - y64).abs().max()), float(y64.abs().max())
     bound = max(4 * e_ref, FLOOR * top)
-    ratio = e_gpu / bound if bound else 0.0
+    return top, e_ref, e_gpu, bound, (e_gpu / bound if bound else 0.0)
+
+
+def check(tag, got, y64, y32):
+    """the rule on one pooled output kind; prints the FWERR line, asserts, returns e_gpu / bound"""
+    assert got.shape == y64.shape == y32.shape, (tag, got.shape, y64.shape, y32.shape)
+    assert bool(torch.isfinite(got).all()), tag
+    top, e_ref, e_gpu, bound, ratio = rule(got, y64, y32)
     print(f'FWERR {tag}: max|y64| {top:.3e} e_ref {e_ref:.3e} e_gpu {e_gpu:.3e} bound {bound:.3e} ratio {ratio:.3f}')
     assert e_gpu <= bound, (tag, e_gpu, bound)
     return ratio
