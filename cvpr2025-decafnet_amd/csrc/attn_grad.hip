@@ -13,7 +13,7 @@
 //                   Pass 2 walks the K rows again: p = exp(s - m) / l, dS, dQ.  Windows of at most 9 / 19 keys are unrolled with the
 //                   scores and dP kept in registers and the rows requested two keys ahead; wider windows loop and recompute.
 //   k_attn_bwd_kv : a wave per KEY row j: a gather over the at most `window` queries whose band holds j -- q_t, dO_t and the three
-//                   statistics of row t, the same score and dP expressions (bit for bit: dotp below pins the contraction), dK and dV
+//                   statistics of row t, the same score and dP expressions (bit for bit: dotp of grad_common.h pins the contraction), dK and dV
 //                   accumulated in registers in ascending t and written once.  No atomics, one fixed summation order.
 // delta is formed from p and dP (not from a stored O): with one key in the window p = 1 and delta = dP exactly, hence dS = 0 exactly.
 // m and 1 / l are kept apart (not as one log-sum-exp): exp(s - m) / l is the forward's own p, without the rounding of m + log l.
@@ -22,7 +22,7 @@
 // vector-memory path and do ~10 flops per loaded float: like the forward they are bound by that path, not by the ALU.
 #include "attn_grad.h"
 
-#include "common.h"
+#include "grad_common.h"
 
 namespace dcf {
 
@@ -30,26 +30,6 @@ template <int LPH>
 __device__ __forceinline__ float ag_head_sum(float v) {
   if constexpr (LPH == 1) return v;
   else return group_sum<LPH>(v);
-}
-
-// the 4-channel partial of a dot product with its contraction written out, so that the query-side and the key-side kernel get the
-// same bits for the same operands whatever the compiler would have fused
-__device__ __forceinline__ float dotp(const f32x4& a, const f32x4& b) {
-  return __builtin_fmaf(a.x, b.x, a.y * b.y) + __builtin_fmaf(a.z, b.z, a.w * b.w);
-}
-
-// exp(x), x <= 0 (or barely above): v_exp_f32 of the rounded product x * log2(e), times 1 + ln 2 * (what the rounding of the product
-// and of the constant dropped).  The forward's one-instruction form has a relative error of |x| 2^-24; the gradient rule leaves
-// ~2^-20 of the largest element for everything, and dS = p (dP - delta) is a difference, so the residual is carried (3 more
-// vector instructions per score and head).  Scores below -1e5 (the -1e4 of a padded key among them: 0 either way) are clamped so that
-// the product stays finite.
-__device__ __forceinline__ float exp_res(float x) {
-  constexpr float L2E = 1.44269504088896340736f, L2E_LO = 1.925963033500003e-8f, LN2 = 0.69314718055994530942f;
-  x = fmaxf(x, -1e5f);
-  const float t = x * L2E;
-  const float r = __builtin_fmaf(x, L2E_LO, __builtin_fmaf(x, L2E, -t));
-  const float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, r * LN2, e);
 }
 
 template <int NCH>

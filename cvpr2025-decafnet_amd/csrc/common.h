@@ -10,12 +10,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #define DCF_WAVE 64
 
 namespace dcf {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// the condition of every 16-byte (f32x4) access: checked by the entry points on the host, by the optimiser kernels per call
+__host__ __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---- wave-level reductions (64 lanes) -------------------------------------------------
 // Cross-lane adds go through DPP (data-parallel primitives: quad_perm / row mirrors / row broadcasts),
@@ -276,6 +281,26 @@ void set_error(const char* fmt, ...);
       return -1;                                                                   \
     }                                                                              \
   } while (0)
+
+// ---- dynamic LDS beyond the 64 KiB a launch gets by default -----------------------------------------
+// Raises the limit of one kernel, passed as &k<...>, on the current device to `bytes`.  The attribute belongs to the device's copy
+// of the kernel, so every instantiation keeps the largest size it has set per device and repeats the call only for a larger one (a
+// forward under graph capture does not repeat it); a device index outside the table gets the call every time.  The entries are
+// relaxed atomics: two host threads racing on the first call repeat it at worst.
+namespace dcf {
+template <auto Kernel>
+int raise_lds_limit(size_t bytes) {
+  static std::atomic<size_t> have[64];
+  int dev = 0;
+  DCF_HIP(hipGetDevice(&dev));
+  const bool in_table = dev >= 0 && dev < 64;
+  if (!in_table || bytes > have[dev].load(std::memory_order_relaxed)) {
+    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (in_table) have[dev].store(bytes, std::memory_order_relaxed);
+  }
+  return 0;
+}
+}  // namespace dcf
 
 // ---- stream-ordered scratch of one entry point ---------------------------------------------------
 // Owns what it allocates with hipMallocAsync on its stream: end(rc) frees everything in allocation order and passes rc on; what an

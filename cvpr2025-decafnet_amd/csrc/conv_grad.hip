@@ -12,7 +12,7 @@
 // plane -- the k-contiguous layout an MFMA operand wants, i.e. the transposition happens in the registers.  The three taps are the
 // same X rows shifted by +-1: the thread reads its 8 rows and a one-row rim (10 loads, converted once) and writes the three
 // shifted, seam-gated vectors; X is read from memory once.  A workgroup owns a 64 (n) x 64 (c) x k tile of the output and one
-// slice of the rows; its fp32 partial goes to scratch and k_cg_reduce adds the slices in a fixed order (blocked summation in balanced trees, no
+// slice of the rows; its fp32 partial goes to scratch and k_cg_reduce adds the slices in a fixed order (blocked_sum, grad_common.h; no
 // floating-point atomics: bit-identical from run to run).  db rides along: the threads that staged dY add up what they staged.
 //
 // Range of dY.  The forward pre-scales activations by a fixed 2^4 because their range is structural; a gradient has no such bound
@@ -50,8 +50,8 @@
 // (row pitch 2 Cin); the odd one carries a zero image for its first tap, because the row GEMM has three taps: 6 taps of work for 5.
 #include <mutex>
 #include "../../include/decafnet_hip.h"
-#include "common.h"
 #include "conv_grad.h"
+#include "grad_common.h"
 #include "gemm.h"
 #include "rowops.h"
 
@@ -397,23 +397,8 @@ __global__ __launch_bounds__(256) void k_cg_reduce(const float* __restrict__ par
                                                    int accumulate, unsigned* __restrict__ status) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= count) return;
-  // fixed-order blocked summation: balanced trees over 8 parts, over 8 of those, then the groups of 64 in order -- nine
-  // roundings on the path of a part at 512 parts instead of 511
   float sum = 0.f;
-  for (int g2 = 0; g2 < nparts; g2 += 64) {
-    float l1[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      float v[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int sl = g2 + 8 * u + t;
-        v[t] = sl < nparts ? part[(int64_t)sl * stride + i] : 0.f;
-      }
-      l1[u] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    sum += ((l1[0] + l1[1]) + (l1[2] + l1[3])) + ((l1[4] + l1[5]) + (l1[6] + l1[7]));
-  }
+  DCF_BLOCKED_SUM(sum, part, nparts, stride, i);
   float inv = 1.f;
   if (absmax) (void)cg_scale(*absmax, inv);
   const float v = (sum * extra) * inv;

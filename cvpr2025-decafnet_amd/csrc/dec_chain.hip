@@ -544,19 +544,11 @@ int launch_dec_chain(const DecChainArgs& a, hipStream_t stream) {
   DCF_CHECK(a.B > 0 && a.T > 0 && a.X && a.mask && a.Wq && a.KV && a.kmask && a.Wp && a.Q3, "launch_dec_chain: null argument");
   DCF_CHECK(a.lk2 == 1 || a.lk2 == 2, "launch_dec_chain: lk2 = %d", a.lk2);
   DCF_CHECK(!a.stats_out || (a.stats_w > 0 && DE % a.stats_w == 0), "launch_dec_chain: stats_out needs a slot width dividing %d", DE);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  DCF_CHECK(al16(a.X) && al16(a.Q3) && al16(a.Wq) && al16(a.Wp) && al16(a.KV) && a.ldx % 4 == 0 && a.ldq % 4 == 0,
+  DCF_CHECK(aligned16(a.X) && aligned16(a.Q3) && aligned16(a.Wq) && aligned16(a.Wp) && aligned16(a.KV) && a.ldx % 4 == 0 && a.ldq % 4 == 0,
             "launch_dec_chain: operands must be 16-byte aligned with row pitches that are multiples of 4");
-  static bool attr_set[64] = {};                         // per device: the attribute belongs to the device's copy of the kernel
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dec_chain<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dec_chain<2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dec_chain<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dec_chain<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_set[dev] = true;
-  }
+  if (raise_lds_limit<&k_dec_chain<1>>(LDS_BYTES) || raise_lds_limit<&k_dec_chain<2>>(LDS_BYTES) ||
+      raise_lds_limit<&k_dec_chain<1, true>>(LDS_BYTES) || raise_lds_limit<&k_dec_chain<2, true>>(LDS_BYTES))
+    return -1;
   const unsigned grid = (unsigned)(a.B * ((a.T + WGROWS - 1) / WGROWS));
   if (a.attn_single) {
     if (a.lk2 == 1) hipLaunchKernelGGL((k_dec_chain<1, true>), dim3(grid), dim3(256), LDS_BYTES, stream, a);

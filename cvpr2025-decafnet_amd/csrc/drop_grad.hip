@@ -16,17 +16,13 @@
 // k_eg_reduce -- so with both probabilities 0 (f = 1) the three outputs have the bits of dcf_op_layerscale_residual_bwd.  Rows of
 // a sample whose path was dropped read neither H nor the random stream.
 #include "../../include/decafnet_hip_train.h"
-#include "common.h"
 #include "dropout.h"
 #include "enc_grad.h"
+#include "grad_common.h"
 
 namespace dcf {
 
 constexpr int DG_NT = 256;
-
-__device__ __forceinline__ f32x4 dg_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void dg_st4(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 dg_zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 enum { DG_DROP = 0, DG_GELU_FWD = 1, DG_GELU_BWD = 2 };
 
@@ -45,9 +41,9 @@ __global__ __launch_bounds__(DG_NT) void k_dg_elementwise(const float* X, const 
   for (int i = 0; i < 4; ++i) {
     if (t0 + i >= T) break;
     const int64_t off = ((int64_t)s * T + t0 + i) * C + 4 * c4;
-    const f32x4 x = dg_ld4(X + off);
-    f32x4 g = dg_zero4(), y;
-    if (MODE == DG_GELU_BWD) g = dg_ld4(G + off);
+    const f32x4 x = ld4(X + off);
+    f32x4 g = zero4(), y;
+    if (MODE == DG_GELU_BWD) g = ld4(G + off);
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) {
       const bool keep = (bits >> (4 * i + cc)) & 1u;
@@ -61,7 +57,7 @@ __global__ __launch_bounds__(DG_NT) void k_dg_elementwise(const float* X, const 
         y[cc] = gk * gelu_slope(x[cc]);
       }
     }
-    dg_st4(Y + off, y);
+    st4(Y + off, y);
   }
 }
 
@@ -92,8 +88,8 @@ __global__ __launch_bounds__(256) void k_drop_res_bwd(DropResGradArgs p) {
   const int64_t r_end = r_begin + p.rows_per_wave < p.rows ? r_begin + p.rows_per_wave : (int64_t)p.rows;
   const bool want_h = p.H != nullptr && p.part != nullptr;
   const bool quads = (T & 3) == 0, dropping = p.drop.p > 0.f;
-  const f32x4 ls = (act && p.dH) ? dg_ld4(p.ls + c) : dg_zero4();
-  f32x4 acc = dg_zero4();
+  const f32x4 ls = (act && p.dH) ? ld4(p.ls + c) : zero4();
+  f32x4 acc = zero4();
   int s = -1;                                            // the sample whose drop-path factor `dp` holds
   float dp = 1.f;
   int64_t quad = -1;                                     // T % 4 == 0: `bits` holds the keep bits of rows 4 quad .. 4 quad + 3
@@ -108,10 +104,10 @@ __global__ __launch_bounds__(256) void k_drop_res_bwd(DropResGradArgs p) {
     }
     const bool mr = !p.mR || p.mR[r], mh = (!p.mH || p.mH[r]) && dp != 0.f;      // a dropped sample: no H, no random stream
     if (!act) continue;
-    const f32x4 g = dg_ld4(p.dY + r * C + c);
-    if (p.dR) dg_st4(p.dR + r * C + c, mr ? g : dg_zero4());
+    const f32x4 g = ld4(p.dY + r * C + c);
+    if (p.dR) st4(p.dR + r * C + c, mr ? g : zero4());
     if (!mh) {
-      if (p.dH) dg_st4(p.dH + r * C + c, dg_zero4());
+      if (p.dH) st4(p.dH + r * C + c, zero4());
       continue;
     }
     unsigned kb = 0xfu;
@@ -130,21 +126,19 @@ __global__ __launch_bounds__(256) void k_drop_res_bwd(DropResGradArgs p) {
     f32x4 gf;
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) gf[cc] = ((kb >> cc) & 1u) ? g[cc] * f : 0.f;
-    if (p.dH) dg_st4(p.dH + r * C + c, ls * gf);
+    if (p.dH) st4(p.dH + r * C + c, ls * gf);
     if (want_h) {
-      const f32x4 h = dg_ld4(p.H + r * C + c);
+      const f32x4 h = ld4(p.H + r * C + c);
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc) acc[cc] = __builtin_fmaf(gf[cc], h[cc], acc[cc]);
     }
   }
   if (!p.part) return;
-  dg_st4(s_ls + wave * 256 + 4 * lane, acc);
+  st4(s_ls + wave * 256 + 4 * lane, acc);
   __syncthreads();
   const int i = threadIdx.x, cg = 256 * blockIdx.y + i;
   if (cg < C) p.part[(int64_t)blockIdx.x * C + cg] = (s_ls[i] + s_ls[256 + i]) + (s_ls[512 + i] + s_ls[768 + i]);
 }
-
-static inline bool dg_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 static int dg_check(const char* what, int B, int T, int C, int c_max, int b0, float p) {
   DCF_CHECK(B > 0 && T > 0, "%s: empty batch (B = %d, T = %d)", what, B, T);
@@ -186,7 +180,7 @@ int dcf_train_ext_version(void) { return DCF_TRAIN_EXT_VERSION; }
 int dcf_op_dropout(const float* X, float* Y, int32_t B, int32_t T, int32_t C, int32_t b0, int64_t seed, int32_t site, float p, void* stream) {
   DCF_CHECK(X && Y, "dcf_op_dropout: null argument");
   if (dg_check("dcf_op_dropout", B, T, C, DG_C_ANY, b0, p)) return -1;
-  DCF_CHECK(dg_aligned16(X) && dg_aligned16(Y), "dcf_op_dropout: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(X) && aligned16(Y), "dcf_op_dropout: pointers must be 16-byte aligned");
   if (p == 0.f && X == Y) return 0;
   return dg_elementwise<DG_DROP>(X, nullptr, Y, B, T, C, b0, seed, site, p, (hipStream_t)stream);
 }
@@ -194,7 +188,7 @@ int dcf_op_dropout(const float* X, float* Y, int32_t B, int32_t T, int32_t C, in
 int dcf_op_gelu_dropout(const float* X, float* Y, int32_t B, int32_t T, int32_t C, int32_t b0, int64_t seed, int32_t site, float p, void* stream) {
   DCF_CHECK(X && Y, "dcf_op_gelu_dropout: null argument");
   if (dg_check("dcf_op_gelu_dropout", B, T, C, DG_C_ANY, b0, p)) return -1;
-  DCF_CHECK(dg_aligned16(X) && dg_aligned16(Y), "dcf_op_gelu_dropout: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(X) && aligned16(Y), "dcf_op_gelu_dropout: pointers must be 16-byte aligned");
   return dg_elementwise<DG_GELU_FWD>(X, nullptr, Y, B, T, C, b0, seed, site, p, (hipStream_t)stream);
 }
 
@@ -202,7 +196,7 @@ int dcf_op_gelu_dropout_bwd(const float* X, const float* dY, float* dX, int32_t 
                             float p, void* stream) {
   DCF_CHECK(X && dY && dX, "dcf_op_gelu_dropout_bwd: null argument");
   if (dg_check("dcf_op_gelu_dropout_bwd", B, T, C, DG_C_ANY, b0, p)) return -1;
-  DCF_CHECK(dg_aligned16(X) && dg_aligned16(dY) && dg_aligned16(dX), "dcf_op_gelu_dropout_bwd: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(X) && aligned16(dY) && aligned16(dX), "dcf_op_gelu_dropout_bwd: pointers must be 16-byte aligned");
   return dg_elementwise<DG_GELU_BWD>(X, dY, dX, B, T, C, b0, seed, site, p, (hipStream_t)stream);
 }
 
@@ -210,7 +204,7 @@ int dcf_op_drop_residual(const float* R, const uint8_t* mR, const float* H, cons
                          int32_t C, int32_t b0, int64_t seed, int32_t drop_site, float drop_p, int32_t path_site, float path_p, void* stream) {
   DCF_CHECK(R && H && ls && Y, "dcf_op_drop_residual: null argument");
   if (dg_check("dcf_op_drop_residual", B, T, C, 1024, b0, drop_p) || dg_check("dcf_op_drop_residual", B, T, C, 1024, b0, path_p)) return -1;
-  DCF_CHECK(dg_aligned16(R) && dg_aligned16(H) && dg_aligned16(ls) && dg_aligned16(Y), "dcf_op_drop_residual: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(R) && aligned16(H) && aligned16(ls) && aligned16(Y), "dcf_op_drop_residual: pointers must be 16-byte aligned");
   DCF_CHECK(!mR || !mH || mR == mH, "dcf_op_drop_residual: mR and mH, where both are given, are one array (a block has one mask)");
   if (drop_p == 0.f && path_p == 0.f) return dcf_op_layerscale_residual(R, mR, H, mH, ls, Y, B * T, C, stream);
   DropResArgs a{};
@@ -230,7 +224,7 @@ int dcf_op_drop_residual_bwd(const float* dY, const float* H, const uint8_t* mR,
   DCF_CHECK(!dH || ls, "dcf_op_drop_residual_bwd: dH needs the scale");
   DCF_CHECK(!dls || H, "dcf_op_drop_residual_bwd: dls needs H");
   if (dg_check("dcf_op_drop_residual_bwd", B, T, C, 1024, b0, drop_p) || dg_check("dcf_op_drop_residual_bwd", B, T, C, 1024, b0, path_p)) return -1;
-  DCF_CHECK(dg_aligned16(dY) && dg_aligned16(H) && dg_aligned16(ls) && dg_aligned16(dR) && dg_aligned16(dH),
+  DCF_CHECK(aligned16(dY) && aligned16(H) && aligned16(ls) && aligned16(dR) && aligned16(dH),
             "dcf_op_drop_residual_bwd: pointers must be 16-byte aligned");
   if (!dR && !dH && !dls) return 0;
   const int rows = B * T;

@@ -604,17 +604,10 @@ int launch_enc_attn(const EncAttnArgs& a, hipStream_t stream) {
   DCF_CHECK(a.B > 0 && a.T > 0 && a.Q && a.K && a.V && a.mask && a.Wp && a.bp && a.R && a.Y && a.win >= 1 && a.win <= 9 && (a.win & 1),
             "launch_enc_attn: bad arguments (window odd, <= 9)");
   DCF_CHECK(!a.stats_out || (a.stats_w > 0 && EE % a.stats_w == 0), "launch_enc_attn: stats_out needs a slot width dividing %d", EE);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  DCF_CHECK(al16(a.Q) && al16(a.K) && al16(a.V) && al16(a.Wp) && al16(a.R) && al16(a.Y) && a.ldr % 4 == 0 && a.ldy % 4 == 0,
+  DCF_CHECK(aligned16(a.Q) && aligned16(a.K) && aligned16(a.V) && aligned16(a.Wp) && aligned16(a.R) && aligned16(a.Y) && a.ldr % 4 == 0 &&
+                a.ldy % 4 == 0,
             "launch_enc_attn: operands must be 16-byte aligned with row pitches that are multiples of 4");
-  static bool attr_set[64] = {};
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_enc_attn<false>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS_BYTES));
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_enc_attn<true>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS_BYTES));
-    attr_set[dev] = true;
-  }
+  if (raise_lds_limit<&k_enc_attn<false>>(A_LDS_BYTES) || raise_lds_limit<&k_enc_attn<true>>(A_LDS_BYTES)) return -1;
   const unsigned grid = (unsigned)(a.B * ((a.T + AWG_ROWS - 1) / AWG_ROWS));
   if (a.attn_single) hipLaunchKernelGGL(k_enc_attn<true>, dim3(grid), dim3(256), A_LDS_BYTES, stream, a);
   else hipLaunchKernelGGL(k_enc_attn<false>, dim3(grid), dim3(256), A_LDS_BYTES, stream, a);
@@ -627,17 +620,11 @@ bool enc_chain_supports(int E, int heads, int win) { return E == EE && heads == 
 int launch_enc_qkv(const EncQkvArgs& a, hipStream_t stream) {
   DCF_CHECK(a.B > 0 && a.T_in > 0 && a.X && a.mask_in && a.ln_w && a.ln_b,
             "launch_enc_qkv: bad arguments");
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   for (int op = 0; op < 3; ++op)
-    DCF_CHECK(a.dw[op] && a.fs[op] && a.fc[op] && a.W[op] && a.out[op] && al16(a.W[op]) && al16(a.out[op]), "launch_enc_qkv: null or misaligned argument");
-  DCF_CHECK(al16(a.X) && a.ldx % 4 == 0, "launch_enc_qkv: X must be 16-byte aligned, its row pitch a multiple of 4");
-  static bool attr_set[64] = {};                         // per device: the attribute belongs to the device's copy of the kernel
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_enc_qkv), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_set[dev] = true;
-  }
+    DCF_CHECK(a.dw[op] && a.fs[op] && a.fc[op] && a.W[op] && a.out[op] && aligned16(a.W[op]) && aligned16(a.out[op]),
+              "launch_enc_qkv: null or misaligned argument");
+  DCF_CHECK(aligned16(a.X) && a.ldx % 4 == 0, "launch_enc_qkv: X must be 16-byte aligned, its row pitch a multiple of 4");
+  if (raise_lds_limit<&k_enc_qkv>(LDS_BYTES)) return -1;
   const unsigned grid = (unsigned)(a.B * ((a.T_in + WGROWS - 1) / WGROWS));
   hipLaunchKernelGGL(k_enc_qkv, dim3(grid), dim3(256), LDS_BYTES, stream, a);
   DCF_HIP(hipGetLastError());

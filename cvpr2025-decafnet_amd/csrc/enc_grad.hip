@@ -19,7 +19,7 @@
 // All of it is streaming work on the vector ALU with 16-byte accesses.  The elementwise kernels give a thread one f32x4; the two
 // column reductions (dW, dls) follow k_ln_bwd (conv_grad.hip): a wave owns a run of rows, a lane four channels of a 256-channel
 // chunk (blockIdx.y), sums stay in registers, four waves meet in LDS, and k_eg_reduce adds the workgroup partials in a fixed order
-// (balanced trees over 8 parts, over 8 of those, then the groups of 64 in order).  No floating-point atomics, one summation order:
+// (blocked_sum, grad_common.h).  No floating-point atomics, one summation order:
 // results are bit-identical from run to run, and every product has the upstream gradient as one factor, so scaling it by a power of
 // two scales the results by exactly that.
 //
@@ -30,8 +30,8 @@
 #include <math.h>
 
 #include "../../include/decafnet_hip.h"
-#include "common.h"
 #include "enc_grad.h"
+#include "grad_common.h"
 
 namespace dcf {
 
@@ -39,10 +39,6 @@ static inline unsigned eg_grid(int64_t n, int per_block) {
   const int64_t g = (n + per_block - 1) / per_block;
   return (unsigned)(g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g));
 }
-
-__device__ __forceinline__ f32x4 ld4(const float* __restrict__ p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* __restrict__ p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 // the three taps of four adjacent channels: W (C, 3) rows c .. c + 3 are 12 consecutive floats; w[j] = tap j of the four channels
 __device__ __forceinline__ void load_taps(const float* __restrict__ W, f32x4* w) {
@@ -157,27 +153,14 @@ __global__ __launch_bounds__(256) void k_dw_bwd_w(DwGradArgs p) {
   }
 }
 
-// out[o(i)] (+)= sum_s part[s][i] in a fixed order: balanced trees over 8 parts, over 8 of those, then the groups of 64 in order (the
-// summation of k_cg_reduce, conv_grad.hip).  KT = 3: part is laid out [n][j][c], out is PyTorch's [n][c][j].
+// out[o(i)] (+)= sum_s part[s][i] in the fixed blocked order of blocked_sum (grad_common.h).  KT = 3: part is laid out [n][j][c], out is
+// PyTorch's [n][c][j].
 __global__ __launch_bounds__(256) void k_eg_reduce(const float* __restrict__ part, int nparts, int64_t stride, int count, float* __restrict__ out,
                                                    int KT, int C, int accumulate) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= count) return;
   float sum = 0.f;
-  for (int g2 = 0; g2 < nparts; g2 += 64) {
-    float l1[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      float v[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int sl = g2 + 8 * u + t;
-        v[t] = sl < nparts ? part[(int64_t)sl * stride + i] : 0.f;
-      }
-      l1[u] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    sum += ((l1[0] + l1[1]) + (l1[2] + l1[3])) + ((l1[4] + l1[5]) + (l1[6] + l1[7]));
-  }
+  DCF_BLOCKED_SUM(sum, part, nparts, stride, i);
   int o = i;
   if (KT > 1) {
     const int n = i / (KT * C), rem = i - n * KT * C, j = rem / C, c = rem - j * C;
@@ -374,8 +357,6 @@ __global__ __launch_bounds__(256) void k_ls_bwd(LsGradArgs p) {
   const int i = threadIdx.x, cg = 256 * blockIdx.y + i;
   if (cg < C) p.part[(int64_t)blockIdx.x * C + cg] = (s_ls[i] + s_ls[256 + i]) + (s_ls[512 + i] + s_ls[768 + i]);
 }
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace dcf
 

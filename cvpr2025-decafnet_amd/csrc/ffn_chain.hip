@@ -924,23 +924,17 @@ int launch_ffn_chain(const FfnChainArgs& a, hipStream_t stream) {
   DCF_CHECK(a.M > 0 && a.X && a.W1s && a.b1 && a.W2s && a.b2 && a.R && a.C, "launch_ffn_chain: null argument");
   DCF_CHECK(!a.stats || (a.ln_s && a.stats_slots >= 1), "launch_ffn_chain: stats need ln_s and stats_slots");
   DCF_CHECK(!a.stats_out || (a.stats_w > 0 && FE % a.stats_w == 0), "launch_ffn_chain: stats_out needs a slot width dividing %d", FE);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  DCF_CHECK(al16(a.X) && al16(a.R) && al16(a.C) && al16(a.b1) && al16(a.b2) && al16(a.W1s) && al16(a.W2s) && (!a.ls || al16(a.ls)) &&
-                (!a.ln_s || al16(a.ln_s)) && a.ldx % 4 == 0 && a.ldr % 4 == 0 && a.ldc % 4 == 0,
+  DCF_CHECK(aligned16(a.X) && aligned16(a.R) && aligned16(a.C) && aligned16(a.b1) && aligned16(a.b2) && aligned16(a.W1s) && aligned16(a.W2s) &&
+                (!a.ls || aligned16(a.ls)) && (!a.ln_s || aligned16(a.ln_s)) && a.ldx % 4 == 0 && a.ldr % 4 == 0 && a.ldc % 4 == 0,
             "launch_ffn_chain: operands must be 16-byte aligned with row pitches that are multiples of 4");
-  static bool attr_set[64] = {};                         // per device: the attribute belongs to the device's copy of the kernel
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffn_chain<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffn_chain<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_set[dev] = true;
-  }
+  if (raise_lds_limit<&k_ffn_chain<true>>(LDS_BYTES) || raise_lds_limit<&k_ffn_chain<false>>(LDS_BYTES) ||
+      raise_lds_limit<&k_ffn_pair<true>>(PAIR_LDS_BYTES) || raise_lds_limit<&k_ffn_pair<false>>(PAIR_LDS_BYTES))
+    return -1;
   const unsigned grid = (unsigned)((a.M + 127) / 128);
   static int n_cu[64] = {};
+  int dev = 0;
+  DCF_HIP(hipGetDevice(&dev));
   if (dev >= 0 && dev < 64 && !n_cu[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffn_pair<true>), hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_LDS_BYTES));
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ffn_pair<false>), hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_LDS_BYTES));
     hipDeviceProp_t prop;
     DCF_HIP(hipGetDeviceProperties(&prop, dev));
     n_cu[dev] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;

@@ -16,16 +16,16 @@
 // max |R| (launch_absmax on R itself, a device word per half: no host wait).  A workgroup owns a 64 (e) x 64 (d) tile of dW and one
 // slice of one video's clips; a slice is a whole number of 64-clip gate tiles, and a 32-clip chunk of a tile that no query of the
 // video keeps takes no K step (R1 is zero there, so the bits do not depend on the skipping while vid is finite).  The fp32
-// partials of the slices go to scratch and k_fg_reduce adds them in the fixed blocked order of k_cg_reduce: no floating-point
+// partials of the slices go to scratch and k_fg_reduce adds them in the fixed blocked order of blocked_sum (grad_common.h): no floating-point
 // atomics, equal inputs give equal bits, and powers of two commute with every rounding here.
 //
 // The per-video query counts arrive as a host array; k_fg_tables receives them by value, 64 videos per launch, and writes the
 // device tables (first row of every video, video of every row): no host memory is read after the call returns.
 #include "../../include/decafnet_hip_front.h"
-#include "common.h"
 #include "conv_grad.h"
 #include "front_grad.h"
 #include "gemm.h"
+#include "grad_common.h"
 #include "rowops.h"
 
 namespace dcf {
@@ -232,36 +232,15 @@ __global__ __launch_bounds__(256) void k_fg_wgrad(FrontWgradArgs p) {
   }
 }
 
-// out[(i / rowlen) pitch + i % rowlen] (+)= extra * inv_scale * sum_s part[s][i], the parts in the fixed blocked order of k_cg_reduce
+// out[(i / rowlen) pitch + i % rowlen] (+)= extra * inv_scale * sum_s part[s][i], the parts in the fixed blocked order of
+// grad_common.h, in its rolled form: the unrolled one's scalar address arithmetic did not fit the scalar registers here
 __global__ __launch_bounds__(256) void k_fg_reduce(const float* __restrict__ part, int nparts, int64_t stride, int count, int rowlen, int pitch,
                                                   const unsigned* __restrict__ absmax, float extra, float* __restrict__ out, int accumulate,
                                                   unsigned* __restrict__ status) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= count) return;
-  // balanced trees over 8 parts, over 8 of those, then the groups of 64 in order.  The second level runs as a loop with the
-  // three pending subtree sums in registers (s0: one tree, s1: two, s2: four or eight), which is the same tree: 8 loads in flight
-  // instead of 64, whose scalar address arithmetic did not fit the scalar registers
   float sum = 0.f;
-  const float* __restrict__ pp = part + i;
-  for (int g2 = 0; g2 < nparts; g2 += 64) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll 1
-    for (int u = 0; u < 8; ++u) {
-      float v[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int sl = g2 + 8 * u + t;
-        v[t] = sl < nparts ? pp[(int64_t)sl * stride] : 0.f;
-      }
-      float x = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-      if (!(u & 1)) { s0 = x; continue; }
-      x = s0 + x;
-      if (!(u & 2)) { s1 = x; continue; }
-      x = s1 + x;
-      s2 = (u & 4) ? s2 + x : x;
-    }
-    sum += s2;
-  }
+  DCF_BLOCKED_SUM_ROLLED(sum, part, nparts, stride, i);
   float inv = 1.f;
   if (absmax) (void)cg_scale(*absmax, inv);
   const float v = (sum * extra) * inv;

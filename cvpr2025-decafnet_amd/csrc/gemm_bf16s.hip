@@ -780,7 +780,7 @@ static int launch_cfg_s(const GemmBatch& b, int count, GemmAMode mode, int nterm
       }
       if (want_score) {
         const size_t lds_sc = lds + (size_t)score_q * p.K * sizeof(float);
-        // (no hipFuncAttributeMaxDynamicSharedMemorySize on these instantiations: the caller keeps the text vectors within the
+        // (no raise_lds_limit (common.h) on these instantiations: the caller keeps the text vectors within the
         // default 64 KiB -- engine.hip scores_on_gemm -- and sends wider features through k_sidekick_*)
         DCF_CHECK(lds_sc <= 65536, "launch_gemm_split: %d text vectors of %d channels beside the tile need %zu bytes of LDS (> 64 KiB)", score_q, p.K, lds_sc);
         constexpr int NST_ = DEEP ? 3 : 2;

@@ -21,7 +21,7 @@
 // No atomics and one fixed summation order: equal inputs give equal bits, and every product and sum is linear in dO with nothing but
 // roundings in between, so dO times a power of two gives that power of two times each output.  delta is formed from p and dP (not
 // from a stored O) and m and 1 / l are kept apart, for the reasons at the top of attn_grad.hip; the exponential carries its residual
-// (exp_res there).  Every accumulation is written as an explicit fma, so what the compiler may contract does not depend on which
+// (exp_res, grad_common.h).  Every accumulation is written as an explicit fma, so what the compiler may contract does not depend on which
 // outputs are wanted: with one of dQ / dK / dV absent the others keep their bits.
 //
 // Arithmetic: fp32 on the vector ALU, 2 T^2 C flops per product and nine products (the query side forms s and dP twice and dQ, the key
@@ -30,20 +30,9 @@
 #include "global_attn_grad.h"
 
 #include "../../include/decafnet_hip_attn.h"
-#include "common.h"
+#include "grad_common.h"
 
 namespace dcf {
-
-// exp(x), x <= 0 (or barely above): v_exp_f32 of the rounded product x * log2(e), times 1 + ln 2 * (what the rounding of the product
-// and of the constant dropped) -- exp_res of attn_grad.hip, for the same reason: dS = p (dP - delta) is a difference
-__device__ __forceinline__ float gg_exp_res(float x) {
-  constexpr float L2E = 1.44269504088896340736f, L2E_LO = 1.925963033500003e-8f, LN2 = 0.69314718055994530942f;
-  x = fmaxf(x, -1e5f);
-  const float t = x * L2E;
-  const float r = __builtin_fmaf(x, L2E_LO, __builtin_fmaf(x, L2E, -t));
-  const float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, r * LN2, e);
-}
 
 constexpr int GG_TILE = 64;           // rows of a query tile and of a key tile
 constexpr int GG_PP = GG_TILE + 4;    // row pitch of the score tile
@@ -139,12 +128,12 @@ __global__ __launch_bounds__(256) void k_gattn_bwd_q(GlobalAttnGradArgs p) {
       tmax = fmaxf(tmax, dpp_self<DPP_XOR1>(tmax));
       tmax = fmaxf(tmax, dpp_self<DPP_XOR2>(tmax));
       const float mn = fmaxf(m, tmax);
-      const float corr = m == -INFINITY ? 0.f : gg_exp_res(m - mn);   // (nothing so far: nothing to rescale)
+      const float corr = m == -INFINITY ? 0.f : exp_res(m - mn);   // (nothing so far: nothing to rescale)
       float ls = 0.f, ds = 0.f;
 #pragma unroll
       for (int jj = 0; jj < 16; ++jj) {
         const bool ok = valid[jj * 4 + part] != 0.f;
-        const float e = ok ? gg_exp_res(s[jj] - mn) : 0.f;
+        const float e = ok ? exp_res(s[jj] - mn) : 0.f;
         ls += e;
         ds = ok ? __builtin_fmaf(e, dp[jj], ds) : ds;
       }
@@ -158,7 +147,7 @@ __global__ __launch_bounds__(256) void k_gattn_bwd_q(GlobalAttnGradArgs p) {
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) {
       const int j = jj * 4 + part;
-      const float pj = gg_exp_res(s[jj] - m) * il;
+      const float pj = exp_res(s[jj] - m) * il;
       const float dsj = pj * (dp[jj] - delta);
       Ss[qi * GG_PP + j] = valid[j] != 0.f ? dsj : 0.f;
     }
@@ -228,7 +217,7 @@ __global__ __launch_bounds__(256) void k_gattn_bwd_kv(GlobalAttnGradArgs p) {
       const f32x4 st = St[t];
       const bool ok = kvalid && t0 + t < T;              // a padded QUERY row is live; rows past T are not rows
       const float s = gg_dot<D>(k, Qs + t * QP);
-      pj[jj] = ok ? gg_exp_res(s - st.x) * st.y : 0.f;
+      pj[jj] = ok ? exp_res(s - st.x) * st.y : 0.f;
       if (want_dk) {
         const float dpj = gg_dot<D>(v, Gs + t * QP);
         ds[jj] = ok ? pj[jj] * (dpj - st.z) : 0.f;

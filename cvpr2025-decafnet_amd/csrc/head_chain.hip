@@ -511,13 +511,7 @@ int launch_split_chain3(const float* Wp, unsigned short* img, int C, hipStream_t
 template <int C>
 static int launch_hc(const HeadChainArgs* a, int count, hipStream_t stream) {
   constexpr int bytes = 2 * Geo<C>::STAGE + (4 * C + 2 * 3 * C + 2 * 4 * 2 * 2 * 16) * (int)sizeof(float);
-  static bool attr_set[64] = {};                         // per device: the attribute belongs to the device's copy of the kernel
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_chain<C>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    attr_set[dev] = true;
-  }
+  if (raise_lds_limit<&k_head_chain<C>>(bytes)) return -1;
   HeadChainBatch b{};
   for (int i = 0; i < count; ++i) b.a[i] = a[i];
   const unsigned grid = (unsigned)((a[0].rows + VALID - 1) / VALID);

@@ -924,13 +924,7 @@ static int launch_tcn_stack_n(const TcnStackArgs& a, hipStream_t st) {
   constexpr int VALID = TS_ROWS - 2 * ((1 << NL) - 1);
   const unsigned grid = (unsigned)(a.B * ((a.T0 + VALID - 1) / VALID));
   const size_t lds = (size_t)2 * TS_ROWS * TS_PITCH * sizeof(float);        // 72 KiB: above the 64 KiB a kernel gets without asking
-  static bool attr_set[64] = {};
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tcn_stack<NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
+  if (raise_lds_limit<&k_tcn_stack<NL>>(lds)) return -1;
   hipLaunchKernelGGL((k_tcn_stack<NL>), dim3(grid), dim3(256), lds, st, a);
   DCF_HIP(hipGetLastError());
   return 0;

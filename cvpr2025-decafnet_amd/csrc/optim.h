@@ -69,7 +69,6 @@ __device__ __forceinline__ void store4(float* __restrict__ base, long long i, lo
   for (int j = 0; j < OPT_VEC; ++j)
     if (i + j < n) base[i + j] = x[j];
 }
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // The bodies of the table kernels, shared by optim.hip and optim_guard.hip (include/decafnet_hip_guard.h): one workgroup of OPT_NT
 // threads owns one chunk of DCF_OPTIM_CHUNK elements of one tensor, which it finds through the chunk map and the row's chunk prefix.

@@ -21,41 +21,18 @@
 // outer products (a lane per channel) are free of bank conflicts.  The backward runs in two phases: k_tcn_bwd1 recomputes the forward
 // of its rows, forms dz and dh, leaves them in dX and in scratch, and accumulates the parameter gradients of its slice of
 // RG_SLICE_ROWS rows -- the two outer products as 12 + 4 register accumulators per thread over the rows in ascending order, the
-// four 32-vectors as wave reductions on DPP; k_tcn_bwd2 gathers dX from dh at t and t -+ d.  k_rg_reduce adds the slices in a fixed
-// blocked order (balanced trees over 8 parts, over 8 of those, then the groups of 64 in order: the summation of k_eg_reduce).  No
+// four 32-vectors as wave reductions on DPP; k_tcn_bwd2 gathers dX from dh at t and t -+ d.  k_rg_reduce adds the slices in the fixed
+// blocked order of blocked_sum (grad_common.h).  No
 // floating-point atomics; the slicing is a constant: results are bit-identical from run to run, and every product has the upstream
 // gradient as one factor, so a power-of-two scale of it scales the results by exactly that.
 #include <math.h>
 
 #include "../../include/decafnet_hip.h"
-#include "common.h"
 #include "dropout.h"
+#include "grad_common.h"
 #include "refine_grad.h"
 
 namespace dcf {
-
-__device__ __forceinline__ f32x4 rg_ld4(const float* __restrict__ p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void rg_st4(float* __restrict__ p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
-
-// out = sum_s part[s * stride + i] in a fixed order: balanced trees over 8 parts, over 8 of those, then the groups of 64 in order
-__device__ __forceinline__ float rg_tree_sum(const float* __restrict__ part, int nparts, int64_t stride, int i) {
-  float sum = 0.f;
-  for (int g2 = 0; g2 < nparts; g2 += 64) {
-    float l1[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      float v[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int sl = g2 + 8 * u + t;
-        v[t] = sl < nparts ? part[(int64_t)sl * stride + i] : 0.f;
-      }
-      l1[u] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    sum += ((l1[0] + l1[1]) + (l1[2] + l1[3])) + ((l1[4] + l1[5]) + (l1[6] + l1[7]));
-  }
-  return sum;
-}
 
 // ------------------------------------------------------------------------------------------
 // refine_in
@@ -67,14 +44,14 @@ __global__ __launch_bounds__(256) void k_refine_in_fwd(RefineInArgs p) {
   const int b = r / p.T0, t = r - b * p.T0;
   const float mf = (!p.mask0 || p.mask0[r]) ? 1.f : 0.f;
   const float* lg = p.logits1 + (int64_t)b * p.S;
-  f32x4 acc = rg_ld4(p.b + c);
+  f32x4 acc = ld4(p.b + c);
   for (int l = 0; l < p.L; ++l) {
     float u = lg[p.off[l] + (t >> l)];
     if (l > 0) u *= mf;
     acc = f32x4{__builtin_fmaf(p.W[(c + 0) * p.L + l], u, acc.x), __builtin_fmaf(p.W[(c + 1) * p.L + l], u, acc.y),
                 __builtin_fmaf(p.W[(c + 2) * p.L + l], u, acc.z), __builtin_fmaf(p.W[(c + 3) * p.L + l], u, acc.w)};
   }
-  rg_st4(p.H + (int64_t)r * RG_C + c, acc);
+  st4(p.H + (int64_t)r * RG_C + c, acc);
 }
 
 // a workgroup owns a slice of RG_SLICE_ROWS rows: dH and u of the slice in LDS, then a thread per (l, c) for the slice's sums of
@@ -88,7 +65,7 @@ __global__ __launch_bounds__(256) void k_refine_in_bwd(RefineInArgs p) {
   const int r0 = blockIdx.x * RG_SLICE_ROWS;
   for (int i = tid; i < RG_SLICE_ROWS * (RG_C / 4); i += 256) {
     const int rr = i >> 3, c = (i & 7) * 4, r = r0 + rr;
-    const f32x4 v = r < p.rows ? rg_ld4(p.dH + (int64_t)r * RG_C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 v = r < p.rows ? ld4(p.dH + (int64_t)r * RG_C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     s_dh[rr * DP + c] = v.x; s_dh[rr * DP + c + 1] = v.y; s_dh[rr * DP + c + 2] = v.z; s_dh[rr * DP + c + 3] = v.w;
   }
   for (int i = tid; i < RG_SLICE_ROWS * (L + 1); i += 256) {
@@ -149,7 +126,7 @@ __global__ __launch_bounds__(256) void k_refine_in_reduce(const float* __restric
   const int c = i & 31, l = i >> 5;
   float* out = l == L ? (db ? db + c : nullptr) : (dW ? dW + c * L + l : nullptr);
   if (!out) return;
-  const float sum = rg_tree_sum(part, nparts, (int64_t)RG_C * (L + 1), i);
+  const float sum = blocked_sum(part, nparts, (int64_t)RG_C * (L + 1), i);
   *out = accumulate ? *out + sum : sum;
 }
 
@@ -208,7 +185,7 @@ __device__ __forceinline__ TcnRow tcn_rows_forward(const TcnLds& s, const TcnLay
     const int f = w * 6 + q, tap = f >> 3, c4 = (f & 7) * 4;
     const int64_t tt = (int64_t)t + (int64_t)(tap - 1) * a.dil;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (o.live && tt >= 0 && tt < a.T0) v = rg_ld4(a.X + ((int64_t)o.r + (int64_t)(tap - 1) * a.dil) * RG_C + c4);
+    if (o.live && tt >= 0 && tt < a.T0) v = ld4(a.X + ((int64_t)o.r + (int64_t)(tap - 1) * a.dil) * RG_C + c4);
     float* dst = s.x + (tap * RG_C + c4) * RG_PITCH + lane;
     dst[0] = v.x; dst[RG_PITCH] = v.y; dst[2 * RG_PITCH] = v.z; dst[3 * RG_PITCH] = v.w;
   }
@@ -219,7 +196,7 @@ __device__ __forceinline__ TcnRow tcn_rows_forward(const TcnLds& s, const TcnLay
 #pragma unroll 4
   for (int k = 0; k < 3 * RG_C; ++k) {
     const float xv = s.x[k * RG_PITCH + lane];
-    const f32x4 w0 = rg_ld4(s.wd + k * RG_C + c0), w1 = rg_ld4(s.wd + k * RG_C + c0 + 4);
+    const f32x4 w0 = ld4(s.wd + k * RG_C + c0), w1 = ld4(s.wd + k * RG_C + c0 + 4);
     h[0] = __builtin_fmaf(w0.x, xv, h[0]); h[1] = __builtin_fmaf(w0.y, xv, h[1]);
     h[2] = __builtin_fmaf(w0.z, xv, h[2]); h[3] = __builtin_fmaf(w0.w, xv, h[3]);
     h[4] = __builtin_fmaf(w1.x, xv, h[4]); h[5] = __builtin_fmaf(w1.y, xv, h[5]);
@@ -234,7 +211,7 @@ __device__ __forceinline__ TcnRow tcn_rows_forward(const TcnLds& s, const TcnLay
 #pragma unroll 4
   for (int ci = 0; ci < RG_C; ++ci) {
     const float hv = s.h[ci * RG_PITCH + lane];
-    const f32x4 w0 = rg_ld4(s.wpT + ci * RG_C + c0), w1 = rg_ld4(s.wpT + ci * RG_C + c0 + 4);
+    const f32x4 w0 = ld4(s.wpT + ci * RG_C + c0), w1 = ld4(s.wpT + ci * RG_C + c0 + 4);
     v[0] = __builtin_fmaf(w0.x, hv, v[0]); v[1] = __builtin_fmaf(w0.y, hv, v[1]);
     v[2] = __builtin_fmaf(w0.z, hv, v[2]); v[3] = __builtin_fmaf(w0.w, hv, v[3]);
     v[4] = __builtin_fmaf(w1.x, hv, v[4]); v[5] = __builtin_fmaf(w1.y, hv, v[5]);
@@ -284,13 +261,13 @@ __global__ __launch_bounds__(256) void k_rg_tcn_fwd(TcnLayerArgs a) {
   const int c0 = 8 * w;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    const f32x4 lw = rg_ld4(a.lnw + c0 + 4 * q), lb = rg_ld4(a.lnb + c0 + 4 * q);
+    const f32x4 lw = ld4(a.lnw + c0 + 4 * q), lb = ld4(a.lnb + c0 + 4 * q);
     f32x4 y;
     y.x = __builtin_fmaf((o.z[4 * q] - o.mean) * o.rs, lw.x, lb.x);
     y.y = __builtin_fmaf((o.z[4 * q + 1] - o.mean) * o.rs, lw.y, lb.y);
     y.z = __builtin_fmaf((o.z[4 * q + 2] - o.mean) * o.rs, lw.z, lb.z);
     y.w = __builtin_fmaf((o.z[4 * q + 3] - o.mean) * o.rs, lw.w, lb.w);
-    rg_st4(a.Y + (int64_t)o.r * RG_C + c0 + 4 * q, y);
+    st4(a.Y + (int64_t)o.r * RG_C + c0 + 4 * q, y);
   }
 }
 
@@ -322,7 +299,7 @@ __global__ __launch_bounds__(256) void k_tcn_bwd1(TcnLayerArgs a) {
     float zh[8], g[8], dy[8];
     {
       f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
-      if (o.live) { d0 = rg_ld4(a.dY + (int64_t)o.r * RG_C + c0); d1 = rg_ld4(a.dY + (int64_t)o.r * RG_C + c0 + 4); }
+      if (o.live) { d0 = ld4(a.dY + (int64_t)o.r * RG_C + c0); d1 = ld4(a.dY + (int64_t)o.r * RG_C + c0 + 4); }
       dy[0] = d0.x; dy[1] = d0.y; dy[2] = d0.z; dy[3] = d0.w; dy[4] = d1.x; dy[5] = d1.y; dy[6] = d1.z; dy[7] = d1.w;
     }
 #pragma unroll
@@ -356,8 +333,8 @@ __global__ __launch_bounds__(256) void k_tcn_bwd1(TcnLayerArgs a) {
       dout[c] = DROP ? (((o.keep >> c) & 1u) ? dz[c] * a.scale : 0.f) : dz[c];
     }
     if (a.dX && o.live) {
-      rg_st4(a.dX + (int64_t)o.r * RG_C + c0, f32x4{dz[0], dz[1], dz[2], dz[3]});
-      rg_st4(a.dX + (int64_t)o.r * RG_C + c0 + 4, f32x4{dz[4], dz[5], dz[6], dz[7]});
+      st4(a.dX + (int64_t)o.r * RG_C + c0, f32x4{dz[0], dz[1], dz[2], dz[3]});
+      st4(a.dX + (int64_t)o.r * RG_C + c0 + 4, f32x4{dz[4], dz[5], dz[6], dz[7]});
     }
     __syncthreads();                                     // s1 / s2 have been read
 #pragma unroll
@@ -370,7 +347,7 @@ __global__ __launch_bounds__(256) void k_tcn_bwd1(TcnLayerArgs a) {
 #pragma unroll 4
     for (int co = 0; co < RG_C; ++co) {
       const float dv = s.p[co * RG_PITCH + lane];
-      const f32x4 w0 = rg_ld4(s.wp + co * RG_C + c0), w1 = rg_ld4(s.wp + co * RG_C + c0 + 4);
+      const f32x4 w0 = ld4(s.wp + co * RG_C + c0), w1 = ld4(s.wp + co * RG_C + c0 + 4);
       dh[0] = __builtin_fmaf(w0.x, dv, dh[0]); dh[1] = __builtin_fmaf(w0.y, dv, dh[1]);
       dh[2] = __builtin_fmaf(w0.z, dv, dh[2]); dh[3] = __builtin_fmaf(w0.w, dv, dh[3]);
       dh[4] = __builtin_fmaf(w1.x, dv, dh[4]); dh[5] = __builtin_fmaf(w1.y, dv, dh[5]);
@@ -382,8 +359,8 @@ __global__ __launch_bounds__(256) void k_tcn_bwd1(TcnLayerArgs a) {
       s.q[(c0 + c) * RG_PITCH + lane] = dh[c];
     }
     if (a.dH && o.live) {
-      rg_st4(a.dH + (int64_t)o.r * RG_C + c0, f32x4{dh[0], dh[1], dh[2], dh[3]});
-      rg_st4(a.dH + (int64_t)o.r * RG_C + c0 + 4, f32x4{dh[4], dh[5], dh[6], dh[7]});
+      st4(a.dH + (int64_t)o.r * RG_C + c0, f32x4{dh[0], dh[1], dh[2], dh[3]});
+      st4(a.dH + (int64_t)o.r * RG_C + c0 + 4, f32x4{dh[4], dh[5], dh[6], dh[7]});
     }
     if (want_part) {
 #pragma unroll
@@ -455,7 +432,7 @@ __global__ __launch_bounds__(256) void k_tcn_bwd2(TcnLayerArgs a) {
     const int f = w * 6 + q, tap = f >> 3, c4 = (f & 7) * 4;
     const int64_t tt = (int64_t)t - (int64_t)(tap - 1) * a.dil;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (live && tt >= 0 && tt < a.T0) v = rg_ld4(a.dH + ((int64_t)r - (int64_t)(tap - 1) * a.dil) * RG_C + c4);
+    if (live && tt >= 0 && tt < a.T0) v = ld4(a.dH + ((int64_t)r - (int64_t)(tap - 1) * a.dil) * RG_C + c4);
     float* dst = s_d + (tap * RG_C + c4) * RG_PITCH + lane;
     dst[0] = v.x; dst[RG_PITCH] = v.y; dst[2 * RG_PITCH] = v.z; dst[3 * RG_PITCH] = v.w;
   }
@@ -466,7 +443,7 @@ __global__ __launch_bounds__(256) void k_tcn_bwd2(TcnLayerArgs a) {
 #pragma unroll 4
   for (int k = 0; k < 3 * RG_C; ++k) {
     const float dv = s_d[k * RG_PITCH + lane];
-    const f32x4 w0 = rg_ld4(s_w + k * RG_C + c0), w1 = rg_ld4(s_w + k * RG_C + c0 + 4);
+    const f32x4 w0 = ld4(s_w + k * RG_C + c0), w1 = ld4(s_w + k * RG_C + c0 + 4);
     acc[0] = __builtin_fmaf(w0.x, dv, acc[0]); acc[1] = __builtin_fmaf(w0.y, dv, acc[1]);
     acc[2] = __builtin_fmaf(w0.z, dv, acc[2]); acc[3] = __builtin_fmaf(w0.w, dv, acc[3]);
     acc[4] = __builtin_fmaf(w1.x, dv, acc[4]); acc[5] = __builtin_fmaf(w1.y, dv, acc[5]);
@@ -474,9 +451,9 @@ __global__ __launch_bounds__(256) void k_tcn_bwd2(TcnLayerArgs a) {
   }
   if (!live) return;
   float* dst = a.dX + (int64_t)r * RG_C + c0;
-  const f32x4 z0 = rg_ld4(dst), z1 = rg_ld4(dst + 4);
-  rg_st4(dst, f32x4{z0.x + acc[0], z0.y + acc[1], z0.z + acc[2], z0.w + acc[3]});
-  rg_st4(dst + 4, f32x4{z1.x + acc[4], z1.y + acc[5], z1.z + acc[6], z1.w + acc[7]});
+  const f32x4 z0 = ld4(dst), z1 = ld4(dst + 4);
+  st4(dst, f32x4{z0.x + acc[0], z0.y + acc[1], z0.z + acc[2], z0.w + acc[3]});
+  st4(dst + 4, f32x4{z1.x + acc[4], z1.y + acc[5], z1.z + acc[6], z1.w + acc[7]});
 }
 
 __global__ __launch_bounds__(256) void k_rg_reduce(const float* __restrict__ part, int nparts, TcnLayerOuts o, int accumulate) {
@@ -490,25 +467,9 @@ __global__ __launch_bounds__(256) void k_rg_reduce(const float* __restrict__ par
   else if (i < RG_P_LNB) out = o.dlnw ? o.dlnw + (i - RG_P_LNW) : nullptr;
   else out = o.dlnb ? o.dlnb + (i - RG_P_LNB) : nullptr;
   if (!out) return;
-  const float sum = rg_tree_sum(part, nparts, (int64_t)RG_P_N, i);
+  const float sum = blocked_sum(part, nparts, (int64_t)RG_P_N, i);
   *out = accumulate ? *out + sum : sum;
 }
-
-// phase 1 needs more than the 64 KiB of LDS a launch gets by default: the kernel's limit is raised once per device
-template <bool DROP>
-static int rg_raise_lds() {
-  static bool have[64] = {};
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !have[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tcn_bwd1<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(RG_LDS_BWD * sizeof(float))));
-    if (dev >= 0 && dev < 64) have[dev] = true;
-  }
-  return 0;
-}
-
-static inline bool rg_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 static int tcn_check(const char* what, int B, int T0, int dil, float p, int layer, int b0) {
   DCF_CHECK(B > 0 && T0 > 0, "%s: empty batch (B = %d, T0 = %d)", what, B, T0);
@@ -552,7 +513,7 @@ int dcf_op_refine_in(const float* logits1, const uint8_t* mask0, const float* W_
   DCF_CHECK(logits1 && W_in && b_in && H, "dcf_op_refine_in: null argument");
   RefineInArgs a{};
   if (refine_in_fill("dcf_op_refine_in", a, B, T0, L)) return -1;
-  DCF_CHECK(rg_aligned16(b_in) && rg_aligned16(H), "dcf_op_refine_in: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(b_in) && aligned16(H), "dcf_op_refine_in: pointers must be 16-byte aligned");
   a.logits1 = logits1; a.mask0 = mask0; a.W = W_in; a.b = b_in; a.H = H;
   const int64_t n = (int64_t)a.rows * (RG_C / 4);
   hipLaunchKernelGGL(k_refine_in_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -568,7 +529,7 @@ int dcf_op_refine_in_bwd(const float* logits1, const uint8_t* mask0, const float
   DCF_CHECK(!dW_in || logits1, "dcf_op_refine_in_bwd: dW_in needs logits1");
   RefineInArgs a{};
   if (refine_in_fill("dcf_op_refine_in_bwd", a, B, T0, L)) return -1;
-  DCF_CHECK(rg_aligned16(dH), "dcf_op_refine_in_bwd: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(dH), "dcf_op_refine_in_bwd: pointers must be 16-byte aligned");
   if (!dlogits1 && !dW_in && !db_in) return 0;
   a.logits1 = logits1; a.mask0 = mask0; a.W = W_in; a.dH = dH;
   const int slices = (a.rows + RG_SLICE_ROWS - 1) / RG_SLICE_ROWS;                  // a fixed function of the row count
@@ -592,7 +553,7 @@ int dcf_op_tcn_layer(const float* X, const uint8_t* mask, const float* Wd, const
                      int32_t layer, int32_t b0, void* stream) {
   DCF_CHECK(X && Wd && bd && Wp && bp && ln_w && ln_b && Y, "dcf_op_tcn_layer: null argument");
   if (tcn_check("dcf_op_tcn_layer", B, T0, dilation, p, layer, b0)) return -1;
-  DCF_CHECK(rg_aligned16(X) && rg_aligned16(Y) && rg_aligned16(ln_w) && rg_aligned16(ln_b), "dcf_op_tcn_layer: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(X) && aligned16(Y) && aligned16(ln_w) && aligned16(ln_b), "dcf_op_tcn_layer: pointers must be 16-byte aligned");
   TcnLayerArgs a{};
   tcn_fill(a, X, mask, Wd, bd, Wp, bp, ln_w, ln_b, B, T0, dilation, seed, p, layer, b0);
   a.Y = Y;
@@ -611,19 +572,19 @@ int dcf_op_tcn_layer_bwd(const float* X, const uint8_t* mask, const float* Wd, c
   hipStream_t st = (hipStream_t)stream;
   DCF_CHECK(X && Wd && bd && Wp && bp && ln_w && ln_b && dY, "dcf_op_tcn_layer_bwd: null argument");
   if (tcn_check("dcf_op_tcn_layer_bwd", B, T0, dilation, p, layer, b0)) return -1;
-  DCF_CHECK(rg_aligned16(X) && rg_aligned16(dY) && rg_aligned16(dX), "dcf_op_tcn_layer_bwd: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(X) && aligned16(dY) && aligned16(dX), "dcf_op_tcn_layer_bwd: pointers must be 16-byte aligned");
   const bool want_part = dWd || dbd || dWp || dbp || dln_w || dln_b;
   if (!dX && !want_part) return 0;
   TcnLayerArgs a{};
   tcn_fill(a, X, mask, Wd, bd, Wp, bp, ln_w, ln_b, B, T0, dilation, seed, p, layer, b0);
   a.dY = dY; a.dX = dX; a.want_wd = dWd != nullptr; a.want_wp = dWp != nullptr;
-  if (p > 0.f ? rg_raise_lds<true>() : rg_raise_lds<false>()) return -1;
+  constexpr size_t lds = RG_LDS_BWD * sizeof(float);    // phase 1 needs more than the 64 KiB of LDS a launch gets by default
+  if (p > 0.f ? raise_lds_limit<&k_tcn_bwd1<true>>(lds) : raise_lds_limit<&k_tcn_bwd1<false>>(lds)) return -1;
   const int slices = (a.rows + RG_SLICE_ROWS - 1) / RG_SLICE_ROWS;                  // a fixed function of the row count
   StreamScratch sc(st);
   if (dX && sc.take(&a.dH, (size_t)a.rows * RG_C)) return -1;
   if (want_part && sc.take(&a.part, (size_t)slices * RG_P_N)) return -1;
   int rc = 0;
-  const size_t lds = RG_LDS_BWD * sizeof(float);
   if (p > 0.f) hipLaunchKernelGGL(k_tcn_bwd1<true>, dim3(slices), dim3(256), lds, st, a);
   else hipLaunchKernelGGL(k_tcn_bwd1<false>, dim3(slices), dim3(256), lds, st, a);
   if (dX) hipLaunchKernelGGL(k_tcn_bwd2, dim3((a.rows + RG_TILE - 1) / RG_TILE), dim3(256), 0, st, a);

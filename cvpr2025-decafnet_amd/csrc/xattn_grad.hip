@@ -13,12 +13,11 @@
 //   load  : thread (row, channel quad) brings scale q and dO of the batch into LDS, one 16-byte load each;
 //   row   : a wave per row, a lane per key: the two dot products against the lane's own K / V row (q, dO are LDS broadcasts), the
 //           softmax and delta as wave reductions on DPP; p and dS of the row go to LDS.  The exponential carries its rounding residual
-//           (exp_res, as attn_grad.hip).  delta comes from p and dP, not from a stored O: with one key p = 1, delta = dP and dS = 0 exactly;
+//           (exp_res, grad_common.h).  delta comes from p and dP, not from a stored O: with one key p = 1, delta = dP and dS = 0 exactly;
 //   sum   : thread (row, channel quad) forms dQ of the batch (ascending j); thread (key group, channel quad) adds the batch's
 //           dS q and p dO into its dK / dV accumulators -- d / 16 keys x 4 channels each, in registers for the whole slice, ascending t.
-// At the end the accumulators go to scratch as the slice's partial; k_xg_reduce adds the slices of a sequence in a fixed blocked order
-// (balanced trees over 8 parts, over 8 of those, then the groups of 64 in order: the summation of k_cg_reduce / k_eg_reduce).  No
-// floating-point atomics, neither global nor LDS; the slicing is a constant, not a function of the device: results are bit-identical
+// At the end the accumulators go to scratch as the slice's partial; k_xg_reduce adds the slices of a sequence in the fixed blocked
+// order of blocked_sum (grad_common.h).  No floating-point atomics, neither global nor LDS; the slicing is a constant, not a function of the device: results are bit-identical
 // from run to run, and every product has dO as one factor, so a power-of-two scale of dO scales the results by exactly that.
 //
 // Arithmetic: fp32 on the vector ALU, five Lk x d products per row and head (scores, dP, dQ, dK, dV) = 10 Lk C flops per row against
@@ -31,14 +30,10 @@
 #include <math.h>
 
 #include "../../include/decafnet_hip.h"
-#include "common.h"
+#include "grad_common.h"
 #include "xattn_grad.h"
 
 namespace dcf {
-
-__device__ __forceinline__ f32x4 xg_ld4(const float* __restrict__ p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void xg_st4(float* __restrict__ p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 xg_zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 // acc + s v and s v with the four channels written out: a vector-typed `s * v` lowers to packed fp32 instructions that broadcast the
 // scalar through op_sel, the form tools/isa_gate.py keeps out of every object (profiles/r04_pkfma_hazard.md)
@@ -46,23 +41,6 @@ __device__ __forceinline__ f32x4 xg_fma_s(float s, const f32x4& v, const f32x4& 
   return f32x4{__builtin_fmaf(s, v.x, acc.x), __builtin_fmaf(s, v.y, acc.y), __builtin_fmaf(s, v.z, acc.z), __builtin_fmaf(s, v.w, acc.w)};
 }
 __device__ __forceinline__ f32x4 xg_mul_s(float s, const f32x4& v) { return f32x4{s * v.x, s * v.y, s * v.z, s * v.w}; }
-
-// the 4-channel partial of a dot product with its contraction written out (dotp of attn_grad.hip)
-__device__ __forceinline__ float xg_dotp(const f32x4& a, const f32x4& b) {
-  return __builtin_fmaf(a.x, b.x, a.y * b.y) + __builtin_fmaf(a.z, b.z, a.w * b.w);
-}
-
-// exp(x), x <= 0: v_exp_f32 of the rounded product x * log2(e), times 1 + ln 2 * (what the rounding of the product and of the
-// constant dropped) -- exp_res of attn_grad.hip: dS = p (dP - delta) is a difference, and the gradient rule leaves ~2^-20 of the
-// largest element for everything
-__device__ __forceinline__ float xg_exp_res(float x) {
-  constexpr float L2E = 1.44269504088896340736f, L2E_LO = 1.925963033500003e-8f, LN2 = 0.69314718055994530942f;
-  x = fmaxf(x, -1e5f);
-  const float t = x * L2E;
-  const float r = __builtin_fmaf(x, L2E_LO, __builtin_fmaf(x, L2E, -t));
-  const float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, r * LN2, e);
-}
 
 // ------------------------------------------------------------------------------------------
 // cross attention backward
@@ -96,8 +74,8 @@ __global__ __launch_bounds__(256) void k_xattn_bwd(XAttnGradArgs p) {
   for (int i = tid; i < Lk * QN; i += 256) {
     const int j = i / QN, c = 4 * (i - j * QN);
     const int64_t src = ((int64_t)b * Lk + j) * C + h * D + c;
-    xg_st4(Ks + j * KP + c, xg_mul_s(scale, xg_ld4(p.K + src)));
-    xg_st4(Vs + j * KP + c, xg_ld4(p.V + src));
+    st4(Ks + j * KP + c, xg_mul_s(scale, ld4(p.K + src)));
+    st4(Vs + j * KP + c, ld4(p.V + src));
   }
   const bool valid = lane < Lk && (!p.kvmask || p.kvmask[(int64_t)b * Lk + (lane < Lk ? lane : 0)] != 0);
   const int jr = lane < Lk ? lane : Lk - 1;           // lanes beyond the text read an existing row and contribute 0
@@ -106,20 +84,20 @@ __global__ __launch_bounds__(256) void k_xattn_bwd(XAttnGradArgs p) {
 
   f32x4 dk[NK], dv[NK];
 #pragma unroll
-  for (int i = 0; i < NK; ++i) { dk[i] = xg_zero4(); dv[i] = xg_zero4(); }
+  for (int i = 0; i < NK; ++i) { dk[i] = zero4(); dv[i] = zero4(); }
 
   const int t0 = s * XG_SLICE_ROWS, t_end = t0 + XG_SLICE_ROWS < T ? t0 + XG_SLICE_ROWS : T;
   for (int tb = t0; tb < t_end; tb += R) {
     const int nr = t_end - tb < R ? t_end - tb : R;
     const int64_t row = (int64_t)b * T + tb + rr;
     // load
-    f32x4 q4 = xg_zero4(), g4 = xg_zero4();
+    f32x4 q4 = zero4(), g4 = zero4();
     if (rr < nr) {
-      q4 = xg_mul_s(scale, xg_ld4(p.Q + row * C + h * D + c4));
-      g4 = xg_ld4(p.dO + row * C + h * D + c4);
+      q4 = xg_mul_s(scale, ld4(p.Q + row * C + h * D + c4));
+      g4 = ld4(p.dO + row * C + h * D + c4);
     }
-    xg_st4(qs + rr * D + c4, q4);
-    xg_st4(gs + rr * D + c4, g4);
+    st4(qs + rr * D + c4, q4);
+    st4(gs + rr * D + c4, g4);
     __syncthreads();                                  // (the first pass: K / V are staged too)
     // row
     for (int r = wave; r < nr; r += 4) {
@@ -127,14 +105,14 @@ __global__ __launch_bounds__(256) void k_xattn_bwd(XAttnGradArgs p) {
       const float* gr = gs + r * D;
       float sc = 0.f, dp = 0.f;
 #pragma unroll
-      for (int c = 0; c < D; c += 4) sc += xg_dotp(xg_ld4(qr + c), xg_ld4(kr + c));
+      for (int c = 0; c < D; c += 4) sc += dotp(ld4(qr + c), ld4(kr + c));
       if (want_ds) {
 #pragma unroll
-        for (int c = 0; c < D; c += 4) dp += xg_dotp(xg_ld4(gr + c), xg_ld4(vr + c));
+        for (int c = 0; c < D; c += 4) dp += dotp(ld4(gr + c), ld4(vr + c));
       }
       sc = valid ? sc : -INFINITY;
       const float m = wave_max(sc);
-      const float e = valid ? xg_exp_res(sc - m) : 0.f;
+      const float e = valid ? exp_res(sc - m) : 0.f;
       const float il = 1.0f / wave_sum(e);            // a sequence without a valid key: 0 / 0, undefined as in the forward
       const float pj = e * il;
       const float delta = wave_sum(pj * dp);
@@ -144,13 +122,13 @@ __global__ __launch_bounds__(256) void k_xattn_bwd(XAttnGradArgs p) {
     __syncthreads();
     // sum
     if (p.dQ && rr < nr) {
-      f32x4 acc = xg_zero4();
-      for (int j = 0; j < Lk; ++j) acc = xg_fma_s(Ss[rr * 64 + j], xg_ld4(Ks + j * KP + c4), acc);
-      xg_st4(p.dQ + row * C + h * D + c4, xg_mul_s(scale, acc));
+      f32x4 acc = zero4();
+      for (int j = 0; j < Lk; ++j) acc = xg_fma_s(Ss[rr * 64 + j], ld4(Ks + j * KP + c4), acc);
+      st4(p.dQ + row * C + h * D + c4, xg_mul_s(scale, acc));
     }
     if (want_k || want_v) {
       for (int r = 0; r < nr; ++r) {
-        const f32x4 qv = xg_ld4(qs + r * D + c4), gv = xg_ld4(gs + r * D + c4);
+        const f32x4 qv = ld4(qs + r * D + c4), gv = ld4(gs + r * D + c4);
 #pragma unroll
         for (int i = 0; i < NK; ++i) {
           const int j = rr + R * i;
@@ -166,55 +144,28 @@ __global__ __launch_bounds__(256) void k_xattn_bwd(XAttnGradArgs p) {
     const int j = rr + R * i;
     if (j < Lk) {
       const int64_t dst = (((int64_t)b * p.S + s) * Lk + j) * C + h * D + c4;
-      if (want_k) xg_st4(p.partK + dst, xg_mul_s(scale, dk[i]));
-      if (want_v) xg_st4(p.partV + dst, dv[i]);
+      if (want_k) st4(p.partK + dst, xg_mul_s(scale, dk[i]));
+      if (want_v) st4(p.partV + dst, dv[i]);
     }
   }
 }
 
-// out[b][i] = sum_s part[b][s][i], i < per = Lk C, in a fixed order: balanced trees over 8 slices, over 8 of those, then the groups
-// of 64 in order
+// out[b][i] = sum_s part[b][s][i], i < per = Lk C, the slices in the fixed blocked order of blocked_sum (grad_common.h)
 __global__ __launch_bounds__(256) void k_xg_reduce(const float* __restrict__ part, float* __restrict__ out, int S, int64_t per, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int64_t b = i / per;
   const float* src = part + b * S * per + (i - b * per);
   float sum = 0.f;
-  for (int g2 = 0; g2 < S; g2 += 64) {
-    float l1[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      float v[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const int sl = g2 + 8 * u + t;
-        v[t] = sl < S ? src[(int64_t)sl * per] : 0.f;
-      }
-      l1[u] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    sum += ((l1[0] + l1[1]) + (l1[2] + l1[3])) + ((l1[4] + l1[5]) + (l1[6] + l1[7]));
-  }
+  DCF_BLOCKED_SUM(sum, src, S, per, 0);
   out[i] = sum;
 }
 
-// d = 128 with more than 45 keys needs more than the 64 KiB of LDS a launch gets by default: the kernel's limit is raised once per
-// device (the attribute belongs to the device's copy of the kernel)
-template <int D>
-static int xg_raise_lds(size_t bytes) {
-  static size_t have[64] = {};
-  int dev = 0;
-  DCF_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || bytes > have[dev]) {
-    DCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_xattn_bwd<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    if (dev >= 0 && dev < 64) have[dev] = bytes;
-  }
-  return 0;
-}
-
+// d = 128 with more than 45 keys needs more than the 64 KiB of LDS a launch gets by default
 template <int D>
 static int xg_launch(const XAttnGradArgs& a, hipStream_t st) {
   const size_t lds = xg_lds_bytes<D>(a.Lk);
-  if (lds > 64 * 1024) { if (int rc = xg_raise_lds<D>(lds)) return rc; }
+  if (lds > 64 * 1024) { if (int rc = raise_lds_limit<&k_xattn_bwd<D>>(lds)) return rc; }
   hipLaunchKernelGGL(k_xattn_bwd<D>, dim3(a.S, a.heads, a.B), dim3(256), lds, st, a);
   return 0;
 }
@@ -313,8 +264,6 @@ static int adaln_launch(const AdaLnArgs& a, hipStream_t st) {
   return 0;
 }
 
-static inline bool xg_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace dcf
 
 using namespace dcf;
@@ -335,7 +284,7 @@ int dcf_op_xattn_bwd(const float* Q, const float* K, const float* V, const uint8
             heads);
   DCF_CHECK((int64_t)B * T < (1ll << 31) - 64 && B <= 65535, "dcf_op_xattn_bwd: %lld rows in %d sequences (< 2^31 rows, <= 65535 sequences)",
             (long long)B * T, B);
-  DCF_CHECK(xg_aligned16(Q) && xg_aligned16(K) && xg_aligned16(V) && xg_aligned16(dO) && xg_aligned16(dQ) && xg_aligned16(dK) && xg_aligned16(dV),
+  DCF_CHECK(aligned16(Q) && aligned16(K) && aligned16(V) && aligned16(dO) && aligned16(dQ) && aligned16(dK) && aligned16(dV),
             "dcf_op_xattn_bwd: pointers must be 16-byte aligned");
   if (!dQ && !dK && !dV) return 0;
   XAttnGradArgs a{};
@@ -372,7 +321,7 @@ static int adaln_check(const char* what, int rows, int C) {
 int dcf_op_adaln(const float* X, const uint8_t* mask, const float* H, float* Y, int32_t rows, int32_t C, int32_t norm, void* stream) {
   DCF_CHECK(X && H && Y, "dcf_op_adaln: null argument");
   if (adaln_check("dcf_op_adaln", rows, C)) return -1;
-  DCF_CHECK(xg_aligned16(X) && xg_aligned16(H) && xg_aligned16(Y), "dcf_op_adaln: pointers must be 16-byte aligned");
+  DCF_CHECK(aligned16(X) && aligned16(H) && aligned16(Y), "dcf_op_adaln: pointers must be 16-byte aligned");
   AdaLnArgs a{};
   a.X = X; a.mask = mask; a.H = H; a.Y = Y; a.rows = rows; a.C = C; a.norm = norm != 0;
   return adaln_launch<false>(a, (hipStream_t)stream);
@@ -383,7 +332,7 @@ int dcf_op_adaln_bwd(const float* X, const uint8_t* mask, const float* H, const 
   DCF_CHECK(X && dY, "dcf_op_adaln_bwd: null argument");
   DCF_CHECK(!dX || H, "dcf_op_adaln_bwd: dX needs H");
   if (adaln_check("dcf_op_adaln_bwd", rows, C)) return -1;
-  DCF_CHECK(xg_aligned16(X) && xg_aligned16(H) && xg_aligned16(dY) && xg_aligned16(dX) && xg_aligned16(dH),
+  DCF_CHECK(aligned16(X) && aligned16(H) && aligned16(dY) && aligned16(dX) && aligned16(dH),
             "dcf_op_adaln_bwd: pointers must be 16-byte aligned");
   if (!dX && !dH) return 0;
   AdaLnArgs a{};
