@@ -205,6 +205,23 @@ CLOCK_SIGNATURES = {
 }
 
 
+# the half-feature extension (include/decafnet_hip_half.h, dcf_half_ext_version): same shared object, an eighth table -- the seven
+# above are frozen (tests/test_half_features_cpu.py checks this table against its header).  A half operand is the device address of
+# IEEE binary16 values (``const uint16_t*``); ``text`` / ``text_mask`` / ``text_len`` / ``nq_per_video`` are HOST arrays as in SIGNATURES.
+c_f16p = ctypes.c_void_p
+HALF_SIGNATURES = {
+    'dcf_half_ext_version': (i32, []),
+    'dcf_forward_eval_h': (i32, [vp, c_f16p, c_f16p, c_u8p, i64, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                 ctypes.POINTER(i32), c_f32p, c_f32p, c_f32p, c_u8p, vp]),
+    'dcf_forward_eval_videos_h': (i32, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), i64, ctypes.POINTER(i32),
+                                        ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(vp),
+                                        c_f32p, c_f32p, c_u8p, vp]),
+    'dcf_op_linear_cm_split_h': (i32, [c_f16p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]),
+    'dcf_op_linear_cm_split_ld_h': (i32, [c_f16p, i64, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]),
+    'dcf_op_sidekick_h': (i32, [c_f16p, c_f32p, c_f32p, i32, i32, i32, i32, vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -216,7 +233,8 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
-                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(CLOCK_SIGNATURES.items()):
+                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(CLOCK_SIGNATURES.items()) + \
+                list(HALF_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -117,6 +117,9 @@ struct dcf_model {
   int64_t text_pe_L = 0;
   char* text_ws = nullptr;
   size_t text_ws_bytes = 0;
+  // half features (decafnet_hip_half.h) of a forward that cannot read them natively: their fp32 copies, vid then shallow of every video
+  char* half_ws = nullptr;
+  size_t half_ws_bytes = 0;
 
   // workspace
   char* arena = nullptr;
@@ -205,6 +208,7 @@ struct VideoSet {
   const float* text_cls[DCF_MAX_VIDEOS];      // (nq[v], D); with gate_override: the gate (nq, T)
   int nq[DCF_MAX_VIDEOS];
   float* logits1_out = nullptr;               // optional (nq, S): the logits of the first cls_head (fpn_logits1, model.py:445,471)
+  bool half = false;                          // vid[] / shallow[] carry the addresses of IEEE binary16 values (decafnet_hip_half.h)
 };
 
 // what a forward reads besides the videos and where its results go: passed unchanged from the entry points down to forward()
@@ -288,6 +292,9 @@ RefineArgs refine_args(dcf_model* m);
 int forward(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall& fc, hipStream_t st);
 void launch_masks_out(const uint8_t* mask_all, uint8_t* out, const LevelTable* lt, const unsigned* status, float* logits, int rows,
                       hipStream_t st);
+
+// ---- half.hip
+int launch_half_to_f32(const uint16_t* src, float* dst, int64_t n, hipStream_t st);
 
 // ---- engine_hybrid.hip
 void free_hybrid(dcf_model* m);

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "engine.h"
+#include "../../include/decafnet_hip_half.h"
 
 namespace dcf {
 
@@ -71,14 +72,58 @@ __global__ void k_gather_masks(MaskPtrs mp, uint8_t* __restrict__ dst, int T0) {
   if (t < T0) dst[(size_t)blockIdx.y * T0 + t] = mp.p[blockIdx.y][t];
 }
 
-int forward(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall& fc, hipStream_t st) {
+// Half features (VideoSet::half): read as they are where the kernels in front can -- the split-operand vid_map GEMMs (with the scores on
+// their side or the scoring kernels beside them) --, otherwise upcast once into m->half_ws and handed on as an fp32 video set.
+// *use = the set the forward goes on with.  dcf_debug_set_option("half_native", 0 / 1 / 2): never / where possible / or fail.
+static int half_features(dcf_model* m, const VideoSet& in, int T0, const ForwardCall& fc, hipStream_t st, VideoSet& f32, const VideoSet** use) {
   const dcf_config& c = m->cfg;
+  DCF_CHECK(!fc.gate && !in.logits1_out && m->hyb_levels == 0, "half features: the eval forwards dcf_forward_eval_h / dcf_forward_eval_videos_h only");
+  const int want = debug_option("half_native", 1);
+  auto image_ok = [&](const float* w) { return !w || (m->wsplit.count(w) && m->wsplit_ldw[w] == m->vid_ldw); };
+  bool native = want != 0 && m->gemm_terms != 0 && c.E % 128 == 0 && T0 % 4 == 0 && image_ok(m->vid_w1) && image_ok(m->vid_w2) && (m->vid_w1 || m->vid_w2);
+  if (m->vid_w1 && m->vid_w2) native = native && m->wsplit_terms[m->vid_w1] == m->wsplit_terms[m->vid_w2];
+  for (int v = 0; v < in.nvid; ++v)
+    native = native && ((reinterpret_cast<uintptr_t>(in.vid[v]) | reinterpret_cast<uintptr_t>(in.shallow[v])) & 7) == 0;
+  DCF_CHECK(native || want != 2, "half features: this forward cannot read them natively (gemm_mode fp32, E %% 128 != 0, T %% 4 != 0 or a feature "
+                                 "pointer that is not 8-byte aligned) and the option half_native = 2 forbids the upcast");
+  if (native) { *use = &in; return 0; }
+  const size_t per = ((size_t)c.D * T0 * sizeof(float) + 255) & ~(size_t)255;
+  const size_t need = per * 2 * in.nvid;
+  if (need > m->half_ws_bytes) {
+    DCF_CHECK(!m->capturing, "internal: workspace growth during graph capture");
+    drop_graph(m, true);                          // (a captured graph bakes the copies' addresses in)
+    DCF_HIP(hipStreamSynchronize(st));
+    if (m->half_ws) DCF_HIP(hipFree(m->half_ws));
+    m->half_ws = nullptr; m->half_ws_bytes = 0;
+    DCF_HIP(hipMalloc(&m->half_ws, need));
+    m->half_ws_bytes = need;
+  }
+  f32 = in;
+  f32.half = false;
+  for (int v = 0; v < in.nvid; ++v) {
+    float* dv = reinterpret_cast<float*>(m->half_ws + per * (2 * v));
+    float* ds = reinterpret_cast<float*>(m->half_ws + per * (2 * v + 1));
+    TRY(launch_half_to_f32(reinterpret_cast<const uint16_t*>(in.vid[v]), dv, (int64_t)c.D * T0, st));
+    TRY(launch_half_to_f32(reinterpret_cast<const uint16_t*>(in.shallow[v]), ds, (int64_t)c.D * T0, st));
+    f32.vid[v] = dv; f32.shallow[v] = ds;
+  }
+  *use = &f32;
+  return 0;
+}
+
+int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCall& fc, hipStream_t st) {
+  const dcf_config& c = m->cfg;
+  VideoSet vs_f32;                                // half features this forward reads as fp32 copies (below)
+  const VideoSet* vsp = &vs_in;
+  DCF_CHECK(m->finalized, "dcf_forward_eval: model not finalized");
+  DCF_CHECK(T0 > 0 && nq > 0 && vs_in.nvid >= 1 && vs_in.nvid <= DCF_MAX_VIDEOS, "dcf_forward_eval: empty input");
+  if (vs_in.half) TRY(half_features(m, vs_in, T0, fc, st, vs_f32, &vsp));
+  const VideoSet& vs = *vsp;
+  const bool half_native = vs.half;               // the kernels that read the features read binary16
   const int E = c.E, D = c.D;
   const int L = m->hyb_levels > 0 ? m->hyb_levels : c.n_levels;      // dcf_hybrid_phase1: the pyramid up to the split level only
   const int nvid = vs.nvid;
   if (m->hyb) m->hyb->valid = false;              // the phases of a level-cut forward live in this workspace
-  DCF_CHECK(m->finalized, "dcf_forward_eval: model not finalized");
-  DCF_CHECK(T0 > 0 && nq > 0 && nvid >= 1 && nvid <= DCF_MAX_VIDEOS, "dcf_forward_eval: empty input");
   DCF_CHECK(!(fc.gate && nvid != 1), "the externally gated forward takes one video");
   int video_of[DCF_MAX_VIDEOS * 64];           // flat query -> video
   {
@@ -151,7 +196,7 @@ int forward(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall&
     }
     sa.nvid = nvid; sa.tn = b.tn; sa.partial = b.partial; sa.correl = b.correl; sa.D = D; sa.T = T0; sa.NQ = nq; sa.norm = c.norm;
     if (scores_on_gemm) TRY(launch_text_cls_norm(sa, st));
-    else TRY(launch_sidekick(sa, st));
+    else TRY(launch_sidekick(sa, st, half_native));
   }
   // Gate first, expert product second (model.py:531-543): `vid * all_weight` is zero outside the top-k blocks, so the rows of
   // W1 . vid under a closed gate are never used -- with every query of a video in THIS chunk (nq <= max_batch) the gate of all of them
@@ -171,7 +216,7 @@ int forward(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall&
     auto flush = [&]() -> int {
       if (ng == 0) return 0;
       for (int i = 0; i < ng; ++i) { g[i].ldw = m->vid_ldw; g[i].a_scale = 1.f; }
-      const int rc = run_gemm(m, g, ng, A_CHANMAJOR, st);
+      const int rc = run_gemm(m, g, ng, half_native ? A_CHANMAJOR_H : A_CHANMAJOR, st);
       ng = 0;
       return rc;
     };
@@ -218,7 +263,8 @@ int forward(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall&
         for (int v = 0; v < nvid; ++v) { zA[v] = vs.vid[v]; zC[v] = b.P1 + (size_t)v * T0 * E; zs[v] = b.tile_flags + (size_t)q_of[v] * nflags; zq[v] = vs.nq[v]; }
         // the profile prices this launch at the clips the gate keeps at least -- int(sratio n) of n blocks -- not at the full product:
         // the tiles it skips are work the reference does (on zeros) and this kernel does not
-        TRY(launch_gemm_split_z(base, nvid, zA, zC, zs, zq, m->wsplit_terms[m->vid_w1], st, std::min(1.0, std::max(0.0, (double)c.sratio))));
+        TRY(launch_gemm_split_z(base, nvid, zA, zC, zs, zq, m->wsplit_terms[m->vid_w1], st, std::min(1.0, std::max(0.0, (double)c.sratio)),
+                                half_native ? A_CHANMAJOR_H : A_CHANMAJOR));
       } else {
         for (int v = 0; v < nvid; ++v) TRY(expert_half(v, true));
         TRY(flush());
@@ -522,7 +568,10 @@ namespace dcf {
 // eager on the first call with a given argument set, capture + replay from the second identical call on
 static int forward_graph_on(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall& fc, hipStream_t st) {
   std::vector<uint64_t> key = {(uint64_t)vs.nvid, (uint64_t)T0, (uint64_t)nq, (uint64_t)vs.logits1_out,
-                               (uint64_t)fc.gate, (uint64_t)fc.logits, (uint64_t)fc.offsets, (uint64_t)fc.masks, (uint64_t)st, (uint64_t)m->pe, (uint64_t)m->pe_T};
+                               (uint64_t)fc.gate, (uint64_t)fc.logits, (uint64_t)fc.offsets, (uint64_t)fc.masks, (uint64_t)st, (uint64_t)m->pe, (uint64_t)m->pe_T,
+                               (uint64_t)(vs.half ? 1 : 0)};      // (the operand type of vid / shallow: an fp32 and a half forward never share a graph;
+                                                                  //  the half_native option needs no slot: every dcf_debug_set_option bumps option_epoch,
+                                                                  //  and forward_maybe_graph drops the captured graph before it gets here)
   for (int v = 0; v < vs.nvid; ++v) {
     key.push_back((uint64_t)vs.vid[v]); key.push_back((uint64_t)vs.shallow[v]); key.push_back((uint64_t)vs.mask[v]);
     key.push_back((uint64_t)vs.text_cls[v]); key.push_back((uint64_t)vs.nq[v]);
@@ -660,6 +709,36 @@ int dcf_forward_eval_videos(dcf_model* m, int32_t nvid, const float* const* vid,
   dcf::VideoSet vs;
   int nq = 0;
   if (dcf::fill_videos(vs, "dcf_forward_eval_videos", nvid, vid, shallow_vid, vid_mask, text_cls, nq_per_video, &nq)) return -1;
+  return dcf::forward_maybe_graph(m, vs, (int)T, nq, {text, text_mask, text_len, nullptr, logits_out, offsets_out, masks_out},
+                                  (hipStream_t)stream);
+}
+
+int dcf_forward_eval_h(dcf_model* m, const uint16_t* vid, const uint16_t* shallow_vid, const uint8_t* vid_mask, int64_t T,
+                       int32_t nq, const float* const* text, const uint8_t* const* text_mask, const int32_t* text_len,
+                       const float* text_cls, float* logits_out, float* offsets_out, uint8_t* masks_out, void* stream) {
+  DCF_CHECK(m && vid && shallow_vid && vid_mask && text && text_len && text_cls && logits_out && offsets_out && masks_out,
+            "dcf_forward_eval_h: null argument");
+  DCF_CHECK(T < (1ll << 24), "T too large");
+  dcf::VideoSet vs;
+  vs.nvid = 1; vs.vid[0] = reinterpret_cast<const float*>(vid); vs.shallow[0] = reinterpret_cast<const float*>(shallow_vid);
+  vs.mask[0] = vid_mask; vs.text_cls[0] = text_cls; vs.nq[0] = nq; vs.half = true;
+  return dcf::forward_maybe_graph(m, vs, (int)T, nq, {text, text_mask, text_len, nullptr, logits_out, offsets_out, masks_out},
+                                  (hipStream_t)stream);
+}
+
+int dcf_forward_eval_videos_h(dcf_model* m, int32_t nvid, const uint16_t* const* vid, const uint16_t* const* shallow_vid,
+                              const uint8_t* const* vid_mask, int64_t T, const int32_t* nq_per_video, const float* const* text,
+                              const uint8_t* const* text_mask, const int32_t* text_len, const float* const* text_cls,
+                              float* logits_out, float* offsets_out, uint8_t* masks_out, void* stream) {
+  DCF_CHECK(m && vid && shallow_vid && vid_mask && nq_per_video && text && text_len && text_cls && logits_out && offsets_out && masks_out,
+            "dcf_forward_eval_videos_h: null argument");
+  DCF_CHECK(nvid >= 1 && nvid <= dcf::DCF_MAX_VIDEOS, "dcf_forward_eval_videos_h: 1 .. %d videos per call", dcf::DCF_MAX_VIDEOS);
+  DCF_CHECK(T < (1ll << 24), "T too large");
+  dcf::VideoSet vs;
+  int nq = 0;
+  if (dcf::fill_videos(vs, "dcf_forward_eval_videos_h", nvid, reinterpret_cast<const float* const*>(vid),
+                       reinterpret_cast<const float* const*>(shallow_vid), vid_mask, text_cls, nq_per_video, &nq)) return -1;
+  vs.half = true;
   return dcf::forward_maybe_graph(m, vs, (int)T, nq, {text, text_mask, text_len, nullptr, logits_out, offsets_out, masks_out},
                                   (hipStream_t)stream);
 }

@@ -99,6 +99,7 @@ int run_gemm(dcf_model* m, GemmArgs* g, int count, GemmAMode mode, hipStream_t s
     g[i].status = m->status;
   }
   if (split && mode == A_CHANMAJOR && (g[0].N % 128 != 0 || g[0].M % 4 != 0)) split = false;
+  DCF_CHECK(split || mode != A_CHANMAJOR_H, "internal: a half operand needs the split-operand GEMM");
   for (int i = 0; i < count; ++i) DCF_CHECK(split || !(g[i].flags & G_ADALN), "internal: G_ADALN needs the split-operand GEMM");
   for (int i = 0; i < count; ++i) DCF_CHECK(split || !g[i].score_out, "internal: scores on the side need the split-operand GEMM");
   return split ? launch_gemm_split(g, count, mode, terms, st) : launch_gemm(g, count, mode, st);

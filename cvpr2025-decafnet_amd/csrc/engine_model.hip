@@ -139,6 +139,7 @@ static int free_model(dcf_model* m) {
   free_hybrid(m);                             // (the level-cut state of dcf_hybrid_phase1 / 2 / 3)
   if (m->arena) (void)hipFree(m->arena);
   if (m->text_ws) (void)hipFree(m->text_ws);
+  if (m->half_ws) (void)hipFree(m->half_ws);
   if (m->ev_in) (void)hipEventDestroy(m->ev_in);
   if (m->ev_out) (void)hipEventDestroy(m->ev_out);
   if (m->own) (void)hipStreamDestroy(m->own);
@@ -657,7 +658,7 @@ int dcf_model_set_dropout(dcf_model* m, float vid_proj_p, float vid_path_p, floa
 
 int dcf_debug_set_option(const char* name, int32_t value) {
   DCF_CHECK(name && *name, "dcf_debug_set_option: empty name");
-  static const char* known[] = {"dec_chain_min_rows", "enc_chain_min_rows", "enc_attn_min_rows", "fuse_scores", "tcn_frag", "gate_skip", "tcn_stack"};
+  static const char* known[] = {"dec_chain_min_rows", "enc_chain_min_rows", "enc_attn_min_rows", "fuse_scores", "tcn_frag", "gate_skip", "tcn_stack", "half_native"};
   bool ok = false;
   for (const char* k : known) ok = ok || strcmp(k, name) == 0;
   DCF_CHECK(ok, "dcf_debug_set_option: unknown option '%s'", name);

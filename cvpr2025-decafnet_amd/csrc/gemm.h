@@ -9,6 +9,8 @@ enum GemmAMode {
   A_ROWS = 0,      // A[m][k] = X[m*lda + k]                       (token-major activation)
   A_ROWS_TAP3 = 1, // A[m][tap*cin + c] = X[(m+tap-1)*lda + c] if neighbour usable else 0  (k3 conv, pad 1)
   A_CHANMAJOR = 2, // A[m][k] = X[k*lda + m]                       (reference (C,T) input layout)
+  A_CHANMAJOR_H = 3, // the same layout with X in IEEE binary16: GemmArgs::A (and launch_gemm_split_z's A[z]) carry the address of the
+                   // half values, lda counts halves.  Split tile kernels only (launch_gemm_split / launch_gemm_split_z); 8-byte aligned base
 };
 
 enum GemmFlags {
@@ -111,8 +113,9 @@ int launch_gemm_split(const GemmArgs* g, int count, GemmAMode mode, int nterms, 
 // one channel-major GEMM (base: W / Ws, shape, lda, ldc, skip_stride) over nz (A, C) pairs in one grid, each with its own row-tile
 // selection skip[z] / skip_nq[z] (GemmArgs::tile_skip; skip or skip[z] null = every tile); 64 x 256 tiles, N % 256 == 0, nz <= 16
 // work_fraction: what the per-launch profile counts as this launch's algorithmic work (a lower bound of the share of row tiles that run)
+// mode: A_CHANMAJOR, or A_CHANMAJOR_H with every A[z] the address of binary16 values
 int launch_gemm_split_z(const GemmArgs& base, int nz, const float* const* A, float* const* C, const uint8_t* const* skip, const int* skip_nq,
-                        int nterms, hipStream_t stream, double work_fraction = 1.0);
+                        int nterms, hipStream_t stream, double work_fraction = 1.0, GemmAMode mode = A_CHANMAJOR);
 // overflow: optional device word, bit 0 set if a weight does not fit the scaled fp16 range (f16x3 only)
 int launch_split_planes(const float* W, unsigned short* out, int N, int K, int64_t ldw, hipStream_t st, int nterms = GEMM_BF16X6,
                         unsigned* overflow = nullptr);

@@ -232,6 +232,8 @@ static int launch_cfg(const GemmBatch& b, int count, GemmAMode mode, hipStream_t
     case A_CHANMAJOR:
       hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, TM, TN, A_CHANMAJOR, BK>), grid, dim3(256), lds_km, stream, b);
       break;
+    default:
+      DCF_CHECK(false, "launch_gemm: the fp32 kernel has no A mode %d (half operands run on the split tile kernels)", (int)mode);
   }
   DCF_HIP(hipGetLastError());
   return 0;

@@ -33,6 +33,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SBK = 32;            // k per LDS tile
 constexpr int ROWB = 80;           // bytes per (plane, row): 64 data + 16 pad
@@ -80,6 +81,9 @@ __device__ __forceinline__ void split_a(float x0, float x1, float sa, unsigned& 
   if constexpr (NTERMS == T_F16) { split2_f16(x0, x1, sa, hi, mid); lo = 0u; }
   else split2(x0, x1, hi, mid, lo);
 }
+// the raw A registers of a channel-major tile as fp32 (A_CHANMAJOR_H: an exact upcast)
+__device__ __forceinline__ f32x4 raw_f32(f32x4 v) { return v; }
+__device__ __forceinline__ f32x4 raw_f32(f16x4 v) { return __builtin_convertvector(v, f32x4); }
 // activation pre-scale of a launch: 2^4 unless the caller knows better (GemmArgs::a_scale, a power of two)
 __device__ __forceinline__ float a_scale_of(const GemmArgs& p) { return p.a_scale > 0.f ? p.a_scale : F16_SA; }
 template <int NTERMS>
@@ -154,28 +158,37 @@ int launch_split_planes(const float* W, unsigned short* out, int N, int K, int64
 // the prefetch distance hides that latency.  Buffers are indexed statically (steps unrolled in groups of NST).
 // STATS = true: the instantiation whose epilogue writes / consumes row statistics (GemmArgs::stats_out / stats_in)
 // ALN = true (A_ROWS_TAP3): the A rows get LayerNorm + ReLU while they are staged (GemmArgs::a_stats)
-// SCORE = true (A_CHANMAJOR): the sidekick scores of the rows on the side (GemmArgs::score_out)
+// SCORE = true (A_CHANMAJOR / A_CHANMAJOR_H): the sidekick scores of the rows on the side (GemmArgs::score_out)
+// A_CHANMAJOR_H: X holds binary16 values, read as they are (8-byte loads of four rows at k and at k + 1).  f16x3: a half value times the
+// power-of-two a_scale IS the hi plane and the "mid" plane of the fp32 mode is exactly zero for it, so ONE A plane is kept in LDS and the
+// product a_mid . w_hi -- exact zeros into the accumulator -- is not issued: a_hi . w_mid, then a_hi . w_hi, the order of the fp32 mode
+// without its middle term.  bf16x6: the values are upcast while they are staged and split as the fp32 mode splits them.
 template <int WM, int WN, int TM, int TN, int AMODE, int NTERMS, bool LN = false, int NST = 3, bool STATS = false, bool ALN = false, bool SCORE = false>
 __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2 && TM * TN >= 4)) ? 2 : 3)) void gemm_bf16s_kernel(GemmBatch batch) {
   constexpr int NT = WM * WN * 64;                    // 4 or 8 wavefronts
   constexpr int BM = WM * TM * 32;
   constexpr int BN = WN * TN * 32;
   constexpr int NPL = NTERMS == 6 ? 3 : 2;            // planes used: hi, mid (, lo); T_F16: the two fp16 planes
+  constexpr bool CM = AMODE == A_CHANMAJOR || AMODE == A_CHANMAJOR_H;
+  constexpr bool HALF = AMODE == A_CHANMAJOR_H;
+  constexpr int APL = (HALF && NTERMS == T_F16) ? 1 : NPL;   // planes of the A tile (half input, f16x3: the values themselves)
+  using a_elem = std::conditional_t<HALF, _Float16, float>;
+  using a_raw = std::conditional_t<HALF, f16x4, f32x4>;      // four rows at one k
   constexpr int ACH = (BM * 4 + NT - 1) / NT;         // 8-float chunks of the A tile per thread (the last may be partial)
   constexpr bool APART = (BM * 4) % NT != 0;          // 3-wave workgroups: chunk ids >= BM * 4 do not exist
   constexpr int BLK = 2 * 3 * 64 * 8;                 // bf16 elements of one weight block (6 KiB)
   static_assert(WM * WN == 2 || WM * WN == 3 || WM * WN == 4 || WM * WN == 6 || WM * WN == 8, "2, 3, 4, 6 or 8 wavefronts");
-  static_assert(!(APART && AMODE == A_CHANMAJOR), "channel-major A needs a whole number of chunks per thread");
-  static_assert(AMODE == A_ROWS || AMODE == A_ROWS_TAP3 || AMODE == A_CHANMAJOR, "unknown A mode");
+  static_assert(!(APART && CM), "channel-major A needs a whole number of chunks per thread");
+  static_assert(AMODE == A_ROWS || AMODE == A_ROWS_TAP3 || CM, "unknown A mode");
 
   extern __shared__ unsigned char smem_b[];
-  unsigned char* As = smem_b;                          // [NPL][BM][ROWB]: the only LDS tile (A is shared by the N-waves)
+  unsigned char* As = smem_b;                          // [APL][BM][ROWB]: the only LDS tile (A is shared by the N-waves)
   // row-statistics block of the workgroup: behind the A tile and behind the epilogue's transpose tiles
-  constexpr int WG_OFF = (NPL * BM * ROWB > WM * WN * EPI_WAVE_FLOATS * 4 ? NPL * BM * ROWB : WM * WN * EPI_WAVE_FLOATS * 4);
+  constexpr int WG_OFF = (APL * BM * ROWB > WM * WN * EPI_WAVE_FLOATS * 4 ? APL * BM * ROWB : WM * WN * EPI_WAVE_FLOATS * 4);
   float* wg_stats = reinterpret_cast<float*>(smem_b + WG_OFF);
 
   GemmArgs p = (LN || batch.zcount > 0) ? batch.g[0] : (blockIdx.z == 0 ? batch.g[0] : (blockIdx.z == 1 ? batch.g[1] : batch.g[2]));
-  if constexpr (AMODE == A_CHANMAJOR && !SCORE && !LN) {
+  if constexpr (CM && !SCORE && !LN) {
     if (batch.zcount > 0) {                             // uniform: operand set blockIdx.z of the one GEMM (GemmBatch::zcount)
       const int z = blockIdx.z;
       p.A = gemm_zsel(batch.zA, z); p.C = gemm_zsel(batch.zC, z); p.tile_skip = gemm_zsel(batch.zskip, z); p.skip_nq = gemm_zsel(batch.zskip_nq, z);
@@ -187,7 +200,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
   int m0, n0;
   if (!tile_origin<BM, BN>(p, m0, n0)) return;
   const int M = p.M, K = p.K;
-  if constexpr (AMODE == A_CHANMAJOR && BM % 64 == 0 && !SCORE) {
+  if constexpr (CM && BM % 64 == 0 && !SCORE) {
     if (p.tile_skip) {                                 // uniform: row tiles no query of this video keeps (GemmArgs::tile_skip)
       const int f0 = m0 >> 6, f1 = min((m0 + BM + 63) >> 6, (M + 63) >> 6);
       unsigned any = 0;
@@ -224,7 +237,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
   }
   // SCORE: the text vectors in LDS behind the statistics block (read from the first store_a on, behind the K loop's first barrier);
   // per thread the partial sums of its 4 rows over its k pairs: sum of squares + one dot product per query
-  static_assert(!SCORE || (AMODE == A_CHANMAJOR && !ALN && !LN), "SCORE is a channel-major mode");
+  static_assert(!SCORE || (CM && !ALN && !LN), "SCORE is a channel-major mode");
   float* sc_tn = wg_stats + stats_lds_floats<WM, WN, TM>();
   const bool do_score = SCORE && p.score_out != nullptr && n0 == 0;         // uniform: the first column tile carries the scores
   f32x4 sc_ss[ACH], sc_dot[ACH][GEMM_SCORE_MAXQ];
@@ -241,16 +254,16 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
 
   // K-invariant addressing (see gemm.hip: nothing but 16-byte loads inside the K loop)
   // A_ROWS / TAP3: thread -> (row, 8-float piece); A_CHANMAJOR (A[m][k] = X[k*lda + m]): thread -> (k pair p, 4 rows)
-  const float* a_ptr[ACH];
+  const a_elem* a_ptr[ACH];
   unsigned a_flag[ACH];
 #pragma unroll
   for (int i = 0; i < ACH; ++i) {
     const int id = i * NT + tid;
-    if constexpr (AMODE == A_CHANMAJOR) {
+    if constexpr (CM) {
       const int pk = id & 15, m4 = id >> 4;
       const int m = m0 + m4 * 4;
       a_flag[i] = m < M ? 1u : 0u;                     // M % 4 == 0 (checked by the launcher)
-      a_ptr[i] = p.A + (int64_t)(2 * pk) * p.lda + (m < M ? m : 0);
+      a_ptr[i] = reinterpret_cast<const a_elem*>(p.A) + (int64_t)(2 * pk) * p.lda + (m < M ? m : 0);
     } else {
       const int row = id >> 2, c8 = id & 3;
       const int m = m0 + row;
@@ -260,7 +273,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
         else f = p.nbr[m];
       }
       a_flag[i] = f;
-      a_ptr[i] = p.A + (int64_t)(m < M ? m : 0) * p.lda + c8 * 8;
+      a_ptr[i] = reinterpret_cast<const a_elem*>(p.A) + (int64_t)(m < M ? m : 0) * p.lda + c8 * 8;
     }
   }
   // B fragments of this wave's TN column tiles: block (n32, kt) at ((n32 * KT + kt) * BLK), lane slot lane*8
@@ -281,8 +294,8 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
     if (slab_major) { const int slab = kt / 3, tap = kt - 3 * slab; return tap * slabs + slab; }
     return kt;
   };
-  f32x4 araw_[NST][ACH][2];
-  auto load_a = [&](int kt_, f32x4 (&araw)[ACH][2]) __attribute__((always_inline)) {
+  a_raw araw_[NST][ACH][2];
+  auto load_a = [&](int kt_, a_raw (&araw)[ACH][2]) __attribute__((always_inline)) {
     const int k0 = phys_kt(kt_) * SBK;
     int64_t shift = k0;
     unsigned bit = 1u;
@@ -291,21 +304,21 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
       bit = tap == 0 ? 2u : (tap == 1 ? 1u : 4u);
       shift = (int64_t)(tap - 1) * p.lda + (k0 - tap * p.cin);
     }
-    if constexpr (AMODE == A_CHANMAJOR) shift = (int64_t)k0 * p.lda;
+    if constexpr (CM) shift = (int64_t)k0 * p.lda;
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
-      f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = {0.f, 0.f, 0.f, 0.f};
+      a_raw v0 = {0, 0, 0, 0}, v1 = {0, 0, 0, 0};
       if (a_flag[i] & bit) {
-        v0 = *reinterpret_cast<const f32x4*>(a_ptr[i] + shift);
-        if constexpr (AMODE == A_CHANMAJOR) v1 = *reinterpret_cast<const f32x4*>(a_ptr[i] + shift + p.lda);   // k + 1
-        else v1 = *reinterpret_cast<const f32x4*>(a_ptr[i] + shift + 4);
+        v0 = *reinterpret_cast<const a_raw*>(a_ptr[i] + shift);
+        if constexpr (CM) v1 = *reinterpret_cast<const a_raw*>(a_ptr[i] + shift + p.lda);   // k + 1
+        else v1 = *reinterpret_cast<const a_raw*>(a_ptr[i] + shift + 4);
       }
       araw[i][0] = v0;
       araw[i][1] = v1;
     }
   };
-  auto store_a = [&](const f32x4 (&araw_in)[ACH][2], int kt_) __attribute__((always_inline)) {
-    f32x4 araw[ACH][2];
+  auto store_a = [&](const a_raw (&araw_in)[ACH][2], int kt_) __attribute__((always_inline)) {
+    a_raw araw[ACH][2];
 #pragma unroll
     for (int i = 0; i < ACH; ++i) { araw[i][0] = araw_in[i][0]; araw[i][1] = araw_in[i][1]; }
     if constexpr (ALN) {
@@ -341,7 +354,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
         const int kk = phys_kt(kt_) * SBK + 2 * (tid & 15);            // pk = id & 15 = tid & 15 (NT is a multiple of 16)
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
-          const f32x4 x0 = araw[i][0], x1 = araw[i][1];                // rows m .. m + 3 at k and k + 1 (zeros beyond M)
+          const f32x4 x0 = raw_f32(araw[i][0]), x1 = raw_f32(araw[i][1]);   // rows m .. m + 3 at k and k + 1 (zeros beyond M)
 #pragma unroll
           for (int e = 0; e < 4; ++e) sc_ss[i][e] = __builtin_fmaf(x1[e], x1[e], __builtin_fmaf(x0[e], x0[e], sc_ss[i][e]));
 #pragma unroll
@@ -358,14 +371,24 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
       const int id = i * NT + tid;
-      if constexpr (AMODE == A_CHANMAJOR) {
+      if constexpr (HALF && NTERMS == T_F16) {
+        // the half values times the power-of-two scale are the hi plane (a_scale = 1: the loaded bits; an exact product unless it
+        // overflows, where the fp32 mode's convert gives the same inf); there is no second plane
+        const int pk = id & 15, m4 = id >> 4;
+        const f16x2 s2 = {(_Float16)sa, (_Float16)sa};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const f16x2 hv = f16x2{araw[i][0][e], araw[i][1][e]} * s2;
+          *reinterpret_cast<unsigned*>(As + (m4 * 4 + e) * ROWB + pk * 4) = __builtin_bit_cast(unsigned, hv);
+        }
+      } else if constexpr (CM) {
         // araw[i][0] = rows m..m+3 at k = 2 pk, araw[i][1] the same rows at k + 1: one packed bf16 pair per row and
         // plane.  Lanes run over pk first: the 32 lanes of a ds_write_b32 group hit 32 distinct banks.
         const int pk = id & 15, m4 = id >> 4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           unsigned hi, mid, lo;
-          split_a<NTERMS>(araw[i][0][e], araw[i][1][e], sa, hi, mid, lo);
+          split_a<NTERMS>((float)araw[i][0][e], (float)araw[i][1][e], sa, hi, mid, lo);
           const int row = m4 * 4 + e;
           *reinterpret_cast<unsigned*>(As + (0 * BM + row) * ROWB + pk * 4) = hi;
           *reinterpret_cast<unsigned*>(As + (1 * BM + row) * ROWB + pk * 4) = mid;
@@ -419,11 +442,11 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
     load_b(kn, bfr_[SN]);
 #pragma unroll
     for (int c = 0; c < SBK / 16; ++c) {
-      bf16x8 a[TM][NPL];
+      bf16x8 a[TM][APL];
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int pl = 0; pl < NPL; ++pl)
+        for (int pl = 0; pl < APL; ++pl)
           a[i][pl] = *reinterpret_cast<const bf16x8*>(As + (pl * BM + (wm * TM + i) * 32 + r) * ROWB + c * 32 + h * 16);
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
@@ -436,7 +459,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((TM * TN >= 5 || TM >= 4 || (NST > 2
             acc[i][j] = mma<NTERMS>(a[i][2], bfr_[S][c][j][0], acc[i][j]);
           }
           acc[i][j] = mma<NTERMS>(a[i][0], bfr_[S][c][j][1], acc[i][j]);
-          acc[i][j] = mma<NTERMS>(a[i][1], bfr_[S][c][j][0], acc[i][j]);
+          if constexpr (APL > 1) acc[i][j] = mma<NTERMS>(a[i][1], bfr_[S][c][j][0], acc[i][j]);
           acc[i][j] = mma<NTERMS>(a[i][0], bfr_[S][c][j][0], acc[i][j]);
         }
       }
@@ -679,12 +702,13 @@ static int launch_cfg_s(const GemmBatch& b, int count, GemmAMode mode, int nterm
   char name[96];
   static const bool shapes = getenv("DCF_PROF_SHAPES") != nullptr;   // per-shape labels for tools/ (not used by bench.py)
   const char* fam = nterms == 6 ? "gemm_bf16x6" : "gemm_f16x3";
-  if (shapes) snprintf(name, sizeof(name), "%s<%dx%d,%s>[%dx%dx%dx%d]", fam, BM, BN, mode == A_ROWS ? "rows" : mode == A_ROWS_TAP3 ? "tap3" : "chanmajor", count, p.M, p.N, p.K);
-  else snprintf(name, sizeof(name), "%s<%dx%d,%s>", fam, BM, BN, mode == A_ROWS ? "rows" : mode == A_ROWS_TAP3 ? "tap3" : "chanmajor");
+  const char* mname = mode == A_ROWS ? "rows" : mode == A_ROWS_TAP3 ? "tap3" : mode == A_CHANMAJOR_H ? "chanmajor_h" : "chanmajor";
+  if (shapes) snprintf(name, sizeof(name), "%s<%dx%d,%s>[%dx%dx%dx%d]", fam, BM, BN, mname, count, p.M, p.N, p.K);
+  else snprintf(name, sizeof(name), "%s<%dx%d,%s>", fam, BM, BN, mname);
   const double mnk = work_fraction * (double)count * p.M * (double)p.N * p.K;     // (work_fraction: the share of the row tiles a gated launch runs at least)
   ProfScope prof(name, stream, 2.0 * mnk,
-                 4.0 * count * ((double)p.M * p.K / (mode == A_ROWS_TAP3 ? 3 : 1) + 1.5 * (double)p.N * p.K + (double)p.M * p.N * ((p.flags & G_RES) ? 2 : 1)));
-  const int npl = nterms == 6 ? 3 : 2;
+                 4.0 * count * ((double)p.M * p.K / (mode == A_ROWS_TAP3 ? 3 : mode == A_CHANMAJOR_H ? 2 : 1) + 1.5 * (double)p.N * p.K + (double)p.M * p.N * ((p.flags & G_RES) ? 2 : 1)));
+  const int npl = (mode == A_CHANMAJOR_H && nterms == T_F16) ? 1 : nterms == 6 ? 3 : 2;     // planes of the A tile (the kernel's APL)
   size_t lds = (size_t)npl * BM * ROWB;
   {   // epilogue: a transpose tile per wave; behind both that and the A tile, the row-statistics block of the workgroup
     const size_t epi = (size_t)WM * WN * EPI_WAVE_FLOATS * sizeof(float);
@@ -757,7 +781,7 @@ static int launch_cfg_s(const GemmBatch& b, int count, GemmAMode mode, int nterm
   } else
   if (p.ln_w) {
     if constexpr (WM == 1 && TM == 2 && TN >= 2) {
-      DCF_CHECK(mode != A_CHANMAJOR && count == 1, "launch_gemm_split: fused LayerNorm: unsupported mode");
+      DCF_CHECK(mode != A_CHANMAJOR && mode != A_CHANMAJOR_H && count == 1, "launch_gemm_split: fused LayerNorm: unsupported mode");
       if (mode == A_ROWS) { if (nterms == 6) LSN(A_ROWS, 6); else LSN(A_ROWS, T_F16); }
       else { if (nterms == 6) LSN(A_ROWS_TAP3, 6); else LSN(A_ROWS_TAP3, T_F16); }
     } else {
@@ -784,8 +808,14 @@ static int launch_cfg_s(const GemmBatch& b, int count, GemmAMode mode, int nterm
         // default 64 KiB -- engine.hip scores_on_gemm -- and sends wider features through k_sidekick_*)
         DCF_CHECK(lds_sc <= 65536, "launch_gemm_split: %d text vectors of %d channels beside the tile need %zu bytes of LDS (> 64 KiB)", score_q, p.K, lds_sc);
         constexpr int NST_ = DEEP ? 3 : 2;
+        if (mode == A_CHANMAJOR_H) {
+          if (nterms == 6) hipLaunchKernelGGL((gemm_bf16s_kernel<WM, WN, TM, TN, A_CHANMAJOR_H, 6, false, 2, false, false, true>), grid, dim3(WM * WN * 64), lds_sc, stream, b);
+          else hipLaunchKernelGGL((gemm_bf16s_kernel<WM, WN, TM, TN, A_CHANMAJOR_H, T_F16, false, NST_, false, false, true>), grid, dim3(WM * WN * 64), lds_sc, stream, b);
+        } else
         if (nterms == 6) hipLaunchKernelGGL((gemm_bf16s_kernel<WM, WN, TM, TN, A_CHANMAJOR, 6, false, 2, false, false, true>), grid, dim3(WM * WN * 64), lds_sc, stream, b);
         else hipLaunchKernelGGL((gemm_bf16s_kernel<WM, WN, TM, TN, A_CHANMAJOR, T_F16, false, NST_, false, false, true>), grid, dim3(WM * WN * 64), lds_sc, stream, b);
+      } else if (mode == A_CHANMAJOR_H) {
+        if (nterms == 6) LS(A_CHANMAJOR_H, 6); else LS(A_CHANMAJOR_H, T_F16);
       } else {
         if (nterms == 6) LS(A_CHANMAJOR, 6); else LS(A_CHANMAJOR, T_F16);
       }
@@ -859,7 +889,7 @@ bool gemm_can_fuse_ln(int M, int N, int K, GemmAMode mode) {
   // workgroups (M = 16384, one per CU) conv + LN fused 64 us vs 40 + 8 us as two kernels on 64x128 tiles; with 510
   // (M = 32640, the heads) 79 vs 74 + 12.5 us.  So: only where the grid still gives two workgroups per CU.
   constexpr long min_tiles = 448;            // (re-swept in f16x3 mode: 448 / 256 / 128 -> 1.892 / 1.973 / 1.988 ms per one-video step)
-  return mode != A_CHANMAJOR && N == 256 && K % SBK == 0 && (M + 63) / 64 >= min_tiles;
+  return mode != A_CHANMAJOR && mode != A_CHANMAJOR_H && N == 256 && K % SBK == 0 && (M + 63) / 64 >= min_tiles;
 }
 
 // same contract as launch_gemm; every g[i].Ws must hold the pre-tiled bf16 planes of g[i].W (launch_split_planes)
@@ -875,7 +905,11 @@ int launch_gemm_split(const GemmArgs* g, int count, GemmAMode mode, int nterms, 
     DCF_CHECK(g[i].M == p.M && g[i].N == p.N && g[i].K == p.K, "launch_gemm_split: grouped shapes differ");
     DCF_CHECK(g[i].A && g[i].Ws && (g[i].C || (g[i].ln_w && g[i].Y)), "launch_gemm_split: null operand");
     DCF_CHECK(g[i].lda % 4 == 0, "launch_gemm_split: lda %% 4 != 0");
-    if (mode == A_CHANMAJOR) DCF_CHECK(g[i].M % 4 == 0 && !(g[i].flags & G_AMASK), "launch_gemm_split: channel-major A needs M %% 4 == 0, no row mask");
+    if (mode == A_CHANMAJOR || mode == A_CHANMAJOR_H) DCF_CHECK(g[i].M % 4 == 0 && !(g[i].flags & G_AMASK), "launch_gemm_split: channel-major A needs M %% 4 == 0, no row mask");
+    if (mode == A_CHANMAJOR_H) {
+      DCF_CHECK((reinterpret_cast<uintptr_t>(g[i].A) & 7) == 0, "launch_gemm_split: half channel-major A needs an 8-byte aligned base (and lda %% 4 == 0, M %% 4 == 0)");
+      DCF_CHECK(!g[i].ln_w && !g[i].stats_out && !g[i].stats_in, "launch_gemm_split: half channel-major A carries neither a fused LayerNorm nor row statistics");
+    }
     if (mode == A_ROWS_TAP3) DCF_CHECK(g[i].nbr && g[i].cin % 32 == 0 && g[i].K == 3 * g[i].cin, "launch_gemm_split: bad tap3 args");
     if (g[i].flags & (G_AMASK | G_RES_MASK | G_OUT_MASK)) DCF_CHECK(g[i].rowmask, "launch_gemm_split: rowmask missing");
     if (g[i].flags & G_RES) DCF_CHECK(g[i].R, "launch_gemm_split: residual missing");
@@ -925,14 +959,14 @@ int launch_gemm_split(const GemmArgs* g, int count, GemmAMode mode, int nterms, 
   // (f16x3: 8192x256x1024, 512 tiles: tile kernel 22.7 us vs 30.4 k-sliced -> 256 tiles for every K)
   if (mode == A_ROWS && N % 64 == 0 && p.K >= 4 * SBK && wgs(64, 64) <= ((p.K >= 16 * SBK && nterms != T_F16) ? kslice_max : kslice_max / 2))
     return launch_kslice(b, count, nterms, stream);
-  if (mode == A_CHANMAJOR) {
+  if (mode == A_CHANMAJOR || mode == A_CHANMAJOR_H) {
     DCF_CHECK(N % 128 == 0, "launch_gemm_split: channel-major A needs N %% 128 == 0");
     if (N % 256 == 0 && wgs(64, 256) >= WANT) return launch_cfg_s<1, 4, 2, 2>(b, count, mode, nterms, stream);
     return launch_cfg_s<1, 4, 2, 1>(b, count, mode, nterms, stream);
   }
   // batched queries (M >= 64 K rows): 128x256 tiles, 128x64 per wave = half the weight fetches per MFMA at 2 waves/SIMD
   // (131072x256x1024: 189 vs 180 TFLOP/s; at M = 16384 the same tile is 30 % slower)
-  if (N % 256 == 0 && p.M >= 65536 && mode != A_CHANMAJOR) return launch_cfg_s<1, 4, 4, 2>(b, count, mode, nterms, stream);
+  if (N % 256 == 0 && p.M >= 65536 && mode != A_CHANMAJOR && mode != A_CHANMAJOR_H) return launch_cfg_s<1, 4, 4, 2>(b, count, mode, nterms, stream);
   if (N % 256 == 0 && wgs(64, 256) >= WANT) return launch_cfg_s<1, 4, 2, 2>(b, count, mode, nterms, stream);   // 64x256, 64x64 per wave
   // N = 288 (heads on E + 32 channels).  Also measured for M = 32640, K = 864: 64x288 tiles of three 64x96 waves
   // with the LayerNorm fused (each weight fragment fetched once, but 252 registers = 2 waves/SIMD) 122 us, 64x96
@@ -955,7 +989,8 @@ int launch_gemm_split(const GemmArgs* g, int count, GemmAMode mode, int nterms, 
 // The same channel-major GEMM (f16x3 / bf16x6 operand split) over nz (A, C) pairs in ONE grid of 64 x 256 tiles, each pair with its own
 // row-tile selection (GemmArgs::tile_skip; skip[z] may be null): see GemmBatch::zcount.
 int launch_gemm_split_z(const GemmArgs& base, int nz, const float* const* A, float* const* C, const uint8_t* const* skip, const int* skip_nq,
-                        int nterms, hipStream_t stream, double work_fraction) {
+                        int nterms, hipStream_t stream, double work_fraction, GemmAMode mode) {
+  DCF_CHECK(mode == A_CHANMAJOR || mode == A_CHANMAJOR_H, "launch_gemm_split_z: a channel-major A mode only");
   DCF_CHECK(nz >= 1 && nz <= GEMM_ZMAX, "launch_gemm_split_z: %d operand sets (1 .. %d)", nz, GEMM_ZMAX);
   DCF_CHECK(nterms == T_F16 || nterms == 6, "launch_gemm_split_z: nterms must be 16 (f16x3) or 6 (bf16x6)");
   DCF_CHECK(base.Ws && base.M > 0 && base.M % 4 == 0 && base.N % 256 == 0 && base.K > 0 && base.K % SBK == 0 && base.lda % 4 == 0 && !base.flags &&
@@ -966,10 +1001,11 @@ int launch_gemm_split_z(const GemmArgs& base, int nz, const float* const* A, flo
   b.zcount = nz;
   for (int z = 0; z < nz; ++z) {
     DCF_CHECK(A[z] && C[z], "launch_gemm_split_z: null operand");
+    if (mode == A_CHANMAJOR_H) DCF_CHECK((reinterpret_cast<uintptr_t>(A[z]) & 7) == 0, "launch_gemm_split_z: half channel-major A needs an 8-byte aligned base");
     b.zA[z] = A[z]; b.zC[z] = C[z]; b.zskip[z] = skip ? skip[z] : nullptr; b.zskip_nq[z] = skip && skip[z] ? skip_nq[z] : 0;
   }
   b.g[0].A = A[0]; b.g[0].C = C[0];
-  return launch_cfg_s<1, 4, 2, 2>(b, nz, A_CHANMAJOR, nterms, stream, work_fraction);
+  return launch_cfg_s<1, 4, 2, 2>(b, nz, mode, nterms, stream, work_fraction);
 }
 
 }  // namespace dcf

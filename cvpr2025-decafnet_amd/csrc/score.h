@@ -23,7 +23,8 @@ struct ScoreArgs {
   float* correl;          // (NQ, T) out
   int D, T, NQ, norm;
 };
-int launch_sidekick(const ScoreArgs& a, hipStream_t st);
+// half: every shallow[v] is the address of IEEE binary16 values (2-byte aligned; 8-byte aligned bases with T % 4 == 0 take 8-byte loads)
+int launch_sidekick(const ScoreArgs& a, hipStream_t st, bool half = false);
 int launch_text_cls_norm(const ScoreArgs& a, hipStream_t st);     // tn only (the scores come out of the vid_map GEMMs)
 // one video
 inline ScoreArgs score_args(const float* shallow, const float* text_cls, float* tn, float* partial, float* correl, int D, int T,

@@ -100,6 +100,68 @@ __global__ __launch_bounds__(64) void k_sidekick_partial(ScoreArgs p) {
   }
 }
 
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+// k_sidekick_partial on a (D, T) matrix of IEEE binary16 values (ScoreArgs::shallow carries their address; a channel row is T halves
+// long): every value is upcast exactly as it is loaded and the sums are those of the fp32 kernel on the upcast matrix, term by term
+// in the same order.  8-byte loads of four clips where the base is 8-byte aligned and T % 4 == 0.  Its own kernel, a copy to be
+// kept in step with k_sidekick_partial by hand: a body shared through a template on the element type (tried by reference, by value and
+// with a bool parameter) made every fp32 instantiation compile to other instructions than before.
+template <int NQ>
+__global__ __launch_bounds__(64) void k_sidekick_partial_h(ScoreArgs p) {
+  const int lane = threadIdx.x;
+  const int t = (blockIdx.x * 64 + lane) * 4;
+  const int slice = blockIdx.y;
+  const int vid = blockIdx.z % p.nvid, q0 = (blockIdx.z / p.nvid) * SCORE_MAXQ;
+  const int nqv = pick(p.nq, vid) - q0;                 // queries of this video left for this chunk (may be <= 0 or > NQ)
+  if (nqv <= 0) return;
+  const int qrow = pick(p.qoff, vid) + q0;              // first of them in tn / correl
+  const _Float16* shallow = reinterpret_cast<const _Float16*>(pick(p.shallow, vid));
+  const float* tn = p.tn + (size_t)qrow * p.D;
+  const int cps = (p.D + SCORE_SLICES - 1) / SCORE_SLICES;
+  const int c0 = slice * cps, c1 = min(c0 + cps, p.D);
+  const bool vec = (p.T & 3) == 0 && (reinterpret_cast<uintptr_t>(shallow) & 7) == 0;
+  f32x4 ss = {0.f, 0.f, 0.f, 0.f};
+  f32x4 dot[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) dot[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (t < p.T) {
+    int c = c0;
+    if (vec) {
+      // eight channel rows requested before the first is used: a load per iteration left the loop waiting for one round trip
+      // per channel (35 us for 64 MiB)
+      for (; c + 8 <= c1; c += 8) {
+        f32x4 x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = __builtin_convertvector(*reinterpret_cast<const f16x4*>(shallow + (size_t)(c + u) * p.T + t), f32x4);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          ss += x[u] * x[u];
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) dot[q] += x[u] * tn[(size_t)(q < nqv ? q : 0) * p.D + c + u];
+        }
+      }
+    }
+    for (; c < c1; ++c) {
+      const _Float16* src = shallow + (size_t)c * p.T + t;
+      f32x4 x = {0.f, 0.f, 0.f, 0.f};
+      if (vec) x = __builtin_convertvector(*reinterpret_cast<const f16x4*>(src), f32x4);
+      else { x.x = (float)src[0]; if (t + 1 < p.T) x.y = (float)src[1]; if (t + 2 < p.T) x.z = (float)src[2]; if (t + 3 < p.T) x.w = (float)src[3]; }
+      ss += x * x;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) dot[q] += x * tn[(size_t)(q < nqv ? q : 0) * p.D + c];   // wave-uniform scalar load
+    }
+    float* dst = p.partial + ((size_t)slice * (p.NQ + p.nvid) + qrow + vid) * p.T + t;      // the video's ss row
+    const int n = min(4, p.T - t);
+    for (int i = 0; i < n; ++i) {
+      if (q0 == 0) dst[i] = ss[i];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+        if (q < nqv) dst[(size_t)(1 + q) * p.T + i] = dot[q][i];
+    }
+  }
+}
+
 // grid = (ceil(T/256), nvid)
 __global__ __launch_bounds__(256) void k_sidekick_final(ScoreArgs p) {
   const int t = blockIdx.x * 256 + threadIdx.x;
@@ -126,15 +188,27 @@ int launch_text_cls_norm(const ScoreArgs& a, hipStream_t st) {
   return 0;
 }
 
-int launch_sidekick(const ScoreArgs& a, hipStream_t st) {
+int launch_sidekick(const ScoreArgs& a, hipStream_t st, bool half) {
   if (a.NQ <= 0 || a.T <= 0 || a.nvid <= 0) return 0;
   DCF_CHECK(a.nvid <= SCORE_MAXVID, "sidekick: %d videos per launch > %d", a.nvid, SCORE_MAXVID);
   int maxq = 0;
   for (int v = 0; v < a.nvid; ++v) maxq = a.nq[v] > maxq ? a.nq[v] : maxq;
   const int chunks = (maxq + SCORE_MAXQ - 1) / SCORE_MAXQ;
-  ProfScope prof("sidekick_score", st, 2.0 * (a.NQ + a.nvid) * a.D * a.T, 4.0 * (double)a.D * a.T * a.nvid * chunks);
+  ProfScope prof(half ? "sidekick_score_h" : "sidekick_score", st, 2.0 * (a.NQ + a.nvid) * a.D * a.T, (half ? 2.0 : 4.0) * (double)a.D * a.T * a.nvid * chunks);
   hipLaunchKernelGGL(k_text_cls_norm, dim3(a.NQ), dim3(256), 0, st, a);
   dim3 grid((a.T + 255) / 256, SCORE_SLICES, a.nvid * chunks);
+  if (half) {
+    switch (maxq < SCORE_MAXQ ? maxq : SCORE_MAXQ) {
+      case 1: hipLaunchKernelGGL(k_sidekick_partial_h<1>, grid, dim3(64), 0, st, a); break;
+      case 2: hipLaunchKernelGGL(k_sidekick_partial_h<2>, grid, dim3(64), 0, st, a); break;
+      case 3: hipLaunchKernelGGL(k_sidekick_partial_h<3>, grid, dim3(64), 0, st, a); break;
+      case 4: hipLaunchKernelGGL(k_sidekick_partial_h<4>, grid, dim3(64), 0, st, a); break;
+      case 5: hipLaunchKernelGGL(k_sidekick_partial_h<5>, grid, dim3(64), 0, st, a); break;
+      case 6: hipLaunchKernelGGL(k_sidekick_partial_h<6>, grid, dim3(64), 0, st, a); break;
+      case 7: hipLaunchKernelGGL(k_sidekick_partial_h<7>, grid, dim3(64), 0, st, a); break;
+      default: hipLaunchKernelGGL(k_sidekick_partial_h<8>, grid, dim3(64), 0, st, a); break;
+    }
+  } else
   switch (maxq < SCORE_MAXQ ? maxq : SCORE_MAXQ) {
     case 1: hipLaunchKernelGGL(k_sidekick_partial<1>, grid, dim3(64), 0, st, a); break;
     case 2: hipLaunchKernelGGL(k_sidekick_partial<2>, grid, dim3(64), 0, st, a); break;

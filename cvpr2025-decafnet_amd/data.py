@@ -29,25 +29,50 @@ import torch.nn.functional as F
 FEATURE_FORMATS = ('npy', 'pt', 'pk0', 'pk1', 'pk_avg')
 
 
-def load_clip_features(path_without_ext: str, fmt: str = 'npy') -> np.ndarray:
-    """One feature source of one video as stored on disk: (T, C)."""
+def feature_dtype(dtype):
+    """The ``dtype`` argument of the feature loaders as one of np.float32, np.float16 or 'stored'; anything else is refused."""
+    if isinstance(dtype, str) and dtype == 'stored':
+        return 'stored'
+    for want, names in ((np.float32, (np.float32, 'float32', torch.float32)), (np.float16, (np.float16, 'float16', 'half', torch.float16))):
+        if any(dtype is n or (isinstance(dtype, str) and dtype == n) for n in names) or (isinstance(dtype, np.dtype) and dtype == want):
+            return want
+    raise ValueError(f"feature dtype {dtype!r}: np.float32 (default), np.float16 or 'stored'")
+
+
+def _cast_features(a, dtype, always_f32):
+    """np.float32: float16 arrays -- and, with ``always_f32`` (the npy format), every array -- become float32, others stay as stored;
+    'stored': float16 arrays stay float16, the rest as under np.float32; np.float16: a cast of everything."""
+    a = np.asarray(a)
+    if dtype is np.float16:
+        return a.astype(np.float16)
+    if a.dtype == np.float16:
+        return a if dtype == 'stored' else a.astype(np.float32)
+    return a.astype(np.float32) if always_f32 else a
+
+
+def load_clip_features(path_without_ext: str, fmt: str = 'npy', dtype=np.float32) -> np.ndarray:
+    """One feature source of one video as stored on disk: (T, C).  ``dtype``: np.float32 (default) hands float16 files on as
+    float32; 'stored' keeps them float16 -- half the bytes from here to the GPU, ``forward(..., eval=True)`` reads them as they
+    are --; np.float16 casts whatever is stored."""
+    dtype = feature_dtype(dtype)
     if fmt == 'npy':
-        return np.load(path_without_ext + '.npy').astype(np.float32)
+        return _cast_features(np.load(path_without_ext + '.npy'), dtype, True)
     if fmt == 'pt':
-        return torch.load(path_without_ext + '.pt').numpy()
+        return _cast_features(torch.load(path_without_ext + '.pt').numpy(), dtype, False)
     if fmt in ('pk0', 'pk1', 'pk_avg'):
         with open(path_without_ext + '.pk', 'rb') as fh:
             entries = pickle.load(fh)
         if fmt == 'pk_avg':
-            return (entries[0] + entries[1]) / 2
-        return entries[int(fmt[2])]
+            return _cast_features((entries[0] + entries[1]) / 2, dtype, False)
+        return _cast_features(entries[int(fmt[2])], dtype, False)
     raise NotImplementedError(f'feature format {fmt!r}: one of {FEATURE_FORMATS}')
 
 
 def load_video_features(feat_dirs: Sequence[str], vid_id: str, fmt: str = 'npy', downsample_rate: int = 1,
-                        normalize: bool = False) -> torch.Tensor:
-    """All feature sources of a video -> (C_total, T) float tensor, the reference's in-memory layout."""
-    srcs = [load_clip_features(os.path.join(d, vid_id), fmt) for d in feat_dirs]
+                        normalize: bool = False, dtype=np.float32) -> torch.Tensor:
+    """All feature sources of a video -> (C_total, T) float tensor, the reference's in-memory layout.  ``dtype`` as in
+    ``load_clip_features``; float16 features are normalised in fp32 and rounded once."""
+    srcs = [load_clip_features(os.path.join(d, vid_id), fmt, dtype) for d in feat_dirs]
     if len(srcs) > 1:
         longest = max(len(a) for a in srcs)
         if longest - min(len(a) for a in srcs) > 10:
@@ -59,6 +84,8 @@ def load_video_features(feat_dirs: Sequence[str], vid_id: str, fmt: str = 'npy',
     if downsample_rate > 1:
         feats = feats[::downsample_rate]
     out = torch.from_numpy(np.ascontiguousarray(feats.transpose()))
+    if normalize and out.dtype == torch.float16:
+        return F.normalize(out.float(), dim=0).half()
     return F.normalize(out, dim=0) if normalize else out
 
 
@@ -118,7 +145,8 @@ class VideoCentricEvalData:
 
     ``cfg`` carries the ``opt.data`` keys the reference reads: anno_file, eval_split (or split), vid_feat_dir,
     shallow_vid_feat_dir, text_feat_dir, text_cls_fname (with ``{split}``), vid_load, shallow_vid_load, downsample_rate,
-    clip_size, clip_stride, normalize_vid, normalize_text, ext_score_dir / normalize_scores / temperature (optional)."""
+    clip_size, clip_stride, normalize_vid, normalize_text, ext_score_dir / normalize_scores / temperature (optional).  Extension key
+    ``feature_dtype`` (np.float32, np.float16 or 'stored', see ``load_clip_features``): the dtype ``vid`` / ``shallow_vid`` come in."""
 
     def __init__(self, cfg):
         g = cfg.get
@@ -132,6 +160,7 @@ class VideoCentricEvalData:
         self.clip_size = g('clip_size', 16)
         self.clip_stride = g('clip_stride', 16) * self.ds                     # dataset.py:240
         self.normalize_vid, self.normalize_text = bool(g('normalize_vid', False)), bool(g('normalize_text', False))
+        self.feature_dtype = feature_dtype(g('feature_dtype', np.float32))
         self.ext_score_dir = g('ext_score_dir')
         self.normalize_scores, self.temperature = bool(g('normalize_scores', False)), float(g('temperature', 1.0))
         self.cls = TextClsTable([cfg['text_cls_fname'].format(split=s) for s in self.splits])
@@ -142,9 +171,9 @@ class VideoCentricEvalData:
     def sample(self, vid_id: str):
         v = self.videos[vid_id]
         n = len(v['segments'])
-        vid = load_video_features(self.vid_dirs, vid_id, self.vid_fmt, self.ds, self.normalize_vid)
+        vid = load_video_features(self.vid_dirs, vid_id, self.vid_fmt, self.ds, self.normalize_vid, self.feature_dtype)
         # the sidekick features are stored at the down-sampled rate already (dataset.py:1033,1066-1068)
-        shallow = load_video_features(self.shallow_dirs, vid_id, self.shallow_fmt, 1, self.normalize_vid)
+        shallow = load_video_features(self.shallow_dirs, vid_id, self.shallow_fmt, 1, self.normalize_vid, self.feature_dtype)
         text = tuple(load_text_features(self.text_dir, t, self.normalize_text) for t in v['text_ids'])
         # the reference indexes the raw annotation list with the index of the kept segment (dataset.py:672-674)
         text_cls = self.cls.lookup([v['annotations'][i]['sentence'] for i in range(n)])

@@ -78,11 +78,14 @@ class RecallCounter:
         return '\n'.join(lines + ['-----', ''])
 
 
-def load_features(path_without_ext: str, fmt: str = 'npy'):
+def load_features(path_without_ext: str, fmt: str = 'npy', dtype=np.float32):
     """One feature file as the reference stores it ((T, C) on disk: npy / pt / pk0 / pk1 / pk_avg, libs/data/dataset.py:107-135)
-    returned channel-major (C, T) like ``_load_vid_feats`` (:398-399).  Multi-source videos: ``data.load_video_features``."""
+    returned channel-major (C, T) like ``_load_vid_feats`` (:398-399).  Multi-source videos: ``data.load_video_features``.
+    ``dtype``: np.float32 (default), 'stored' (a float16 file stays float16) or np.float16 (a cast), as in ``data.load_clip_features``."""
     from . import data as _data
-    a = np.asarray(_data.load_clip_features(path_without_ext, fmt), dtype=np.float32)
+    a = np.asarray(_data.load_clip_features(path_without_ext, fmt, dtype))
+    if a.dtype != np.float16:
+        a = np.asarray(a, dtype=np.float32)
     return torch.from_numpy(np.ascontiguousarray(a.transpose()))
 
 
@@ -135,8 +138,15 @@ class GroundingEvaluator:
     """``opt`` needs ``opt.model.{max_vid_len, num_fpn_levels, mha_win_size, vid_stride}``, ``opt.eval.{pre_nms_topk,
     pre_nms_thresh, seg_len_thresh}`` and ``opt.nms`` (libs/core/opt.py:174-194)."""
 
-    def __init__(self, opt, model):
+    def __init__(self, opt, model, feature_dtype=None):
+        """``feature_dtype``: None -- ``vid`` / ``shallow_vid`` go to the GPU in the dtype they come in --, or 'float16': ``prepare``
+        rounds them to float16 on the host, before padding, and uploads half the bytes; the forward reads them as they are
+        (``model.half_features``).  The proposals then are those of features rounded to float16."""
         self.opt, self.model = opt, model
+        if feature_dtype is not None and not any(feature_dtype is x or (isinstance(feature_dtype, str) and feature_dtype == x)
+                                                 for x in ('float16', 'half', torch.float16, np.float16)):
+            raise ValueError(f"feature_dtype {feature_dtype!r}: None (as the features come) or 'float16'")
+        self.feature_dtype = None if feature_dtype is None else torch.float16
         mo = opt['model']
         self.max_vid_len = mo['max_vid_len']
         self.vid_stride = mo.get('vid_stride', 1)
@@ -151,7 +161,7 @@ class GroundingEvaluator:
         self._pinned = {}                              # free pinned host buffers of launch_proposals, by packed shape
 
     @classmethod
-    def from_checkpoint(cls, opt, root=None, ckpt=None, device='cuda'):
+    def from_checkpoint(cls, opt, root=None, ckpt=None, device='cuda', feature_dtype=None):
         """What ``Evaluator.__init__`` + ``load_model`` do for the model (libs/worker_v2.py:747-749, 806-812): build it with
         ``create_model(opt)``, load ``<root>/models/<ckpt>.pth``['model_ema'] (a checkpoint written by the reference's
         ``Trainer``: the state_dict names are the parameter ABI), move it to the GPU, eval mode, no gradients.
@@ -166,7 +176,19 @@ class GroundingEvaluator:
         model = modeling.create_model(opt)
         model.load_state_dict(state['model_ema'])
         model = model.to(device).eval().requires_grad_(False)
-        return cls(opt, model)
+        return cls(opt, model, feature_dtype=feature_dtype)
+
+    @staticmethod
+    def _to_half(x, what, name):
+        """x rounded to float16 on the host; a finite value that leaves the float16 range (|x| > 65504) is an error, not an inf"""
+        if x.dtype == torch.float16:
+            return x
+        h = x.to(torch.float16)
+        bad = ~torch.isfinite(h) & torch.isfinite(x)
+        if bool(bad.any()):
+            raise ValueError(f'video {name}: {int(bad.sum())} finite values of {what} (max |x| = {float(x[bad].abs().max()):.6g}) leave the float16 '
+                             f'range (65504): these features cannot be evaluated with feature_dtype=\'float16\'')
+        return h
 
     @torch.no_grad()
     def prepare(self, data, model=None):
@@ -184,6 +206,9 @@ class GroundingEvaluator:
             texts.append(t)
             tmasks.append(m)
         vid, shallow = data['vid'], data['shallow_vid']
+        if self.feature_dtype is not None:
+            name = data.get('clip_id', '?') if isinstance(data, dict) else '?'
+            vid, shallow = self._to_half(vid, 'vid', name), self._to_half(shallow, 'shallow_vid', name)
         vid_len = vid.size(-1)
         T = padded_length(vid_len, self.max_vid_len, self.num_fpn_levels, self.mha_win_size, self.vid_stride)
         window = F.pad(vid, (0, T - vid_len))[None].to(dev, non_blocking=True)

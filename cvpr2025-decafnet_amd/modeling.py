@@ -445,6 +445,12 @@ GEMM_MODES = {'f16x3': 16, 'bf16x6': 6, 'fp32': 1}
 ATTN_MODES = {'f16x3': 0, 'f16': 1}
 
 
+def _check_feature_dtypes(vid, shallow):
+    if (vid.dtype == torch.float16) != (shallow.dtype == torch.float16):
+        raise ValueError(f'vid is {vid.dtype} and shallow_vid is {shallow.dtype}: float16 clip features come as a pair '
+                         f'(cast one of them, or set model.half_features = False and pass both as fp32)')
+
+
 class PtTransformerEarlyFusionIterative(nn.Module):
     """Drop-in for libs/modeling/model.py:397-565 (created by libs/worker_v2.py:182-211).
 
@@ -454,6 +460,10 @@ class PtTransformerEarlyFusionIterative(nn.Module):
 
     MODEL_KIND = 0
     _dropout = None                                 # enable_dropout: (refine_pdrop, private generator or None)
+    # float16 clip features (vid and shallow_vid both torch.float16) go to the engine as they are stored in ``forward(..., eval=True)``
+    # and ``forward_videos`` (include/decafnet_hip_half.h); False: they are upcast to fp32 first, as every other dtype is
+    half_features = True
+    last_feature_dtype = None                       # what the engine read vid / shallow_vid as in the last eval forward
     last_dropout_seed = None                        # the 64-bit key of the last training forward with dropout
 
     def __init__(self, opt, second_fusion=True):
@@ -566,6 +576,14 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         """model.py:434-436: tokens (bs, C_t, Lq) f32, token_masks (bs, 1, Lq) bool -> ((bs, TE, Lk), (bs, 1, Lk)),
         Lk = Lq + use_bkgd_token.  Runs TextTransformer.forward (text_net.py:158-188) on the GPU (dcf_text_encode)."""
         return _encode_text(self, tokens, token_masks)
+
+    def _feature_pair(self, vid, shallow, half_ok=True):
+        """(vid, shallow, half) contiguous for the engine: float16 tensors themselves (no copy of a contiguous tensor) where the pair is
+        float16 and ``half_features`` is on, fp32 otherwise.  One of the two in float16 and the other not is refused."""
+        _check_feature_dtypes(vid, shallow)
+        if half_ok and self.half_features and vid.dtype == torch.float16:
+            return vid.contiguous(), shallow.contiguous(), True
+        return vid.contiguous().float(), shallow.contiguous().float(), False
 
     def forward(self, vid, shallow_vid, vid_masks, text, text_cls, text_masks, text_size=None, mv_data=None, eval=False):
         if not eval:
@@ -878,6 +896,10 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         ``(vid (1,D,T), shallow_vid (1,D,T), vid_masks (1,T), text: tuple, text_cls (NQ,D), text_masks: tuple)`` --
         the arguments of ``forward`` per video.  Returns a list with, per video, what ``forward(..., eval=True)`` returns."""
         assert len(videos) >= 1
+        for video in videos:
+            _check_feature_dtypes(video[0], video[1])
+        if len({video[0].dtype == torch.float16 for video in videos}) != 1:
+            raise ValueError('forward_videos: the videos of one call are all float16 or none of them is')
         if not videos[0][0].is_cuda:
             raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
         dev = videos[0][0].device
@@ -895,7 +917,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         flat_text, flat_masks = [], []
         for v, (vid, shallow, vmask, text, text_cls, tmasks) in enumerate(videos):
             assert vid.size(0) == 1 and vid.size(-1) == T, 'videos of one call share the padded length'
-            vc, sc = vid[0].contiguous().float(), shallow[0].contiguous().float()
+            vc, sc, half = self._feature_pair(vid[0], shallow[0])
             mc = vmask.reshape(-1).to(torch.bool).contiguous()
             if not isinstance(text, (tuple, list)):
                 text, tmasks = (text,), (tmasks,)
@@ -928,8 +950,10 @@ class PtTransformerEarlyFusionIterative(nn.Module):
             masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
             if self.reuse_output_buffers:
                 self._out_cache = {okey: (logits, offsets, masks)}
-        _lib.check(lib.dcf_forward_eval_videos(eng.handle, nv, vptr, sptr, mptr_v, T, nqs, tptr, mptr, tlen, cptr, _lib.ptr(logits),
-                                               _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()), 'dcf_forward_eval_videos')
+        fn, what = (lib.dcf_forward_eval_videos_h, 'dcf_forward_eval_videos_h') if half else (lib.dcf_forward_eval_videos, 'dcf_forward_eval_videos')
+        _lib.check(fn(eng.handle, nv, vptr, sptr, mptr_v, T, nqs, tptr, mptr, tlen, cptr, _lib.ptr(logits),
+                      _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()), what)
+        self.last_feature_dtype = torch.float16 if half else torch.float32
         self._last_inputs = (keep, pe)
         self._last_flat = (logits, offsets, masks)
         self._probe_numerics()
@@ -948,6 +972,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
                            eval=False, gate=None, pe_tokens=None):
         assert mv_data is None and eval
         assert vid.size(0) == 1, vid.size()                                  # model.py:496
+        _check_feature_dtypes(vid, shallow_vid)
         if not vid.is_cuda:
             raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
         dev = vid.device
@@ -958,8 +983,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         eng.bind(self)
         lib = eng.lib
         T = vid.size(-1)
-        vid_c = vid[0].contiguous().float()
-        sh_c = shallow_vid[0].contiguous().float()
+        vid_c, sh_c, half = self._feature_pair(vid[0], shallow_vid[0], half_ok=gate is None)
         mask_c = vid_masks.reshape(-1).to(torch.bool).contiguous()
         assert mask_c.numel() == T and sh_c.shape == vid_c.shape == (self.D, T)
         if not isinstance(text, (tuple, list)):
@@ -998,10 +1022,11 @@ class PtTransformerEarlyFusionIterative(nn.Module):
             masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
             if self.reuse_output_buffers:
                 self._out_cache = {okey: (logits, offsets, masks)}
-        fn = lib.dcf_forward_eval if gate is None else lib.dcf_forward_eval_gated
+        fn = lib.dcf_forward_eval_h if half else lib.dcf_forward_eval if gate is None else lib.dcf_forward_eval_gated
         _lib.check(fn(eng.handle, _lib.ptr(vid_c), _lib.ptr(sh_c), _lib.ptr(mask_c), T, nq, tptr, mptr, tlen,
                       _lib.ptr(cls_c), _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()),
-                   'dcf_forward_eval')
+                   'dcf_forward_eval_h' if half else 'dcf_forward_eval')
+        self.last_feature_dtype = torch.float16 if half else torch.float32
         # keep the borrowed inputs alive until the stream has consumed them
         self._last_inputs = (vid_c, sh_c, mask_c, cls_c, keep, pe)
         self._last_flat = (logits, offsets, masks)
