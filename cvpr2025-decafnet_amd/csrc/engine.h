@@ -61,6 +61,7 @@ struct HeadW {
   const float* out_w;                        // packed [NO][3][Cin]
   const float* out_b;
   const unsigned short* chain[2] = {nullptr, nullptr};   // chain images of the two trunk convolutions (head_chain.hip) or nullptr
+  const unsigned short* out_chain = nullptr;             // ... and of the output convolution
 };
 
 // opt.model.vid_net.stride (video_net.py:39): the embedding convolutions divide the sequence by it; 0 (older callers) reads as 1

@@ -300,7 +300,7 @@ int run_encoder(dcf_model* m, const EncW& w, Buffers& b, const float* Xin, int64
 static bool can_chain_head(dcf_model* m, const HeadW& h, int rows, int Cin, int NO) {
   static const Setting min_rows(nullptr, "DCF_HEAD_CHAIN_MIN_ROWS", 30000);     // developer switch
   static const Setting off(nullptr, "DCF_NO_HEAD_CHAIN", 0, Setting::PRESENT);     // developer switch: GEMM + LayerNorm + output-convolution launches
-  if (off.get() || rows < min_rows.get() || m->gemm_terms != GEMM_F16X3 || !h.chain[0] || !h.chain[1]) return false;
+  if (off.get() || rows < min_rows.get() || m->gemm_terms != GEMM_F16X3 || !h.chain[0] || !h.chain[1] || !h.out_chain) return false;
   if (h.conv.size() != 2 || !head_chain_supports(Cin, NO)) return false;
   for (int i = 0; i < 2; ++i)
     if (!m->wsplit.count(h.conv[i]) || m->wsplit_terms[h.conv[i]] != GEMM_F16X3) return false;
@@ -310,7 +310,7 @@ static HeadChainArgs head_chain_args(dcf_model* m, const HeadW& h, Buffers& b, c
   HeadChainArgs a{};
   a.X = b.F; a.ldx = m->cfg.E + TCN_HID; a.nbr = b.nbr_all; a.W1c = h.chain[0]; a.W2c = h.chain[1];
   a.ln1_w = h.ln_w[0]; a.ln1_b = h.ln_b[0]; a.ln2_w = h.ln_w[1]; a.ln2_b = h.ln_b[1];
-  a.Wout = h.out_w; a.bout = h.out_b; a.lt = pl.d_lt; a.out = out; a.rows = pl.B * pl.lt.S; a.NO = NO; a.mode = mode;
+  a.Wout = h.out_w; a.Woc = h.out_chain; a.bout = h.out_b; a.lt = pl.d_lt; a.out = out; a.rows = pl.B * pl.lt.S; a.NO = NO; a.mode = mode;
   a.query_major = query_major; a.status = m->status;
   return a;
 }

@@ -362,7 +362,7 @@ static int resolve_head(dcf_model* m, const std::string& p, const std::string& o
   GET(p + "." + out_name + ".conv.weight", SH(NO, C, 3), t);
   if (pack3(m, t, NO, C, 3, 0, 2, 1, st, &h.out_w)) return -1;
   GET(p + "." + out_name + ".conv.bias", SH(NO), h.out_b);
-  h.chain[0] = h.chain[1] = nullptr;
+  h.chain[0] = h.chain[1] = h.out_chain = nullptr;
   if (m->gemm_terms == GEMM_F16X3 && layers == 2 && head_chain_supports(C, NO)) {      // the whole head as one kernel (head_chain.hip)
     for (int i = 0; i < 2; ++i) {
       unsigned short* img = nullptr;
@@ -371,6 +371,11 @@ static int resolve_head(dcf_model* m, const std::string& p, const std::string& o
       if (launch_split_chain3(h.conv[i], img, C, st, nullptr)) return -1;   // (range: the same weights passed split_weight above)
       h.chain[i] = img;
     }
+    unsigned short* img = nullptr;                       // the output convolution runs in f16x3 too: same weight range, same fallback
+    DCF_HIP(hipMalloc(&img, head_chain_out_image_halfs(C) * sizeof(unsigned short)));
+    m->owned.push_back(reinterpret_cast<float*>(img));
+    if (launch_split_chain_out(h.out_w, NO, img, C, st, m->status ? m->status + 1 : nullptr)) return -1;
+    h.out_chain = img;
   }
   return 0;
 }

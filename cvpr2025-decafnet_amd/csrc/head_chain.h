@@ -16,6 +16,7 @@ struct HeadChainArgs {
   const unsigned short* W2c;    // ... of trunk convolution 2
   const float* ln1_w; const float* ln1_b; const float* ln2_w; const float* ln2_b;   // [C]
   const float* Wout;            // [NO][3][C] output convolution
+  const unsigned short* Woc;    // ... as a chain image (launch_split_chain_out): what the kernel reads
   const float* bout;            // [NO]
   const LevelTable* lt;         // device copy: level starts, per-level scale, query-major offsets
   float* out;                   // query_major: out[(b * S + off_l + t) * NO + o], else out[row * NO + o]
@@ -34,5 +35,9 @@ size_t head_chain_image_halfs(int C);
 // Wp: the packed fp32 weight [C out][3 taps][C in] (engine_model.hip pack3) -> img: fp16 hi / lo fragments in the order the kernel
 // streams them; overflow (optional): bit 0 set if a weight leaves the scaled fp16 range
 int launch_split_chain3(const float* Wp, unsigned short* img, int C, hipStream_t stream, unsigned* overflow = nullptr);
+// the same for the output convolution, Wout: packed fp32 [NO][3][C] -> img: head_chain_out_image_halfs(C) halfs (one stage of the
+// kernel's weight stream, 3 NO of its 32 rows real)
+size_t head_chain_out_image_halfs(int C);
+int launch_split_chain_out(const float* Wout, int NO, unsigned short* img, int C, hipStream_t stream, unsigned* overflow = nullptr);
 
 }  // namespace dcf

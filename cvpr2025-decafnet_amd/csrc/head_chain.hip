@@ -17,6 +17,11 @@
 // neighbouring lanes, across a wave boundary the two products concerned (tap 0 of the last row, tap 2 of the first) go through
 // LDS and are added after the next barrier; the window's outer rows have nobody to ask, so of the 128 rows the inner 122 come out
 // valid after two trunk layers and the output convolution (windows of consecutive workgroups overlap by 6 rows).
+// The output convolution is the chain's last product: after the second LayerNorm + ReLU the activations are split into planes like
+// the first layer's, and Wo (3 NO real rows of a 32-row A operand, k_split_chain_out) meets them in C / 16 x 3 MFMAs on an image
+// that the last trunk stage requested into the free ring buffer; its three taps are put together like a trunk layer's.  f16x3 like
+// every other convolution of the model (it was fp32 FMAs on broadcast LDS reads: 216 ds_read_b128 and 864 FMAs per lane; that form
+// is still there under DCF_HC_VECTOR_OUT for A/B builds; profiles/head_planes.md).
 #include "head_chain.h"
 
 #include <type_traits>
@@ -121,7 +126,32 @@ __global__ void k_split_chain3(const float* __restrict__ Wp, unsigned short* __r
   *reinterpret_cast<unsigned*>(img + o + 64 * 8) = lo;
 }
 
-// NO = 2 is the compiled width of the output convolution; a head with one output leaves the second one's weights zero in LDS.
+// Wout [NO][3][C] fp32 -> the output convolution as one more A operand of the chain: a stage-sized image (the kernel requests it like
+// any stage; pieces from 2 KS on stay zero), piece (kk, plane), lane (h, r'), half j as above.  Of the 32 A rows 3 NO are real:
+// output e = 2 tap + o sits in row r' = 8 (e >> 2) + (e & 3), the row that the MFMA leaves in accumulator register e of the lanes
+// of half 0 (D row = 8 g + 4 h + i in register 4 g + i), so every row's six products end up in its own lane.  The rest is zero.
+template <int C>
+__global__ void k_split_chain_out(const float* __restrict__ Wout, int NO, unsigned short* __restrict__ img, unsigned* __restrict__ overflow) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;          // (e, k pair)
+  if (i >= 6 * (C / 2)) return;
+  const int e = i / (C / 2), k = (i - e * (C / 2)) * 2, tap = e >> 1, o = e & 1;
+  if (o >= NO) return;
+  const float w0 = Wout[((size_t)o * 3 + tap) * C + k], w1 = Wout[((size_t)o * 3 + tap) * C + k + 1];
+  unsigned hi, lo;
+  split2_f16(w0, w1, SW, hi, lo);
+  if (!(__builtin_fabsf(w0) * SW <= 65504.f) || !(__builtin_fabsf(w1) * SW <= 65504.f)) {
+    if (overflow) atomicOr(overflow, 1u);
+  }
+  const int rr = 8 * (e >> 2) + (e & 3), kk = k >> 4, kr = k & 15;
+  const int a = kr >> 3, h = (kr >> 2) & 1, ii = kr & 3, j = 4 * a + ii;
+  const size_t o_ = ((size_t)(2 * kk) * 64 + h * 32 + rr) * 8 + j;
+  *reinterpret_cast<unsigned*>(img + o_) = hi;
+  *reinterpret_cast<unsigned*>(img + o_ + 64 * 8) = lo;
+}
+
+// DCF_HC_VECTOR_OUT: the output convolution on the vector ALUs from fp32 weights in LDS (the form before the chain image of Wout),
+// kept for A/B builds.
+// NO = 2 is the compiled width of the output convolution; a head with one output leaves the second one's weights zero.
 // blockIdx.y picks the head: two heads of the same width on the same rows (cls_head2 and reg_head) share a grid, so the partly
 // filled last round of workgroups is paid once, not twice.
 struct HeadChainBatch { HeadChainArgs a[2]; };
@@ -133,9 +163,13 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   constexpr int KS = G::KS, KH = G::KH, NT = G::NT, STAGE = G::STAGE, PIECES = G::PIECES, NPW = G::NPW;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   float* lds_ln = reinterpret_cast<float*>(lds + 2 * STAGE);      // ln1_w, ln1_b, ln2_w, ln2_b: 4 x [C]
+#ifdef DCF_HC_VECTOR_OUT
   float* lds_wo = lds_ln + 4 * C;                                  // [NO][3][C]
-  // boundary rows of the waves: xch[parity][wave][0: last row's tap-0 product, 1: first row's tap-2 product][lane half][16]
   float* lds_x = lds_wo + NO * 3 * C;
+#else
+  // boundary rows of the waves: xch[parity][wave][0: last row's tap-0 product, 1: first row's tap-2 product][lane half][16]
+  float* lds_x = lds_ln + 4 * C;
+#endif
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned lane16 = (unsigned)lane * 16u;
@@ -171,7 +205,9 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   for (int i = tid; i < C; i += 256) {
     lds_ln[i] = p.ln1_w[i]; lds_ln[C + i] = p.ln1_b[i]; lds_ln[2 * C + i] = p.ln2_w[i]; lds_ln[3 * C + i] = p.ln2_b[i];
   }
+#ifdef DCF_HC_VECTOR_OUT
   for (int i = tid; i < NO * 3 * C; i += 256) lds_wo[i] = i < p.NO * 3 * C ? p.Wout[i] : 0.f;
+#endif
 
   // Register budget: X planes 8 KS, Y 16 NT, Z 48, fragments 48.  Y and Z live in accumulation registers (192 of 256 at C = 288);
   // the planes of the first XA K steps join them there (MFMA operands may), which leaves the ordinary registers room for two
@@ -234,11 +270,16 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
     unsigned ab = lane16 + HF * STAGE;
     asm volatile("" : "+v"(ab));
     const unsigned char* buf = lds + ab;
-    // the next stage: same layer, or the first one of layer 2, or none
+    // the next stage: same layer, or the first one of layer 2, or the image of the output convolution (one stage)
     constexpr bool LAST = OT == NT - 1 && HF == 1;
+#ifdef DCF_HC_VECTOR_OUT
     const unsigned short* nimg = LAST ? p.W2c : (layer ? p.W2c : p.W1c);
-    const int nsl = LAST ? 0 : 2 * OT + HF + 1;
     const bool has_next = !LAST || layer == 0;             // wave uniform
+#else
+    const unsigned short* nimg = LAST ? (layer ? p.Woc : p.W2c) : (layer ? p.W2c : p.W1c);
+    const bool has_next = true;
+#endif
+    const int nsl = LAST ? 0 : 2 * OT + HF + 1;
     f32x16 (&Z)[3] = Z2[OT & 1];
     if constexpr (HF == 0) {
 #pragma unroll
@@ -400,10 +441,16 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
     };
     tiles(tiles, std::integral_constant<int, 0>{});
     STAMP(2);
+#ifndef DCF_HC_VECTOR_OUT
+    if (layer == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's pieces of the output convolution's image have landed
+#endif
     __syncthreads();
     fixup(std::integral_constant<int, NT - 1>{});
     ln_relu(lds_ln + 2 * C * layer, lds_ln + 2 * C * layer + C);
-    if (layer == 0) {                                      // the next layer's B operand: Y[ot][8 q .. 8 q + 7] = K step 2 ot + q
+#ifdef DCF_HC_VECTOR_OUT
+    if (layer == 0)
+#endif
+    {                                                      // the next product's B operand: Y[ot][8 q .. 8 q + 7] = K step 2 ot + q
 #pragma unroll
       for (int ot = 0; ot < NT; ++ot)
 #pragma unroll
@@ -419,6 +466,7 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   }
 
   STAMP(4);
+#ifdef DCF_HC_VECTOR_OUT
   // output convolution (head.py:60, :99): per-lane tap partials over the lane's channels, the two lane halves added, the taps
   // put together across rows as above
   float pt[3][NO];
@@ -441,6 +489,36 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   float d0[NO], d1[NO], d2[NO];
 #pragma unroll
   for (int o = 0; o < NO; ++o) { d0[o] = xor32_sum(pt[0][o]); d1[o] = xor32_sum(pt[1][o]); d2[o] = xor32_sum(pt[2][o]); }
+#else
+  // output convolution (head.py:60, :99) as the chain's last product: Z = Wo Y^T from the image in ring buffer 0 (requested during
+  // the last trunk stage, waited for in front of the barrier above) and the planes of Y the split above made.  One accumulator per
+  // term (dependent MFMAs into one accumulator issue at half rate); output e = 2 tap + o of the lane's row comes out in register e
+  // of the lanes of half 0 (k_split_chain_out), the lanes of half 1 hold the products of zero rows
+  float d0[NO], d1[NO], d2[NO];
+  {
+    f32x16 (&T3)[3] = Z2[0];
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) T3[t][e] = 0.f;
+    const unsigned char* buf = lds + lane16;
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+      const f16x8 ah = *reinterpret_cast<const f16x8*>(buf + (2 * kk) * 1024), al = *reinterpret_cast<const f16x8*>(buf + (2 * kk + 1) * 1024);
+      T3[0] = mma(al, xh[kk], T3[0]);
+      T3[1] = mma(ah, xl[kk], T3[1]);
+      T3[2] = mma(ah, xh[kk], T3[2]);
+    }
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      d0[o] = ((T3[0][o] + T3[1][o]) + T3[2][o]) * UNSCALE;
+      d1[o] = ((T3[0][2 + o] + T3[1][2 + o]) + T3[2][2 + o]) * UNSCALE;
+      d2[o] = ((T3[0][4 + o] + T3[1][4 + o]) + T3[2][4 + o]) * UNSCALE;
+    }
+    // (a second-layer activation beyond the scaled fp16 range makes its products non-finite: no LayerNorm behind this one to see it)
+    bad |= h == 0 && !(__builtin_fabsf((d0[0] + d0[1]) + (d1[0] + d1[1]) + (d2[0] + d2[1])) <= 3.4028234664e38f);
+  }
+#endif
   __syncthreads();                                         // (everybody is past the last fix-up: the exchange area is free)
   if (h == 0) {
 #pragma unroll
@@ -497,6 +575,18 @@ namespace dcf {
 
 bool head_chain_supports(int C, int NO) { return (C == 256 || C == 288) && (NO == 1 || NO == 2); }
 
+size_t head_chain_out_image_halfs(int C) { return (size_t)(3 * (C / 32) * 2) * 512; }
+
+int launch_split_chain_out(const float* Wout, int NO, unsigned short* img, int C, hipStream_t stream, unsigned* overflow) {
+  DCF_CHECK((C == 256 || C == 288) && (NO == 1 || NO == 2), "launch_split_chain_out: C = %d, NO = %d", C, NO);
+  DCF_HIP(hipMemsetAsync(img, 0, head_chain_out_image_halfs(C) * sizeof(unsigned short), stream));
+  const int n = 6 * (C / 2);
+  if (C == 256) hipLaunchKernelGGL(k_split_chain_out<256>, dim3((n + 255) / 256), dim3(256), 0, stream, Wout, NO, img, overflow);
+  else hipLaunchKernelGGL(k_split_chain_out<288>, dim3((n + 255) / 256), dim3(256), 0, stream, Wout, NO, img, overflow);
+  DCF_HIP(hipGetLastError());
+  return 0;
+}
+
 size_t head_chain_image_halfs(int C) { return (size_t)(C / 32) * 2 * (3 * (C / 32) * 2) * 512; }
 
 int launch_split_chain3(const float* Wp, unsigned short* img, int C, hipStream_t stream, unsigned* overflow) {
@@ -510,7 +600,12 @@ int launch_split_chain3(const float* Wp, unsigned short* img, int C, hipStream_t
 
 template <int C>
 static int launch_hc(const HeadChainArgs* a, int count, hipStream_t stream) {
+#ifdef DCF_HC_VECTOR_OUT
   constexpr int bytes = 2 * Geo<C>::STAGE + (4 * C + 2 * 3 * C + 2 * 4 * 2 * 2 * 16) * (int)sizeof(float);
+#else
+  constexpr int bytes = 2 * Geo<C>::STAGE + (4 * C + 2 * 4 * 2 * 2 * 16) * (int)sizeof(float);
+  static_assert(2 * Geo<C>::KS <= Geo<C>::PIECES, "the image of the output convolution fits a stage");
+#endif
   if (raise_lds_limit<&k_head_chain<C>>(bytes)) return -1;
   HeadChainBatch b{};
   for (int i = 0; i < count; ++i) b.a[i] = a[i];
@@ -528,6 +623,7 @@ int launch_head_chain(const HeadChainArgs* a, int count, int C, hipStream_t stre
                   a[i].ln2_b && a[i].Wout && a[i].bout && a[i].lt && a[i].out, "launch_head_chain: null argument or unequal row counts");
     DCF_CHECK((reinterpret_cast<uintptr_t>(a[i].X) & 15) == 0 && a[i].ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(a[i].W1c) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(a[i].W2c) & 15) == 0, "launch_head_chain: X / weight images must be 16-byte aligned");
+    DCF_CHECK(a[i].Woc && (reinterpret_cast<uintptr_t>(a[i].Woc) & 15) == 0, "launch_head_chain: no image of the output convolution, or not 16-byte aligned");
   }
   return C == 256 ? launch_hc<256>(a, count, stream) : launch_hc<288>(a, count, stream);
 }

@@ -252,7 +252,7 @@ int dcf_op_head(const float* X, const uint8_t* mask, const float* W1, const floa
   const int rows = B * T, nterms = dcf::GEMM_F16X3;
   float *wp[2] = {nullptr, nullptr}, *wo = nullptr, *ha = nullptr, *hb = nullptr;
   uint8_t* nbr = nullptr;
-  unsigned short* img[2] = {nullptr, nullptr};
+  unsigned short *img[2] = {nullptr, nullptr}, *woc = nullptr;
   dcf::StreamScratch sc(st);
   dcf::LevelTable lt{}, *d_lt = nullptr;
   lt.n_levels = 1; lt.B = B; lt.S = T; lt.T[0] = T; lt.start[0] = 0; lt.start[1] = rows; lt.off[0] = 0; lt.scale[0] = scale;
@@ -271,9 +271,13 @@ int dcf_op_head(const float* X, const uint8_t* mask, const float* W1, const floa
   dcf::launch_permute3(Wout, wo, NO, C, 3, 0, 2, 1, st);
   const int mode = scale != 0.f ? 1 : 0;                    // scale = 0: raw logits (ClsHead); otherwise relu(scale * y) (RegHead)
   if (rc == 0 && chain) {
+    if (sc.take(&woc, dcf::head_chain_out_image_halfs(C))) return -1;
+    rc = dcf::launch_split_chain_out(wo, NO, woc, C, st);
+  }
+  if (rc == 0 && chain) {
     dcf::HeadChainArgs a{};
     a.X = X; a.ldx = C; a.nbr = nbr; a.W1c = img[0]; a.W2c = img[1]; a.ln1_w = ln1_w; a.ln1_b = ln1_b; a.ln2_w = ln2_w; a.ln2_b = ln2_b;
-    a.Wout = wo; a.bout = bout; a.lt = d_lt; a.out = out; a.rows = rows; a.NO = NO; a.mode = mode; a.query_major = 0;
+    a.Wout = wo; a.Woc = woc; a.bout = bout; a.lt = d_lt; a.out = out; a.rows = rows; a.NO = NO; a.mode = mode; a.query_major = 0;
     rc = dcf::launch_head_chain(&a, 1, C, st);
   } else if (rc == 0) {
     if (sc.take(&ha, (size_t)rows * C) || sc.take(&hb, (size_t)rows * C)) return -1;

@@ -2,6 +2,7 @@
 # Diagnostic build of csrc/head_chain.hip with in-kernel stamps (wave 0 of workgroup 1): private library copy under /tmp, the head
 # operator alone (tools/head_time.py), cycle shares of the segments.  GPU box only.  usage: tools/hc_stamp.sh [C] [rows]
 # HC_ABLATIONS="-DDCF_HC_NO_DMA -DDCF_HC_NO_LDS": further builds without the weight stream / without the fragment reads (timing only)
+# HC_ABLATIONS="-DDCF_HC_VECTOR_OUT": a further build with the output convolution on the vector ALUs (results valid: the A/B form)
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf /tmp/hcstamp && mkdir -p /tmp/hcstamp && cp -r $R/cvpr2025-decafnet_amd /tmp/hcstamp/ && cd /tmp/hcstamp/cvpr2025-decafnet_amd
