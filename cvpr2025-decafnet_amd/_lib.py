@@ -222,6 +222,16 @@ HALF_SIGNATURES = {
 }
 
 
+# the half-feature training-front-end extension (include/decafnet_hip_front_half.h, dcf_front_half_ext_version): same shared object, a
+# ninth table -- the eight above are frozen (tests/test_front_half_cpu.py checks this table against its header).  The operators of
+# FRONT_SIGNATURES with ``vid`` / ``shallow`` the device address of IEEE binary16 values; ``nq`` is a HOST array of int32.
+FRONT_HALF_SIGNATURES = {
+    'dcf_front_half_ext_version': (i32, []),
+    'dcf_op_vidmap_shared_h': (i32, [c_f16p, c_f16p, c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_i32p, c_f32p, i32, i32, i32, i32, i32, vp]),
+    'dcf_op_vidmap_shared_bwd_h': (i32, [c_f16p, c_f16p, c_f32p, c_u8p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, i32, vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -234,7 +244,7 @@ def lib():
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
                 list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(CLOCK_SIGNATURES.items()) + \
-                list(HALF_SIGNATURES.items()):
+                list(HALF_SIGNATURES.items()) + list(FRONT_HALF_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -299,7 +299,8 @@ def masked_conv1d(x, mask, weight, bias=None, stride=1):
 
 
 class _GatedVidMapFn(torch.autograd.Function):
-    """dcf_op_vidmap_shared / dcf_op_vidmap_shared_bwd (csrc/front_grad.hip).  Saves its inputs and nothing else."""
+    """dcf_op_vidmap_shared / dcf_op_vidmap_shared_bwd (csrc/front_grad.hip), or their ``_h`` forms on float16 features
+    (include/decafnet_hip_front_half.h).  Saves its inputs -- the features as they are stored -- and nothing else."""
 
     @staticmethod
     def forward(ctx, vid, shallow, gate, mask, correl, sizes, weight, bias, skip):
@@ -310,9 +311,9 @@ class _GatedVidMapFn(torch.autograd.Function):
         y = torch.empty(nq, T, E, dtype=torch.float32, device=vid.device)
         host_nq = torch.tensor(sizes, dtype=torch.int32)
         w, b = weight.detach().float().reshape(E, -1).contiguous(), bias.detach().float().contiguous()
-        _lib.check(_lib.lib().dcf_op_vidmap_shared(_lib.ptr(vid), _lib.ptr(shallow), _lib.ptr(w), _lib.ptr(b), _lib.ptr(gate), _lib.ptr(mask),
-                                                   _lib.ptr(correl), _lib.ptr(host_nq), _lib.ptr(y), nvid, D, T, E, flags, _lib.current_stream()),
-                   'dcf_op_vidmap_shared')
+        name = 'dcf_op_vidmap_shared_h' if vid.dtype == torch.float16 else 'dcf_op_vidmap_shared'
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(vid), _lib.ptr(shallow), _lib.ptr(w), _lib.ptr(b), _lib.ptr(gate), _lib.ptr(mask),
+                                             _lib.ptr(correl), _lib.ptr(host_nq), _lib.ptr(y), nvid, D, T, E, flags, _lib.current_stream()), name)
         ctx.save_for_backward(vid, gate, mask, *(z for z in (shallow, correl) if z is not None))
         ctx.msf, ctx.scat, ctx.sizes, ctx.flags, ctx.wshape = shallow is not None, correl is not None, sizes, flags, tuple(weight.shape)
         return y
@@ -332,9 +333,10 @@ class _GatedVidMapFn(torch.autograd.Function):
         gw = torch.empty(ctx.wshape, dtype=torch.float32, device=vid.device)
         gb = torch.empty(E, dtype=torch.float32, device=vid.device) if want_b else None
         host_nq = torch.tensor(ctx.sizes, dtype=torch.int32)
-        _lib.check(_lib.lib().dcf_op_vidmap_shared_bwd(_lib.ptr(vid), _lib.ptr(shallow), _lib.ptr(gate), _lib.ptr(mask), _lib.ptr(correl),
-                                                       _lib.ptr(host_nq), _lib.ptr(gy), _lib.ptr(gw), _lib.ptr(gb), nvid, D, T, E, ctx.flags, 0,
-                                                       _lib.current_stream()), 'dcf_op_vidmap_shared_bwd')
+        name = 'dcf_op_vidmap_shared_bwd_h' if vid.dtype == torch.float16 else 'dcf_op_vidmap_shared_bwd'
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(vid), _lib.ptr(shallow), _lib.ptr(gate), _lib.ptr(mask), _lib.ptr(correl),
+                                             _lib.ptr(host_nq), _lib.ptr(gy), _lib.ptr(gw), _lib.ptr(gb), nvid, D, T, E, ctx.flags, 0,
+                                             _lib.current_stream()), name)
         return None, None, None, None, None, None, (gw if want_w else None), gb, None
 
 
@@ -347,10 +349,16 @@ def gated_vid_map(vid, shallow, gate, mask, correl, text_size, weight, bias, ski
     ``W[:, :D] . vid`` and ``W[:, D:2D] . shallow`` are computed once per video, 64-clip tiles that no query of the video keeps not
     at all (``skip=False`` computes them: a test switch, the same bits); the backward gives the weight and the bias their gradients
     (include/decafnet_hip_front.h) and saves only its inputs.  The features, the gate and the scores are data: a feature tensor
-    that requires a gradient is refused."""
+    that requires a gradient is refused.
+    ``vid`` / ``shallow`` may be ``torch.float16``, both or neither (one of the two is a ValueError): a float16 pair goes to
+    dcf_op_vidmap_shared_h / dcf_op_vidmap_shared_bwd_h (include/decafnet_hip_front_half.h) as it is stored -- no fp32 copy is made or
+    saved -- and the result and the gradients are those of the same values passed as fp32, bit for bit."""
     for name, z in (('vid', vid), ('shallow', shallow), ('gate', gate), ('correl', correl)):
         if z is not None and z.requires_grad:
             raise ValueError(f'gated_vid_map: `{name}` requires a gradient; the features, the gate and the scores are data (no gradient reaches them)')
+    if torch.is_tensor(vid) and torch.is_tensor(shallow):
+        from .modeling import _check_feature_dtypes
+        _check_feature_dtypes(vid, shallow)
     if not (torch.is_tensor(vid) and vid.is_cuda and vid.dim() == 3):
         raise RuntimeError('gated_vid_map: (nvid, D, T) features on the GPU are required (there is no CPU path)')
     nvid, D, T = vid.shape
@@ -369,7 +377,8 @@ def gated_vid_map(vid, shallow, gate, mask, correl, text_size, weight, bias, ski
     f = lambda z: None if z is None else z.detach().float().contiguous()
     m = mask.detach()
     m = (m if m.dtype == torch.bool else m != 0).contiguous()
-    return _GatedVidMapFn.apply(f(vid), f(shallow), f(gate), m, f(correl), sizes, weight, bias, bool(skip))
+    x = (lambda z: None if z is None else z.detach().contiguous()) if vid.dtype == torch.float16 else f      # float16: as stored
+    return _GatedVidMapFn.apply(x(vid), x(shallow), f(gate), m, f(correl), sizes, weight, bias, bool(skip))
 
 
 def strided_masked_conv1d(x, mask, weight):

@@ -12,7 +12,7 @@ constexpr int FG_NQ_CHUNK = 64;         // videos whose query counts one table l
 // dW[n][c] = sum_b sum_t R[b][t][n] X[b][c][t] for up to two (R, X) pairs (blockIdx.z): the expert half and the shallow half
 struct FrontWgradArgs {
   const float* R[2];          // (nvid, T, N) token-major row sums of the upstream gradient
-  const float* X[2];          // (nvid, C, T) channel-major features
+  const void* X[2];           // (nvid, C, T) channel-major features: fp32, or binary16 for the half form of the kernel
   const unsigned* absmax[2];  // device word per pair: bits of max |R|
   const uint8_t* skip[2];     // (nvid, ntiles) or nullptr: tile f of video b holds a clip some query keeps; 0 = no K step
   float* part[2];             // (nslices, N, C) partial sums in the scaled domain
@@ -20,6 +20,7 @@ struct FrontWgradArgs {
   int slice_t, slices_per_video, ntiles;     // slice_t is a multiple of FG_TILE
 };
 
-int launch_front_wgrad(const FrontWgradArgs& a, int pairs, hipStream_t st);
+// half: X holds binary16 values (any alignment), read as stored: one X plane and two products per k-step instead of two and three
+int launch_front_wgrad(const FrontWgradArgs& a, int pairs, hipStream_t st, bool half = false);
 
 }  // namespace dcf

@@ -21,8 +21,17 @@
 //
 // The per-video query counts arrive as a host array; k_fg_tables receives them by value, 64 videos per launch, and writes the
 // device tables (first row of every video, video of every row): no host memory is read after the call returns.
+//
+// Features stored as IEEE binary16 (include/decafnet_hip_front_half.h): dcf_op_vidmap_shared_h / dcf_op_vidmap_shared_bwd_h share
+// everything above.  The forward products take the A_CHANMAJOR_H mode of the split tile path where it applies and one upcast into
+// scratch otherwise; the weight gradient is k_fg_wgrad<true>, which reads the halves for every shape.  Both return the bits of the
+// fp32 operators on the upcast values.
+#include <type_traits>
+
 #include "../../include/decafnet_hip_front.h"
+#include "../../include/decafnet_hip_front_half.h"
 #include "conv_grad.h"
+#include "engine.h"
 #include "front_grad.h"
 #include "gemm.h"
 #include "grad_common.h"
@@ -31,6 +40,10 @@
 namespace dcf {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// a thread's 8 clips of X on their way to LDS: fp32 values one by one, or the 16 bytes of eight halves
+template <bool HALF> struct FrontXRegs { float v[8]; };
+template <> struct FrontXRegs<true> { f16x8 v; };
 
 constexpr int FG_ROWS = 32;      // clips per LDS chunk (two k-steps of 16)
 constexpr int FG_PITCH = 40;     // halfs per (plane, column): 32 clips + 8 pad = 80 B, every 16-byte vector stays aligned
@@ -125,13 +138,21 @@ __global__ __launch_bounds__(256) void k_fg_rowsums(const float* __restrict__ dY
 }
 
 // accumulator element e of lane (h, r32): n = 4 h + (e & 3) + 8 (e >> 2) (the A operand's row), c = r32 (the B operand's column)
+// HALF: X holds binary16 values (include/decafnet_hip_front_half.h).  A thread's 8 clips are ONE 16-byte load where their address
+// is 16-byte aligned and all 8 lie in the slice, 8 two-byte loads otherwise.  The value times 2^4 -- an exact fp16 product over the
+// operator's range -- IS the hi plane of the fp32 form and the lo plane of the fp32 form is exactly zero for it, so one X plane is
+// staged and the product r_hi . x_lo (exact zeros into the accumulator) is not issued: r_lo . x_hi, then r_hi . x_hi, the order of
+// the fp32 form without its middle term.
+template <bool HALF>
 __global__ __launch_bounds__(256) void k_fg_wgrad(FrontWgradArgs p) {
+  constexpr int XPL = HALF ? 1 : 2;                 // planes of the X tile
+  using x_elem = std::conditional_t<HALF, _Float16, float>;
   __shared__ __attribute__((aligned(16))) _Float16 s_r[2 * 64 * FG_PITCH];
-  __shared__ __attribute__((aligned(16))) _Float16 s_x[2 * 64 * FG_PITCH];
+  __shared__ __attribute__((aligned(16))) _Float16 s_x[XPL * 64 * FG_PITCH];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int z = blockIdx.z;
   const float* __restrict__ Rp = z == 0 ? p.R[0] : p.R[1];
-  const float* __restrict__ Xp = z == 0 ? p.X[0] : p.X[1];
+  const x_elem* __restrict__ Xp = static_cast<const x_elem*>(z == 0 ? p.X[0] : p.X[1]);
   const unsigned* __restrict__ am = z == 0 ? p.absmax[0] : p.absmax[1];
   const uint8_t* __restrict__ skip = z == 0 ? p.skip[0] : p.skip[1];
   float* __restrict__ part = z == 0 ? p.part[0] : p.part[1];
@@ -151,7 +172,7 @@ __global__ __launch_bounds__(256) void k_fg_wgrad(FrontWgradArgs p) {
   const int c_g = tc * 64 + xc;
   const bool c_ok = c_g < C;
   const float* __restrict__ rp = Rp + (int64_t)b * T * N + n_g;
-  const float* __restrict__ xp = Xp + ((int64_t)b * C + (c_ok ? c_g : 0)) * T;
+  const x_elem* __restrict__ xp = Xp + ((int64_t)b * C + (c_ok ? c_g : 0)) * T;
   const int h = lane >> 5, r32 = lane & 31;
   const int wn = wave & 1, wc = wave >> 1;
   const bool active = tn * 64 + wn * 32 < N && tc * 64 + wc * 32 < C;      // (N, C are multiples of 32: a 32-block is whole or absent)
@@ -165,17 +186,25 @@ __global__ __launch_bounds__(256) void k_fg_wgrad(FrontWgradArgs p) {
     while (r < t_end && skip && !skip[(int64_t)b * p.ntiles + r / FG_TILE]) r += FG_ROWS;
     return r;
   };
-  float rv[8], xv[8];
+  float rv[8];
+  FrontXRegs<HALF> xv;
   auto load = [&](int r0) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int t = r0 + wave * 8 + i;
       rv[i] = (n_ok && t < t_end) ? rp[(int64_t)t * N] : 0.f;
     }
+    if constexpr (HALF) {
+      const int t = r0 + xt;
+      if (c_ok && t + 8 <= t_end && (reinterpret_cast<uintptr_t>(xp + t) & 15) == 0) {
+        xv.v = *reinterpret_cast<const f16x8*>(xp + t);
+        return;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int t = r0 + xt + i;
-      xv[i] = (c_ok && t < t_end) ? xp[t] : 0.f;
+      xv.v[i] = (c_ok && t < t_end) ? xp[t] : (x_elem)0;
     }
   };
 
@@ -183,7 +212,7 @@ __global__ __launch_bounds__(256) void k_fg_wgrad(FrontWgradArgs p) {
   if (r0 < t_end) load(r0);
   while (r0 < t_end) {
     {
-      f16x8 rh, rl, xh, xl;
+      f16x8 rh, rl;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float v = rv[i] * s;
@@ -191,17 +220,22 @@ __global__ __launch_bounds__(256) void k_fg_wgrad(FrontWgradArgs p) {
         rh[i] = hi;
         rl[i] = (_Float16)(v - (float)hi);
       }
+      f16x8 xh, xl;
+      if constexpr (HALF) {
+        xh = xv.v * (_Float16)FG_SX;                 // exact; there is no lo plane
+      } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float v = xv[i];
-        const _Float16 hi = (_Float16)(v * FG_SX);
-        xh[i] = hi;
-        xl[i] = (_Float16)__builtin_fmaf(v, FG_SX, -(float)hi);
+        for (int i = 0; i < 8; ++i) {
+          const float v = xv.v[i];
+          const _Float16 hi = (_Float16)(v * FG_SX);
+          xh[i] = hi;
+          xl[i] = (_Float16)__builtin_fmaf(v, FG_SX, -(float)hi);
+        }
       }
       *reinterpret_cast<f16x8*>(&s_r[(0 * 64 + lane) * FG_PITCH + wave * 8]) = rh;
       *reinterpret_cast<f16x8*>(&s_r[(1 * 64 + lane) * FG_PITCH + wave * 8]) = rl;
       *reinterpret_cast<f16x8*>(&s_x[(0 * 64 + xc) * FG_PITCH + xt]) = xh;
-      *reinterpret_cast<f16x8*>(&s_x[(1 * 64 + xc) * FG_PITCH + xt]) = xl;
+      if constexpr (!HALF) *reinterpret_cast<f16x8*>(&s_x[(1 * 64 + xc) * FG_PITCH + xt]) = xl;
     }
     __syncthreads();
     r0 = next_chunk(r0 + FG_ROWS);
@@ -213,9 +247,11 @@ __global__ __launch_bounds__(256) void k_fg_wgrad(FrontWgradArgs p) {
         const f16x8 a_hi = *reinterpret_cast<const f16x8*>(&s_r[(0 * 64 + wn * 32 + r32) * FG_PITCH + ko]);
         const f16x8 a_lo = *reinterpret_cast<const f16x8*>(&s_r[(1 * 64 + wn * 32 + r32) * FG_PITCH + ko]);
         const f16x8 b_hi = *reinterpret_cast<const f16x8*>(&s_x[(0 * 64 + wc * 32 + r32) * FG_PITCH + ko]);
-        const f16x8 b_lo = *reinterpret_cast<const f16x8*>(&s_x[(1 * 64 + wc * 32 + r32) * FG_PITCH + ko]);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, acc, 0, 0, 0);
+        if constexpr (!HALF) {
+          const f16x8 b_lo = *reinterpret_cast<const f16x8*>(&s_x[(1 * 64 + wc * 32 + r32) * FG_PITCH + ko]);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, acc, 0, 0, 0);
+        }
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc, 0, 0, 0);
       }
     }
@@ -250,9 +286,10 @@ __global__ __launch_bounds__(256) void k_fg_reduce(const float* __restrict__ par
   out[o] = accumulate ? out[o] + v : v;
 }
 
-int launch_front_wgrad(const FrontWgradArgs& a, int pairs, hipStream_t st) {
+int launch_front_wgrad(const FrontWgradArgs& a, int pairs, hipStream_t st, bool half) {
   const dim3 grid(((a.N + 63) / 64) * ((a.C + 63) / 64), a.nvid * a.slices_per_video, pairs);
-  hipLaunchKernelGGL(k_fg_wgrad, grid, dim3(256), 0, st, a);
+  if (half) hipLaunchKernelGGL(k_fg_wgrad<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_fg_wgrad<false>, grid, dim3(256), 0, st, a);
   DCF_HIP(hipGetLastError());
   return 0;
 }
@@ -262,7 +299,7 @@ struct FrontShape {
   int nvid, D, T, E, Cin, rows_q, ntiles;      // rows_q = B'
 };
 
-static int front_check(const char* what, const float* vid, const float* gate, const uint8_t* mask, const int32_t* nq, int32_t nvid, int32_t D,
+static int front_check(const char* what, const void* vid, const float* gate, const uint8_t* mask, const int32_t* nq, int32_t nvid, int32_t D,
                        int32_t T, int32_t E, bool msf, bool scat, FrontShape* s) {
   DCF_CHECK(vid && gate && mask && nq, "%s: null argument", what);
   DCF_CHECK(nvid > 0 && nvid <= 65535 && T > 0, "%s: nvid = %d (1 .. 65535), T = %d (>= 1)", what, nvid, T);
@@ -294,29 +331,39 @@ static int front_tables(const FrontShape& s, const int32_t* nq, const float* gat
   return 0;
 }
 
-}  // namespace dcf
+static bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
-using namespace dcf;
-
-extern "C" {
-
-int dcf_front_ext_version(void) { return DCF_FRONT_EXT_VERSION; }
-
-int dcf_op_vidmap_shared(const float* vid, const float* shallow, const float* W, const float* bias, const float* gate,
-                         const uint8_t* mask, const float* correl, const int32_t* nq, float* Y, int32_t nvid, int32_t D, int32_t T,
-                         int32_t E, int32_t flags, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const char* what = "dcf_op_vidmap_shared";
+// dcf_op_vidmap_shared (half = false: vid / shallow fp32) and dcf_op_vidmap_shared_h (half = true: binary16, read by the split tile
+// path's A_CHANMAJOR_H mode where it applies, upcast once into scratch otherwise; the option half_native decides as in the engine)
+static int front_forward(const char* what, const void* vid_in, const void* shallow_in, bool half, const float* W, const float* bias,
+                         const float* gate, const uint8_t* mask, const float* correl, const int32_t* nq, float* Y, int32_t nvid, int32_t D,
+                         int32_t T, int32_t E, int32_t flags, hipStream_t st) {
   FrontShape s{};
   DCF_CHECK(W && bias && Y, "%s: null argument", what);
-  if (front_check(what, vid, gate, mask, nq, nvid, D, T, E, shallow != nullptr, correl != nullptr, &s)) return -1;
+  if (front_check(what, vid_in, gate, mask, nq, nvid, D, T, E, shallow_in != nullptr, correl != nullptr, &s)) return -1;
+  bool native = false;
+  if (half) {
+    const int want = debug_option("half_native", 1);
+    native = want != 0 && E % 128 == 0 && T % 4 == 0 && aligned_to(vid_in, 8) && aligned_to(shallow_in, 8);
+    DCF_CHECK(native || want != 2, "%s: these products cannot read the half features natively (E %% 128 != 0, T %% 4 != 0 or a feature pointer "
+                                   "that is not 8-byte aligned) and the option half_native = 2 forbids the upcast", what);
+  }
   unsigned* status = nullptr;
   if (cg_begin(what, st, &status)) return -1;
   const int Cin = s.Cin;
-  const size_t pe = (size_t)nvid * T * E;
-  // the split tile path of the channel-major GEMM: 64-row tiles of 128 columns, 16-byte loads along T
-  const bool split = E % 128 == 0 && T % 4 == 0 && (reinterpret_cast<uintptr_t>(vid) & 15) == 0 && (!shallow || (reinterpret_cast<uintptr_t>(shallow) & 15) == 0);
+  const size_t pe = (size_t)nvid * T * E, px = (size_t)nvid * D * T;
   StreamScratch sc(st);
+  const void *vid = vid_in, *shallow = shallow_in;
+  if (half && !native) {                              // the fp32 path on fp32 copies
+    float *up1 = nullptr, *up2 = nullptr;
+    if (sc.take(&up1, px) || (shallow_in && sc.take(&up2, px))) return -1;
+    if (launch_half_to_f32(static_cast<const uint16_t*>(vid_in), up1, (int64_t)px, st)) return -1;
+    if (shallow_in && launch_half_to_f32(static_cast<const uint16_t*>(shallow_in), up2, (int64_t)px, st)) return -1;
+    vid = up1; shallow = up2;
+  }
+  const size_t xbytes = native ? sizeof(uint16_t) : sizeof(float);
+  // the split tile path of the channel-major GEMM: 64-row tiles of 128 columns, 16-byte loads along T (8-byte loads of halves)
+  const bool split = native || (E % 128 == 0 && T % 4 == 0 && aligned_to(vid, 16) && aligned_to(shallow, 16));
   int *qoff = nullptr, *vtab = nullptr;
   uint8_t* tflags = nullptr;
   float *P1 = nullptr, *P2 = nullptr, *W1c = nullptr, *W2c = nullptr, *w3c = nullptr;
@@ -339,24 +386,25 @@ int dcf_op_vidmap_shared(const float* vid, const float* shallow, const float* W,
     if (rc == 0 && shallow) rc = launch_split_planes(W + D, pl2, E, D, Cin, st, GEMM_F16X3, status);
   }
   // the products, three videos per grid; the expert half leaves the row tiles no query keeps unwritten (split path)
-  for (int half = 0; half < (shallow ? 2 : 1) && rc == 0; ++half) {
-    const float* X = half ? shallow : vid;
-    float* P = half ? P2 : P1;
+  for (int pair = 0; pair < (shallow ? 2 : 1) && rc == 0; ++pair) {
+    const char* X = static_cast<const char*>(pair ? shallow : vid);       // (GemmArgs::A carries the address of the halves too)
+    float* P = pair ? P2 : P1;
     for (int v0 = 0; v0 < nvid && rc == 0; v0 += 3) {
       GemmArgs g[3];
       const int ng = nvid - v0 < 3 ? nvid - v0 : 3;
       for (int i = 0; i < ng; ++i) {
         g[i] = GemmArgs{};
-        g[i].A = X + (size_t)(v0 + i) * D * T; g[i].lda = T; g[i].C = P + (size_t)(v0 + i) * T * E; g[i].ldc = E;
+        g[i].A = reinterpret_cast<const float*>(X + (size_t)(v0 + i) * D * T * xbytes); g[i].lda = T;
+        g[i].C = P + (size_t)(v0 + i) * T * E; g[i].ldc = E;
         g[i].M = T; g[i].N = E; g[i].K = D;
         if (split) {
-          g[i].W = W + (half ? D : 0); g[i].ldw = Cin; g[i].Ws = half ? pl2 : pl1; g[i].status = status;
-          if (!half) { g[i].tile_skip = tflags + (size_t)(v0 + i) * s.ntiles; g[i].skip_nq = 1; g[i].skip_stride = s.ntiles; }
+          g[i].W = W + (pair ? D : 0); g[i].ldw = Cin; g[i].Ws = pair ? pl2 : pl1; g[i].status = status;
+          if (!pair) { g[i].tile_skip = tflags + (size_t)(v0 + i) * s.ntiles; g[i].skip_nq = 1; g[i].skip_stride = s.ntiles; }
         } else {
-          g[i].W = half ? W2c : W1c; g[i].ldw = D;
+          g[i].W = pair ? W2c : W1c; g[i].ldw = D;
         }
       }
-      rc = split ? launch_gemm_split(g, ng, A_CHANMAJOR, GEMM_F16X3, st) : launch_gemm(g, ng, A_CHANMAJOR, st);
+      rc = split ? launch_gemm_split(g, ng, native ? A_CHANMAJOR_H : A_CHANMAJOR, GEMM_F16X3, st) : launch_gemm(g, ng, A_CHANMAJOR, st);
     }
   }
   if (rc == 0) rc = launch_vidmap_combine(P1, P2, bias, gate, mask, w3c, correl, Y, T, s.rows_q * T, E, 0ull, st, vtab);
@@ -364,11 +412,11 @@ int dcf_op_vidmap_shared(const float* vid, const float* shallow, const float* W,
   return rc == 0 ? cg_end(st) : rc;
 }
 
-int dcf_op_vidmap_shared_bwd(const float* vid, const float* shallow, const float* gate, const uint8_t* mask, const float* correl,
-                             const int32_t* nq, const float* dY, float* dW, float* db, int32_t nvid, int32_t D, int32_t T, int32_t E,
-                             int32_t flags, int32_t accumulate, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const char* what = "dcf_op_vidmap_shared_bwd";
+// dcf_op_vidmap_shared_bwd (half = false) and dcf_op_vidmap_shared_bwd_h (half = true: k_fg_wgrad<true> reads the stored values, for
+// every shape and alignment; nothing is upcast)
+static int front_backward(const char* what, const void* vid, const void* shallow, bool half, const float* gate, const uint8_t* mask,
+                          const float* correl, const int32_t* nq, const float* dY, float* dW, float* db, int32_t nvid, int32_t D, int32_t T,
+                          int32_t E, int32_t flags, int32_t accumulate, hipStream_t st) {
   FrontShape s{};
   DCF_CHECK(dY && dW, "%s: null argument", what);
   if (front_check(what, vid, gate, mask, nq, nvid, D, T, E, shallow != nullptr, correl != nullptr, &s)) return -1;
@@ -411,13 +459,13 @@ int dcf_op_vidmap_shared_bwd(const float* vid, const float* shallow, const float
     a.R[0] = R1; a.X[0] = vid; a.absmax[0] = words; a.skip[0] = tflags; a.part[0] = part;
     a.R[1] = R2; a.X[1] = shallow; a.absmax[1] = words + 1; a.skip[1] = nullptr; a.part[1] = part + (size_t)nslices * count;
     a.nvid = nvid; a.T = T; a.N = E; a.C = D; a.slice_t = slice_t; a.slices_per_video = spv; a.ntiles = s.ntiles;
-    rc = launch_front_wgrad(a, pairs, st);
+    rc = launch_front_wgrad(a, pairs, st, half);
   }
   if (rc == 0) {
     const dim3 gw((unsigned)((count + 255) / 256)), ge((E + 255) / 256);
-    for (int half = 0; half < pairs; ++half)
-      hipLaunchKernelGGL(k_fg_reduce, gw, dim3(256), 0, st, part + (size_t)half * nslices * count, nslices, count, (int)count, D, Cin,
-                         words + half, 1.f / FG_SX, dW + (half ? D : 0), accumulate, status);
+    for (int pair = 0; pair < pairs; ++pair)
+      hipLaunchKernelGGL(k_fg_reduce, gw, dim3(256), 0, st, part + (size_t)pair * nslices * count, nslices, count, (int)count, D, Cin,
+                         words + pair, 1.f / FG_SX, dW + (pair ? D : 0), accumulate, status);
     if (correl)
       hipLaunchKernelGGL(k_fg_reduce, ge, dim3(256), 0, st, rpart + E, nvid * nstrips, (int64_t)2 * E, E, 1, Cin, (const unsigned*)nullptr, 1.f,
                          dW + (Cin - 1), accumulate, status);
@@ -428,6 +476,42 @@ int dcf_op_vidmap_shared_bwd(const float* vid, const float* shallow, const float
   }
   rc = sc.end(rc);
   return rc == 0 ? cg_end(st) : rc;
+}
+
+}  // namespace dcf
+
+using namespace dcf;
+
+extern "C" {
+
+int dcf_front_ext_version(void) { return DCF_FRONT_EXT_VERSION; }
+
+int dcf_front_half_ext_version(void) { return DCF_FRONT_HALF_EXT_VERSION; }
+
+int dcf_op_vidmap_shared(const float* vid, const float* shallow, const float* W, const float* bias, const float* gate,
+                         const uint8_t* mask, const float* correl, const int32_t* nq, float* Y, int32_t nvid, int32_t D, int32_t T,
+                         int32_t E, int32_t flags, void* stream) {
+  return front_forward("dcf_op_vidmap_shared", vid, shallow, false, W, bias, gate, mask, correl, nq, Y, nvid, D, T, E, flags, (hipStream_t)stream);
+}
+
+int dcf_op_vidmap_shared_bwd(const float* vid, const float* shallow, const float* gate, const uint8_t* mask, const float* correl,
+                             const int32_t* nq, const float* dY, float* dW, float* db, int32_t nvid, int32_t D, int32_t T, int32_t E,
+                             int32_t flags, int32_t accumulate, void* stream) {
+  return front_backward("dcf_op_vidmap_shared_bwd", vid, shallow, false, gate, mask, correl, nq, dY, dW, db, nvid, D, T, E, flags, accumulate,
+                        (hipStream_t)stream);
+}
+
+int dcf_op_vidmap_shared_h(const uint16_t* vid, const uint16_t* shallow, const float* W, const float* bias, const float* gate,
+                           const uint8_t* mask, const float* correl, const int32_t* nq, float* Y, int32_t nvid, int32_t D, int32_t T,
+                           int32_t E, int32_t flags, void* stream) {
+  return front_forward("dcf_op_vidmap_shared_h", vid, shallow, true, W, bias, gate, mask, correl, nq, Y, nvid, D, T, E, flags, (hipStream_t)stream);
+}
+
+int dcf_op_vidmap_shared_bwd_h(const uint16_t* vid, const uint16_t* shallow, const float* gate, const uint8_t* mask, const float* correl,
+                               const int32_t* nq, const float* dY, float* dW, float* db, int32_t nvid, int32_t D, int32_t T, int32_t E,
+                               int32_t flags, int32_t accumulate, void* stream) {
+  return front_backward("dcf_op_vidmap_shared_bwd_h", vid, shallow, true, gate, mask, correl, nq, dY, dW, db, nvid, D, T, E, flags, accumulate,
+                        (hipStream_t)stream);
 }
 
 }  // extern "C"

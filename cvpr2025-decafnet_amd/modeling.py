@@ -464,6 +464,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
     # and ``forward_videos`` (include/decafnet_hip_half.h); False: they are upcast to fp32 first, as every other dtype is
     half_features = True
     last_feature_dtype = None                       # what the engine read vid / shallow_vid as in the last eval forward
+    last_train_feature_dtype = None                 # what train.training_forward handed to autograd.gated_vid_map (float16: as stored)
     last_dropout_seed = None                        # the 64-bit key of the last training forward with dropout
 
     def __init__(self, opt, second_fusion=True):

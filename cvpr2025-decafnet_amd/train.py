@@ -72,6 +72,11 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     for a model without ``enable_dropout()``.  With ``model.enable_dropout()`` the forward applies all five rates of
     ``model._dropout_rates()`` with b0 = 0 under one 64-bit key: ``dropout_seed`` if given, else ``model._next_dropout_seed()``
     (the CPU generator ``enable_dropout`` set up); the key is left in ``model.last_dropout_seed``.
+    ``vid`` / ``shallow`` may be float16, both or neither.  With ``front_end='shared'`` (or a ``scat`` model) and
+    ``model.half_features`` (default True) a float16 pair is read as it is stored -- dcf_op_sidekick_h for the scores,
+    ``autograd.gated_vid_map`` on the float16 tensors, which its backward keeps: no fp32 copy of the features exists -- and every output
+    and gradient has the bits of the same values passed as fp32.  ``model.last_train_feature_dtype`` says what ``gated_vid_map`` was
+    handed (torch.float16 or torch.float32); the dense front end and ``half_features = False`` upcast as before.
     ``front_end``: how the input of the network is made of the features.  'dense' builds the reference's (B', T, Cin) tensor --
     every video's features once per query, gated, concatenated -- and runs ``masked_conv1d`` on it.  'shared' is
     ``autograd.gated_vid_map``: the products of ``vid_map`` with the features once per video, clips that no query's gate keeps not at
@@ -100,12 +105,22 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     nq = sum(sizes)
     if len(sizes) != bs or min(sizes) < 1 or tokens.size(0) != nq or text_cls.size(0) != nq:
         raise ValueError(f'text_size {sizes} does not match {bs} videos, {tokens.size(0)} token rows and {text_cls.size(0)} text_cls rows')
+    # float16 features go to the sidekick scores and to gated_vid_map as they are stored (include/decafnet_hip_half.h,
+    # include/decafnet_hip_front_half.h); the dense front end builds an fp32 (B', T, Cin) tensor anyway and keeps its upcast
+    half = False
+    if shared and model.half_features:
+        modeling._check_feature_dtypes(vid, shallow)
+        half = vid.dtype == torch.float16
+    model.last_train_feature_dtype = torch.float16 if half else torch.float32
+    if shared and not half:
+        vid, shallow = vid.float(), shallow.float()
     gates, masks, correls, q = [], [], [], 0
     for b, k in enumerate(sizes):                                   # one video and its k queries per call
-        sh, cls = shallow[b].float().contiguous(), text_cls[q:q + k].float().contiguous()
+        sh, cls = (shallow[b] if half else shallow[b].float()).contiguous(), text_cls[q:q + k].float().contiguous()
         vm = vid_masks[b].reshape(-1).to(torch.bool).contiguous()
         correl = torch.empty(k, T, device=vid.device)
-        _lib.check(lib.dcf_op_sidekick(_lib.ptr(sh), _lib.ptr(cls), _lib.ptr(correl), D, T, k, int(model.norm), st), 'dcf_op_sidekick')
+        sidekick = 'dcf_op_sidekick_h' if half else 'dcf_op_sidekick'
+        _lib.check(getattr(lib, sidekick)(_lib.ptr(sh), _lib.ptr(cls), _lib.ptr(correl), D, T, k, int(model.norm), st), sidekick)
         gate, mo = torch.empty(k, T, device=vid.device), torch.empty(k, T, dtype=torch.bool, device=vid.device)
         _lib.check(lib.dcf_op_gate(_lib.ptr(correl), _lib.ptr(vm), _lib.ptr(gate), _lib.ptr(mo), T, k, model.sn, float(model.sratio),
                                    int(model.msf), st), 'dcf_op_gate')
