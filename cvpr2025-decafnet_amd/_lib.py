@@ -232,6 +232,15 @@ FRONT_HALF_SIGNATURES = {
 }
 
 
+# the embedding-stage extension (include/decafnet_hip_embd.h, dcf_embd_ext_version): same shared object, a tenth table -- the nine
+# above are frozen (tests/test_embd_chain_cpu.py checks this table against its header).  ``model`` is a finalized dcf_model.
+EMBD_SIGNATURES = {
+    'dcf_embd_ext_version': (i32, []),
+    'dcf_op_embd_chain': (i32, [vp, c_f32p, i64, c_u8p, i32, i32, i32, c_f32p, c_f32p, i64, vp]),
+    'dcf_op_embd_launches': (i32, [vp, c_f32p, i64, c_u8p, i32, i32, i32, c_f32p, c_f32p, i64, vp]),
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -244,7 +253,7 @@ def lib():
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
                 list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(CLOCK_SIGNATURES.items()) + \
-                list(HALF_SIGNATURES.items()) + list(FRONT_HALF_SIGNATURES.items()):
+                list(HALF_SIGNATURES.items()) + list(FRONT_HALF_SIGNATURES.items()) + list(EMBD_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

@@ -5,7 +5,7 @@
 
 One translation unit per kernel family, compiled in parallel, linked into a single shared
 object that exports the C ABI of include/decafnet_hip.h and of its extensions,
-include/decafnet_hip_train.h, include/decafnet_hip_dist.h, include/decafnet_hip_attn.h, include/decafnet_hip_front.h, include/decafnet_hip_guard.h, include/decafnet_hip_clock.h, include/decafnet_hip_half.h and include/decafnet_hip_front_half.h.  The .so stays in the source tree
+include/decafnet_hip_train.h, include/decafnet_hip_dist.h, include/decafnet_hip_attn.h, include/decafnet_hip_front.h, include/decafnet_hip_guard.h, include/decafnet_hip_clock.h, include/decafnet_hip_half.h, include/decafnet_hip_front_half.h and include/decafnet_hip_embd.h.  The .so stays in the source tree
 (git-ignored) so that it travels with the working copy to the GPU machine.
 """
 import os

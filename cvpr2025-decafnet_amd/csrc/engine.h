@@ -12,6 +12,7 @@
 #include "common.h"
 #include "dec_chain.h"
 #include "dropout.h"
+#include "embd_chain.h"
 #include "enc_chain.h"
 #include "ffn_chain.h"
 #include "gemm.h"
@@ -103,6 +104,12 @@ struct dcf_model {
   const float *embd_fc_w = nullptr, *embd_fc_b = nullptr;
   const float *embd_fc_wf = nullptr, *embd_fc_s = nullptr, *embd_fc_c = nullptr;   // vid_net.embd_fc with fusion.ln_out folded in
   std::vector<const float*> embd_conv, embd_ln_w, embd_ln_b;
+  // the embedding stage as one kernel (embd_chain.h): embd_fc folded into embd_convs[0] as a chain image + the per-tap bias [3][E],
+  // [0] for the raw stream (fusion.ln_out's affine folded in too, the kernel normalises), [1] for rows that come normalised; the
+  // chain image of embd_convs[1].  nullptr where not built, or where a folded weight leaves the scaled fp16 range.
+  const unsigned short* embd_chain_w1[2] = {nullptr, nullptr};
+  const float* embd_chain_cb[2] = {nullptr, nullptr};
+  const unsigned short* embd_chain_w2 = nullptr;
   std::vector<dcf::EncW> stem, branch;
   std::vector<const float*> pool_w;          // vid_net.pool_only: depthwise k3 weight [3][E] of every branch layer (video_net.py:107-109)
   dcf::HeadW cls1, cls2, reg;
@@ -288,6 +295,9 @@ int run_fusion(dcf_model* m, Buffers& b, float* X, int64_t ldx, int B, int T, co
 int run_fusion_drop(dcf_model* m, Buffers& b, float* X, int64_t ldx, int B, int T, const uint8_t* mask, const TextMeta* dm, int Lk,
                     float* out, int64_t ld_out, hipStream_t st);
 RefineArgs refine_args(dcf_model* m);
+bool can_chain_embd(dcf_model* m, int rows0);
+int run_embd_chain(dcf_model* m, const float* X, int64_t ldx, const uint8_t* nbr, int rows, int T, bool ln_in, const float* pe, float* Y,
+                   int64_t ldy, hipStream_t st);
 
 // ---- engine.hip
 int forward(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall& fc, hipStream_t st);

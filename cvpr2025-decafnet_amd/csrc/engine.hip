@@ -340,6 +340,14 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
 
     // ---- vid_net: VideoTransformer.forward (video_net.py:123-164)
     {
+      const bool chain_embd = can_chain_embd(m, rows0);
+      if (chain_embd) {
+        // embd_fc, both embedding convolutions, their LayerNorms and + pe * mask in one kernel: from the raw stream in b.X where
+        // fusion.ln_out came as row statistics (the kernel normalises its rows itself), from the normalised rows in R[0] otherwise.
+        // Not in place: neighbouring windows read each other's halo rows.
+        TRY(run_embd_chain(m, fused_as_stats ? b.X : b.R[0], E, b.nbr_all, rows0, T0, fused_as_stats, c.use_abs_pe ? m->pe : nullptr, b.R[3], E, st));
+        std::swap(b.X, b.R[3]);
+      } else
       if (c.model_kind != 1 && fused_as_stats) {
         // embd_fc(ln_out(x) * mask) from the raw x in b.X: padded rows come out as finite garbage instead of the bias, and every
         // consumer masks its input rows (blocks.py:98-99).  Not in place: column tiles of other workgroups still read b.X.
@@ -379,7 +387,7 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
         DCF_CHECK(Tc == Tp, "vid_net.arch[0]=%d embedding convolutions cannot divide the sequence by vid_net.stride=%d (video_net.py:53)", c.n_embd_convs, sv);
       }
       int epend = -1, epend_w = 0;                  // embedding layer whose LayerNorm + ReLU the next convolution applies on load
-      for (int i = 0; i < c.n_embd_convs && sv == 1; ++i) {
+      for (int i = 0; i < c.n_embd_convs && sv == 1 && !chain_embd; ++i) {
         GemmArgs g = gemm(b.X, E, m->embd_conv[i], nullptr, b.R[0], E, rows0, E, 3 * E);
         g.cin = E; g.nbr = b.nbr_all;
         const bool with_pe = c.use_abs_pe && i == c.n_embd_convs - 1;

@@ -649,6 +649,29 @@ int run_fusion_drop(dcf_model* m, Buffers& b, float* X, int64_t ldx, int B, int 
   return launch_ln(ln, st);
 }
 
+// From 16 384 level-0 rows on (one video of T = 16 384), in the f16x3 mode at E = 256 with two stride-1 embedding convolutions:
+// embd_fc, both convolutions, their LayerNorms and + pe * mask as ONE kernel (embd_chain.h).  Not for late fusion (embd_fc takes
+// the gated input there), the dropout forward, an armed debug tap, or a model whose folded weight left the fp16 range.
+bool can_chain_embd(dcf_model* m, int rows0) {
+  static const Setting off(nullptr, "DCF_NO_EMBD_CHAIN", 0, Setting::PRESENT);    // developer switch: the separate launches
+  static const Setting min_rows("embd_chain_min_rows", "DCF_EMBD_CHAIN_MIN_ROWS", 16384);
+  const dcf_config& c = m->cfg;
+  return !off.get() && debug_option("embd_chain", 1) != 0 && m->gemm_terms == GEMM_F16X3 && c.E == 256 && c.model_kind != 1 &&
+         vid_stride_of(c) == 1 && c.n_embd_convs == 2 && !m->drop && !m->keep_debug && m->embd_chain_w1[0] && m->embd_chain_w1[1] &&
+         m->embd_chain_w2 && rows0 >= min_rows.get();
+}
+// priced at the two convolutions and at the rows in and out once: the folded embd_fc product is work the kernel does not do
+int run_embd_chain(dcf_model* m, const float* X, int64_t ldx, const uint8_t* nbr, int rows, int T, bool ln_in, const float* pe, float* Y,
+                   int64_t ldy, hipStream_t st) {
+  const int E = m->cfg.E, v = ln_in ? 0 : 1;
+  EmbdChainArgs a{};
+  a.X = X; a.ldx = ldx; a.nbr = nbr; a.W1c = m->embd_chain_w1[v]; a.W2c = m->embd_chain_w2; a.cb = m->embd_chain_cb[v];
+  a.ln1_w = m->embd_ln_w[0]; a.ln1_b = m->embd_ln_b[0]; a.ln2_w = m->embd_ln_w[1]; a.ln2_b = m->embd_ln_b[1];
+  a.pe = pe; a.Y = Y; a.ldy = ldy; a.rows = rows; a.T = T; a.ln_in = ln_in ? 1 : 0; a.status = m->status;
+  ProfScope prof("gemm_f16x3<embd_chain>", st, 2.0 * rows * 256.0 * 768.0 * 2.0, (double)rows * E * 4.0 * 2.0);
+  return launch_embd_chain(a, st);
+}
+
 RefineArgs refine_args(dcf_model* m) {
   static const Setting stack("tcn_stack", "DCF_TCN_STACK", -1);     // developer switch: leading TCN layers per launch
   RefineArgs ra{};

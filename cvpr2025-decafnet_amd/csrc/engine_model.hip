@@ -111,6 +111,31 @@ void launch_fold_ln(const float* W, const float* bias, const float* g, const flo
   hipLaunchKernelGGL(k_fold_ln, dim3(N), dim3(64), 0, st, W, bias, g, beta, Wf, s, c, K);
 }
 
+// vid_net.embd_fc folded into the first embedding convolution (embd_chain.h), formed in fp64 and rounded once:
+//   d[j] = sum_k Wfc[j][k] beta[k] + b_fc[j];   Wf[n][tap][k] = (sum_j Wc[n][tap][j] Wfc[j][k]) g[k];   cb[tap][n] = sum_j Wc[n][tap][j] d[j]
+// Wc: the packed convolution [E][3][E]; g / beta: fusion.ln_out's affine, or nullptr (1 / 0).  One block per (n, tap), E threads.
+__global__ void k_fold_embd_d(const float* __restrict__ Wfc, const float* __restrict__ bfc, const float* __restrict__ beta, double* __restrict__ d, int E) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= E) return;
+  double a = bfc[j];
+  if (beta)
+    for (int k = 0; k < E; ++k) a += (double)Wfc[(int64_t)j * E + k] * (double)beta[k];
+  d[j] = a;
+}
+__global__ void k_fold_embd(const float* __restrict__ Wc, const float* __restrict__ Wfc, const float* __restrict__ g, const double* __restrict__ d,
+                            float* __restrict__ Wf, float* __restrict__ cb, int E) {
+  const int n = blockIdx.x / 3, tap = blockIdx.x - 3 * n, k = threadIdx.x;
+  const float* wc = Wc + ((int64_t)n * 3 + tap) * E;
+  double a = 0.;
+  for (int j = 0; j < E; ++j) a += (double)wc[j] * (double)Wfc[(int64_t)j * E + k];
+  Wf[((int64_t)n * 3 + tap) * E + k] = (float)(g ? a * (double)g[k] : a);
+  if (k == 0) {
+    double c = 0.;
+    for (int j = 0; j < E; ++j) c += (double)wc[j] * d[j];
+    cb[(int64_t)tap * E + n] = (float)c;
+  }
+}
+
 void drop_graph(dcf_model* m, bool keep_last_key) {
   if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
   if (m->graph) (void)hipGraphDestroy(m->graph);
@@ -501,6 +526,33 @@ static int finalize(dcf_model* m, hipStream_t st) {
     GET("vid_net.embd_norms." + s + ".weight", SH(E), lw); GET("vid_net.embd_norms." + s + ".bias", SH(E), lb);
     m->embd_ln_w.push_back(lw); m->embd_ln_b.push_back(lb);
   }
+  // the embedding stage as one kernel: the folded first convolution for both kinds of input rows, the second as it is
+  m->embd_chain_w1[0] = m->embd_chain_w1[1] = m->embd_chain_w2 = nullptr;
+  m->embd_chain_cb[0] = m->embd_chain_cb[1] = nullptr;
+  unsigned* embd_overflow = nullptr;
+  if (m->gemm_terms == GEMM_F16X3 && c.model_kind != 1 && vid_stride_of(c) == 1 && c.n_embd_convs == 2 && embd_chain_supports(E)) {
+    const size_t img = head_chain_image_halfs(E) * sizeof(unsigned short), wf = (size_t)E * 3 * E * sizeof(float);
+    char* buf = nullptr;                               // 3 images, 2 bias sets, the overflow word; the fp32 / fp64 intermediates
+    DCF_HIP(hipMalloc(&buf, 3 * img + 2 * 3 * E * sizeof(float) + 256 + wf + E * sizeof(double)));
+    m->owned.push_back(reinterpret_cast<float*>(buf));
+    unsigned short* imgs[3] = {reinterpret_cast<unsigned short*>(buf), reinterpret_cast<unsigned short*>(buf + img), reinterpret_cast<unsigned short*>(buf + 2 * img)};
+    float* cb = reinterpret_cast<float*>(buf + 3 * img);
+    embd_overflow = reinterpret_cast<unsigned*>(cb + 2 * 3 * E);
+    float* Wf = reinterpret_cast<float*>(buf + 3 * img + 2 * 3 * E * sizeof(float) + 256);
+    double* d = reinterpret_cast<double*>(reinterpret_cast<char*>(Wf) + wf);
+    DCF_HIP(hipMemsetAsync(embd_overflow, 0, sizeof(unsigned), st));
+    for (int v = 0; v < 2; ++v) {                      // (stream order: Wf and d are reused)
+      const float *g = v == 0 ? m->fus_out_w : nullptr, *beta = v == 0 ? m->fus_out_b : nullptr;
+      hipLaunchKernelGGL(k_fold_embd_d, dim3((E + 255) / 256), dim3(256), 0, st, m->embd_fc_w, m->embd_fc_b, beta, d, E);
+      hipLaunchKernelGGL(k_fold_embd, dim3(3 * E), dim3(E), 0, st, m->embd_conv[0], m->embd_fc_w, g, (const double*)d, Wf, cb + v * 3 * E, E);
+      DCF_HIP(hipGetLastError());
+      // its own range word: a folded weight beyond the scaled fp16 range keeps the launch path, the model's arithmetic mode stays
+      if (launch_split_chain3(Wf, imgs[v], E, st, embd_overflow)) return -1;
+      m->embd_chain_w1[v] = imgs[v]; m->embd_chain_cb[v] = cb + v * 3 * E;
+    }
+    if (launch_split_chain3(m->embd_conv[1], imgs[2], E, st, nullptr)) return -1;      // (range: the same weights passed split_weight above)
+    m->embd_chain_w2 = imgs[2];
+  }
   for (int i = 0; i < c.n_stem; ++i) {
     EncW w{};
     if (resolve_encoder(m, "vid_net.stem." + std::to_string(i), E, st, w)) return -1;
@@ -530,6 +582,11 @@ static int finalize(dcf_model* m, hipStream_t st) {
   }
   if (c.model_kind == 0 && resolve_tcn(m, "refine", L, L, st)) return -1;
   DCF_HIP(hipStreamSynchronize(st));
+  if (embd_overflow) {
+    unsigned over = 0u;
+    DCF_HIP(hipMemcpy(&over, embd_overflow, sizeof(over), hipMemcpyDeviceToHost));
+    if (over) m->embd_chain_w1[0] = m->embd_chain_w1[1] = m->embd_chain_w2 = nullptr;
+  }
   for (auto& pl : m->plans) if (pl.d_lt) (void)hipFree(pl.d_lt);
   m->plans.clear();
   free_hybrid(m);                             // reg scales live in the level tables
@@ -663,7 +720,7 @@ int dcf_model_set_dropout(dcf_model* m, float vid_proj_p, float vid_path_p, floa
 
 int dcf_debug_set_option(const char* name, int32_t value) {
   DCF_CHECK(name && *name, "dcf_debug_set_option: empty name");
-  static const char* known[] = {"dec_chain_min_rows", "enc_chain_min_rows", "enc_attn_min_rows", "fuse_scores", "tcn_frag", "gate_skip", "tcn_stack", "half_native"};
+  static const char* known[] = {"dec_chain_min_rows", "enc_chain_min_rows", "enc_attn_min_rows", "fuse_scores", "tcn_frag", "gate_skip", "tcn_stack", "half_native", "embd_chain", "embd_chain_min_rows", "gemm_uniform"};
   bool ok = false;
   for (const char* k : known) ok = ok || strcmp(k, name) == 0;
   DCF_CHECK(ok, "dcf_debug_set_option: unknown option '%s'", name);

@@ -854,10 +854,17 @@ static int launch_kslice(const GemmBatch& b, int count, int nterms, hipStream_t 
   return 0;
 }
 
+// dcf_debug_set_option("gemm_uniform", 1): no kernel choice below depends on the grid size -- 64x128 tiles wherever N allows, never
+// the k-sliced kernel (it splits K over the waves: another summation order), no LayerNorm / AdaLN fused into an epilogue that only
+// some tile shapes have, row statistics wherever the shape allows them.  Slower; for comparing forwards of different batch sizes bit for bit (a one-video and a four-video
+// forward otherwise differ by rounding wherever a small grid takes the k-sliced kernel).
+int debug_option(const char* name, int dflt);               // (engine_model.hip)
+static bool gemm_uniform() { return debug_option("gemm_uniform", 0) != 0; }
+
 // mirrors the dispatch below: true when an A_ROWS GEMM of this shape goes to the 128x256 or the 64x256 tile kernel, whose
 // waves own 64 columns = one (scale, shift) pair of 32-column fragments
 bool gemm_can_fuse_adaln(int M, int N, int K) {
-  if (N % 256 != 0 || K % SBK != 0) return false;
+  if (N % 256 != 0 || K % SBK != 0 || gemm_uniform()) return false;
   const long tiles64 = (long)((M + 63) / 64) * (N / 64);
   if (K >= 4 * SBK && tiles64 <= 512) return false;                   // k-sliced kernel (small grids)
   return M >= 65536 || (long)((M + 63) / 64) * (N / 256) >= 448;      // 128x256 / 64x256 (WANT workgroups)
@@ -867,6 +874,7 @@ bool gemm_can_fuse_adaln(int M, int N, int K) {
 // of the N % 64 == 0 tiles are)
 bool gemm_can_carry_stats(int M, int N, int K, int count, int nterms) {
   if (nterms == 0 || N % 64 != 0 || K % SBK != 0 || M <= 0) return false;
+  if (gemm_uniform()) return true;                                    // (always a tile kernel)
   const long tiles64 = (long)((M + 63) / 64) * (N / 64) * count;
   constexpr long kslice_max = 512;
   if (K >= 4 * SBK && tiles64 <= ((K >= 16 * SBK && nterms != T_F16) ? kslice_max : kslice_max / 2)) return false;
@@ -875,7 +883,7 @@ bool gemm_can_carry_stats(int M, int N, int K, int count, int nterms) {
 
 // mirrors the A_ROWS_TAP3 dispatch below (no forced tile, no fused LayerNorm)
 bool gemm_can_norm_a(int M, int N, int K, int nterms, int* stats_w) {
-  if (nterms == 0 || K % SBK != 0 || M <= 0) return false;
+  if (nterms == 0 || K % SBK != 0 || M <= 0 || gemm_uniform()) return false;
   // the 128x256 tile only.  On the three-wave 128x96 tile (reg_head trunks, N = 288) the normalisation in the A staging made
   // the consumer 1.7x slower (two GEMMs per launch: 0.82 -> 1.42 ms at 261120 rows) for 0.12 ms of LayerNorm launches saved:
   // three waves stage the 128 rows that four stage on the wide tile, and that kernel's staging is already its critical path
@@ -888,6 +896,7 @@ bool gemm_can_fuse_ln(int M, int N, int K, GemmAMode mode) {
   // The fused kernel needs a 64 x N tile, i.e. M / 64 workgroups.  Measured at T = 16384 (rocprofv3): with 256
   // workgroups (M = 16384, one per CU) conv + LN fused 64 us vs 40 + 8 us as two kernels on 64x128 tiles; with 510
   // (M = 32640, the heads) 79 vs 74 + 12.5 us.  So: only where the grid still gives two workgroups per CU.
+  if (gemm_uniform()) return false;
   constexpr long min_tiles = 448;            // (re-swept in f16x3 mode: 448 / 256 / 128 -> 1.892 / 1.973 / 1.988 ms per one-video step)
   return mode != A_CHANMAJOR && mode != A_CHANMAJOR_H && N == 256 && K % SBK == 0 && (M + 63) / 64 >= min_tiles;
 }
@@ -948,6 +957,8 @@ int launch_gemm_split(const GemmArgs* g, int count, GemmAMode mode, int nterms, 
       if (bm == 128 && bn == 256) return launch_cfg_s<1, 4, 4, 2>(b, count, mode, nterms, stream);
     }
   }
+  const bool uniform = gemm_uniform();
+  if (uniform && !p.ln_w && N % 128 == 0) return launch_cfg_s<1, 4, 2, 1>(b, count, mode, nterms, stream);
   if (p.ln_w) {                                          // fused LayerNorm: the tile must span the row
     DCF_CHECK(count == 1 && p.Y && p.ln_b && gemm_can_fuse_ln(p.M, N, p.K, mode), "launch_gemm_split: LayerNorm cannot be fused for %dx%dx%d", p.M, N, p.K);
     if (p.ln_pe) DCF_CHECK(p.ln_mask && p.ln_T >= 64, "launch_gemm_split: fused position encoding needs a mask and T >= 64");
@@ -957,7 +968,7 @@ int launch_gemm_split(const GemmArgs* g, int count, GemmAMode mode, int nterms, 
   constexpr long kslice_max = 512;
   // (8192x256x256, 512 tiles: tile kernel 14.9 us vs 18.0 k-sliced; 8192x256x1024: 40 vs 38 -> short K switches at 256 tiles)
   // (f16x3: 8192x256x1024, 512 tiles: tile kernel 22.7 us vs 30.4 k-sliced -> 256 tiles for every K)
-  if (mode == A_ROWS && N % 64 == 0 && p.K >= 4 * SBK && wgs(64, 64) <= ((p.K >= 16 * SBK && nterms != T_F16) ? kslice_max : kslice_max / 2))
+  if (!uniform && mode == A_ROWS && N % 64 == 0 && p.K >= 4 * SBK && wgs(64, 64) <= ((p.K >= 16 * SBK && nterms != T_F16) ? kslice_max : kslice_max / 2))
     return launch_kslice(b, count, nterms, stream);
   if (mode == A_CHANMAJOR || mode == A_CHANMAJOR_H) {
     DCF_CHECK(N % 128 == 0, "launch_gemm_split: channel-major A needs N %% 128 == 0");

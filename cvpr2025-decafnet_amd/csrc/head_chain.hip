@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "embd_chain.h"
 
 namespace dcf {
 
@@ -38,7 +39,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float SA = 16.f, SW = 256.f, UNSCALE = 1.f / 4096.f;     // the f16x3 scaling of gemm_bf16s.hip
-constexpr int HALO = 3, WGROWS = 128, VALID = WGROWS - 2 * HALO;   // a workgroup's window of consecutive rows, of which the inner 122 come out valid
+constexpr int WGROWS = 128;                                        // a workgroup's window of consecutive rows
+// the halo: a row per k3 layer and side.  A head (two trunk layers + output convolution) leaves the inner 122 rows valid, the
+// embedding stage (two layers, embd_chain.h) the inner 124
+template <bool EMBD>
+struct Win {
+  static constexpr int HALO = EMBD ? 2 : 3, VALID = WGROWS - 2 * HALO;
+};
 
 template <int C>
 struct Geo {
@@ -154,26 +161,37 @@ __global__ void k_split_chain_out(const float* __restrict__ Wout, int NO, unsign
 // NO = 2 is the compiled width of the output convolution; a head with one output leaves the second one's weights zero.
 // blockIdx.y picks the head: two heads of the same width on the same rows (cls_head2 and reg_head) share a grid, so the partly
 // filled last round of workgroups is paid once, not twice.
+//
+// The body serves two kernels.  Args = HeadChainArgs: a head, as described above.  Args = EmbdChainArgs (embd_chain.h): the level-0
+// embedding stage of the video backbone, the same two trunk layers with (i) an optional LayerNorm without affine on the loaded rows,
+// (ii) three bias vectors behind the first layer's taps, each under its tap's neighbour flag (vid_net.embd_fc folded into the first
+// convolution), and (iii) the rows stored with + pe * mask where a head runs its output convolution.
 struct HeadChainBatch { HeadChainArgs a[2]; };
-template <int C>
-__global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
+template <int C, class Args>
+__device__ __forceinline__ void chain_body(const Args& p) {
+  constexpr bool EMBD = std::is_same<Args, EmbdChainArgs>::value;
   constexpr int NO = 2;
-  const HeadChainArgs& p = batch.a[blockIdx.y];
+  constexpr int HALO = Win<EMBD>::HALO, VALID = Win<EMBD>::VALID;
   using G = Geo<C>;
   constexpr int KS = G::KS, KH = G::KH, NT = G::NT, STAGE = G::STAGE, PIECES = G::PIECES, NPW = G::NPW;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   float* lds_ln = reinterpret_cast<float*>(lds + 2 * STAGE);      // ln1_w, ln1_b, ln2_w, ln2_b: 4 x [C]
 #ifdef DCF_HC_VECTOR_OUT
+  static_assert(!EMBD, "DCF_HC_VECTOR_OUT is an A/B build of the heads");
   float* lds_wo = lds_ln + 4 * C;                                  // [NO][3][C]
   float* lds_x = lds_wo + NO * 3 * C;
+  float* lds_cb = nullptr;
 #else
+  float* lds_cb = lds_ln + 4 * C;                                  // (embedding stage) the first layer's per-tap bias: 3 x [C]
   // boundary rows of the waves: xch[parity][wave][0: last row's tap-0 product, 1: first row's tap-2 product][lane half][16]
-  float* lds_x = lds_ln + 4 * C;
+  float* lds_x = lds_ln + (EMBD ? 7 : 4) * C;
 #endif
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned lane16 = (unsigned)lane * 16u;
-  auto xch = [&](int par, int wave, int dir) __attribute__((always_inline)) -> float* { return lds_x + (((par * 4 + wave) * 2 + dir) * 2 + h) * 16; };
+  // (embedding stage: a third slot per wave, dir 2 = the last row's OWN left term, see lfl_x below)
+  constexpr int ND = EMBD ? 3 : 2;
+  auto xch = [&](int par, int wave, int dir) __attribute__((always_inline)) -> float* { return lds_x + (((par * 4 + wave) * ND + dir) * 2 + h) * 16; };
   const int wr = w * 32 + r;                                                       // row of the workgroup's window
   const int row = (int)blockIdx.x * VALID - HALO + wr;                           // this lane's pyramid row
   const bool inr = row >= 0 && row < p.rows;
@@ -183,8 +201,13 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   // except for rows 0 / 31 of a wave: theirs sits in the neighbouring WAVE and comes through LDS (exchange below); the window's
   // first and last row have none (halo rows)
   const float sfl = (fl & 1u) ? UNSCALE : 0.f;
-  const float lfl_in = ((fl & 2u) && r != 0) ? UNSCALE : 0.f, rfl_in = ((fl & 4u) && r != 31) ? UNSCALE : 0.f;
-  const float lfl_x = ((fl & 2u) && r == 0 && w > 0) ? UNSCALE : 0.f, rfl_x = ((fl & 4u) && r == 31 && w < 3) ? UNSCALE : 0.f;
+  // Embedding stage: a row's bits must not depend on where in a window it lies (a row of a one-video forward is the same row in an
+  // eight-video forward, at another lane).  Inside a wave the terms are added as (self + right) + left; row 31 gets its right term
+  // only with the exchange, so it parks its left term in LDS (slot dir 2) and adds it there, behind the right one.  (The heads add
+  // row 31's right term last: (self + left) + right.)
+  const bool l_late = EMBD && r == 31;
+  const float lfl_in = ((fl & 2u) && r != 0 && !l_late) ? UNSCALE : 0.f, rfl_in = ((fl & 4u) && r != 31) ? UNSCALE : 0.f;
+  const float lfl_x = ((fl & 2u) && ((r == 0 && w > 0) || l_late)) ? UNSCALE : 0.f, rfl_x = ((fl & 4u) && r == 31 && w < 3) ? UNSCALE : 0.f;
   const float lfl1 = (fl & 2u) ? 1.f : 0.f, rfl1 = (fl & 4u) ? 1.f : 0.f, sfl1 = (fl & 1u) ? 1.f : 0.f;   // (output convolution: unscaled partials)
 
   // weight stream: stage g = layer * SPL + 2 ot + hf; wave w requests pieces w, w + 4, ... (the last one twice where PIECES is
@@ -204,6 +227,7 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
 
   for (int i = tid; i < C; i += 256) {
     lds_ln[i] = p.ln1_w[i]; lds_ln[C + i] = p.ln1_b[i]; lds_ln[2 * C + i] = p.ln2_w[i]; lds_ln[3 * C + i] = p.ln2_b[i];
+    if constexpr (EMBD) { lds_cb[i] = p.cb[i]; lds_cb[C + i] = p.cb[C + i]; lds_cb[2 * C + i] = p.cb[2 * C + i]; }
   }
 #ifdef DCF_HC_VECTOR_OUT
   for (int i = tid; i < NO * 3 * C; i += 256) lds_wo[i] = i < p.NO * 3 * C ? p.Wout[i] : 0.f;
@@ -215,7 +239,46 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   constexpr int XA = (256 - 16 * NT - 96) / 8 - 1 > 0 ? (256 - 16 * NT - 96) / 8 - 1 : 0;
   // the window's rows as B operands in chain order: K step kk, lane (r, h): channels 16 kk + 4 h .. + 3 and 16 kk + 8 + 4 h .. + 3
   f16x8 xh[KS], xl[KS];
-  {
+  if constexpr (EMBD) {
+    // the whole row first: with ln_in it is normalised in registers -- (x - mean) * rstd, the mean, then the mean of squared
+    // deviations, as ln_relu below, no affine (the fold carries it) -- and split afterwards; without, mean 0 and rstd 1 leave the
+    // values as they are.  The statistics are computed either way: a branch here would keep the row alive twice.
+    const float* px = p.X + (int64_t)row_c * p.ldx + 4 * h;
+    const bool use = (fl & 1u) != 0;
+    f32x4 v[KS][2];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+      v[kk][0] = *reinterpret_cast<const f32x4*>(px + 16 * kk); v[kk][1] = *reinterpret_cast<const f32x4*>(px + 16 * kk + 8);
+      if (!use) { v[kk][0] = f32x4{0.f, 0.f, 0.f, 0.f}; v[kk][1] = v[kk][0]; }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s += v[kk][0][i] + v[kk][1][i];
+    const float mean = xor32_sum(s) * (1.0f / C);
+    float q = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float d0 = v[kk][0][i] - mean, d1 = v[kk][1][i] - mean;
+        q = __builtin_fmaf(d0, d0, q); q = __builtin_fmaf(d1, d1, q);
+      }
+    const float rstd = 1.0f / sqrtf(xor32_sum(q) * (1.0f / C) + 1e-5f);
+    const float mu = p.ln_in ? mean : 0.f, rs = p.ln_in ? rstd : 1.f;
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+      unsigned hi[4], lo[4];
+      split2_f16((v[kk][0].x - mu) * rs, (v[kk][0].y - mu) * rs, SA, hi[0], lo[0]);
+      split2_f16((v[kk][0].z - mu) * rs, (v[kk][0].w - mu) * rs, SA, hi[1], lo[1]);
+      split2_f16((v[kk][1].x - mu) * rs, (v[kk][1].y - mu) * rs, SA, hi[2], lo[2]);
+      split2_f16((v[kk][1].z - mu) * rs, (v[kk][1].w - mu) * rs, SA, hi[3], lo[3]);
+      xh[kk] = __builtin_bit_cast(f16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
+      xl[kk] = __builtin_bit_cast(f16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
+      if (kk < XA) { asm volatile("" : "+a"(xh[kk])); asm volatile("" : "+a"(xl[kk])); }
+    }
+  } else {
     const float* px = p.X + (int64_t)row_c * p.ldx + 4 * h;
     const bool use = (fl & 1u) != 0;                       // MaskedConv1D multiplies its input by the mask
 #pragma unroll
@@ -245,7 +308,7 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   // after the next barrier: rows 0 / 31 of the wave take the neighbouring waves' share of tile OT
   auto fixup = [&](auto ot_) __attribute__((always_inline)) {
     constexpr int OT = decltype(ot_)::value;
-    const float* pl_ = xch(OT & 1, w > 0 ? w - 1 : 0, 0);
+    const float* pl_ = l_late ? xch(OT & 1, w, 2) : xch(OT & 1, w > 0 ? w - 1 : 0, 0);
     const float* pr_ = xch(OT & 1, w < 3 ? w + 1 : 3, 1);
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
@@ -276,8 +339,14 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
     const unsigned short* nimg = LAST ? p.W2c : (layer ? p.W2c : p.W1c);
     const bool has_next = !LAST || layer == 0;             // wave uniform
 #else
-    const unsigned short* nimg = LAST ? (layer ? p.Woc : p.W2c) : (layer ? p.W2c : p.W1c);
-    const bool has_next = true;
+    const unsigned short* nimg;
+    bool has_next = true;
+    if constexpr (EMBD) {                                  // (no output convolution: the second layer's last stage requests nothing)
+      nimg = layer ? p.W2c : (LAST ? p.W2c : p.W1c);
+      has_next = !LAST || layer == 0;                      // wave uniform
+    } else {
+      nimg = LAST ? (layer ? p.Woc : p.W2c) : (layer ? p.W2c : p.W1c);
+    }
 #endif
     const int nsl = LAST ? 0 : 2 * OT + HF + 1;
     f32x16 (&Z)[3] = Z2[OT & 1];
@@ -343,6 +412,7 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
           }
           if (k == 8) {
             if (r == 31) *reinterpret_cast<f32x4*>(xch(PT & 1, w, 0) + 4 * g4) = f32x4{t0[0], t0[1], t0[2], t0[3]};
+            if constexpr (EMBD) { if (r == 31) *reinterpret_cast<f32x4*>(xch(PT & 1, w, 2) + 4 * g4) = f32x4{p0[0], p0[1], p0[2], p0[3]}; }
             if (r == 0) *reinterpret_cast<f32x4*>(xch(PT & 1, w, 1) + 4 * g4) = f32x4{t2[0], t2[1], t2[2], t2[3]};
           }
           const int tn = (k + 1) % 3, pn = (k + 1) / 3 == 0 ? 1 : 0;
@@ -385,6 +455,7 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
         for (int i = 0; i < 4; ++i) { p0[i] = from_prev(bz0[g4][i]); n2[i] = from_next(bz2[g4][i]); }
 #pragma unroll
         for (int i = 0; i < 4; ++i) Y[OT][4 * g4 + i] = __builtin_fmaf(p0[i], lfl_in, __builtin_fmaf(n2[i], rfl_in, Z[1][4 * g4 + i] * sfl));
+        if constexpr (EMBD) { if (r == 31) *reinterpret_cast<f32x4*>(xch(OT & 1, w, 2) + 4 * g4) = f32x4{p0[0], p0[1], p0[2], p0[3]}; }
       }
       if (r == 31) {                                         // the next wave's first row adds these (still scaled by 2^12) ...
         float* o = xch(OT & 1, w, 0);
@@ -446,11 +517,29 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
 #endif
     __syncthreads();
     fixup(std::integral_constant<int, NT - 1>{});
+    if constexpr (EMBD) {
+      // embd_fc's bias seen through the three taps of the first convolution: c_t where the tap's row is usable (unscaled values,
+      // like the taps under their flags)
+      if (layer == 0) {
+#pragma unroll
+        for (int ot = 0; ot < NT; ++ot)
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4) {
+            const float* pc = lds_cb + 32 * ot + 8 * g4 + 4 * h;
+            const f32x4 c0 = *reinterpret_cast<const f32x4*>(pc), c1 = *reinterpret_cast<const f32x4*>(pc + C), c2 = *reinterpret_cast<const f32x4*>(pc + 2 * C);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              Y[ot][4 * g4 + i] += __builtin_fmaf(c0[i], lfl1, __builtin_fmaf(c2[i], rfl1, c1[i] * sfl1));
+          }
+      }
+    }
     ln_relu(lds_ln + 2 * C * layer, lds_ln + 2 * C * layer + C);
+    bool split = true;
 #ifdef DCF_HC_VECTOR_OUT
-    if (layer == 0)
+    split = layer == 0;
 #endif
-    {                                                      // the next product's B operand: Y[ot][8 q .. 8 q + 7] = K step 2 ot + q
+    if constexpr (EMBD) split = layer == 0;                // (the second layer's rows go to memory as they are)
+    if (split) {                                                  // the next product's B operand: Y[ot][8 q .. 8 q + 7] = K step 2 ot + q
 #pragma unroll
       for (int ot = 0; ot < NT; ++ot)
 #pragma unroll
@@ -466,6 +555,26 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
   }
 
   STAMP(4);
+  if constexpr (EMBD) {
+    // the inner rows as they lie in the accumulators: 16 bytes per lane and register group, + pe[t] * mask (video_net.py:149-151).
+    // Position-encoding values are requested whether or not there is an encoding (from the LayerNorm parameters then, and dropped).
+    const bool with_pe = p.pe != nullptr;                    // uniform
+    const int t = with_pe ? row_c % p.T : 0;
+    const float* ppe = (with_pe ? p.pe + (int64_t)t * C : p.ln2_w) + 4 * h;
+    float* py = p.Y + (int64_t)row_c * p.ldy + 4 * h;
+    const bool keep = wr >= HALO && wr < HALO + VALID && inr;
+#pragma unroll
+    for (int ot = 0; ot < NT; ++ot)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        f32x4 e = *reinterpret_cast<const f32x4*>(ppe + 32 * ot + 8 * g4);
+        if (!with_pe) e = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = __builtin_fmaf(e[i], sfl1, Y[ot][4 * g4 + i]);
+        if (keep) *reinterpret_cast<f32x4*>(py + 32 * ot + 8 * g4) = o;
+      }
+  } else {
 #ifdef DCF_HC_VECTOR_OUT
   // output convolution (head.py:60, :99): per-lane tap partials over the lane's channels, the two lane halves added, the taps
   // put together across rows as above
@@ -554,6 +663,7 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
       if (o < p.NO) p.out[dst * p.NO + o] = y;
     }
   }
+  }   // (!EMBD)
   if (bad && p.status) atomicOr(p.status, 1u);
 #ifdef DCF_HC_STAMP
   STAMP(6);
@@ -564,6 +674,16 @@ __global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
     for (int i = 0; i < 8; ++i) dcf_hc_stamps[i] = acc_[i];
 #endif
 }
+
+template <int C>
+__global__ __launch_bounds__(256, 1) void k_head_chain(HeadChainBatch batch) {
+  chain_body<C>(batch.a[blockIdx.y]);
+}
+#ifndef DCF_HC_VECTOR_OUT
+__global__ __launch_bounds__(256, 1) void k_embd_chain(EmbdChainArgs a) {
+  chain_body<256>(a);
+}
+#endif
 
 #ifdef DCF_HC_STAMP
 }  // namespace dcf
@@ -609,7 +729,7 @@ static int launch_hc(const HeadChainArgs* a, int count, hipStream_t stream) {
   if (raise_lds_limit<&k_head_chain<C>>(bytes)) return -1;
   HeadChainBatch b{};
   for (int i = 0; i < count; ++i) b.a[i] = a[i];
-  const unsigned grid = (unsigned)((a[0].rows + VALID - 1) / VALID);
+  const unsigned grid = (unsigned)((a[0].rows + Win<false>::VALID - 1) / Win<false>::VALID);
   hipLaunchKernelGGL((k_head_chain<C>), dim3(grid, (unsigned)count), dim3(256), bytes, stream, b);
   DCF_HIP(hipGetLastError());
   return 0;
@@ -626,6 +746,28 @@ int launch_head_chain(const HeadChainArgs* a, int count, int C, hipStream_t stre
     DCF_CHECK(a[i].Woc && (reinterpret_cast<uintptr_t>(a[i].Woc) & 15) == 0, "launch_head_chain: no image of the output convolution, or not 16-byte aligned");
   }
   return C == 256 ? launch_hc<256>(a, count, stream) : launch_hc<288>(a, count, stream);
+}
+
+bool embd_chain_supports(int C) { return C == 256; }
+
+int launch_embd_chain(const EmbdChainArgs& a, hipStream_t stream) {
+#ifdef DCF_HC_VECTOR_OUT
+  DCF_CHECK(false, "launch_embd_chain: not in a DCF_HC_VECTOR_OUT build");
+#else
+  constexpr int C = 256;
+  DCF_CHECK(a.rows > 0 && a.T > 0 && a.X && a.nbr && a.W1c && a.W2c && a.cb && a.ln1_w && a.ln1_b && a.ln2_w && a.ln2_b && a.Y, "launch_embd_chain: null argument");
+  DCF_CHECK(a.X != a.Y, "launch_embd_chain: not in place (neighbouring windows read each other's halo rows)");
+  DCF_CHECK((reinterpret_cast<uintptr_t>(a.X) & 15) == 0 && a.ldx % 4 == 0 && a.ldx >= C && (reinterpret_cast<uintptr_t>(a.Y) & 15) == 0 && a.ldy % 4 == 0 &&
+                a.ldy >= C && (reinterpret_cast<uintptr_t>(a.W1c) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.W2c) & 15) == 0 &&
+                (reinterpret_cast<uintptr_t>(a.pe) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.ln2_w) & 15) == 0,
+            "launch_embd_chain: X / Y / pe / ln2_w / weight images must be 16-byte aligned, the row pitches multiples of 4 and >= %d", C);
+  constexpr int bytes = 2 * Geo<C>::STAGE + (7 * C + 2 * 4 * 3 * 2 * 16) * (int)sizeof(float);
+  if (raise_lds_limit<&k_embd_chain>(bytes)) return -1;
+  const unsigned grid = (unsigned)((a.rows + Win<true>::VALID - 1) / Win<true>::VALID);
+  hipLaunchKernelGGL(k_embd_chain, dim3(grid), dim3(256), bytes, stream, a);
+  DCF_HIP(hipGetLastError());
+  return 0;
+#endif
 }
 
 }  // namespace dcf

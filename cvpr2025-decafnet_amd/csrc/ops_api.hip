@@ -1,6 +1,7 @@
 // Post-processing and single-operator entry points of the C ABI: what the tests and autograd.py call outside a forward.
 #include <algorithm>
 
+#include "../../include/decafnet_hip_embd.h"
 #include "engine.h"
 
 namespace dcf {
@@ -465,6 +466,70 @@ int dcf_op_tcn(dcf_model* m, const char* prefix, const float* x, const uint8_t* 
   rc = scratch_end(m, st, rc);
   if (buf) (void)hipFree(buf);
   return rc;
+}
+
+// ---- the embedding-stage extension (include/decafnet_hip_embd.h): on a finalized model's own parameters
+int dcf_embd_ext_version(void) { return DCF_EMBD_EXT_VERSION; }
+
+static int embd_op_check(const dcf_model* m, const char* what, const float* X, int64_t ldx, const uint8_t* mask, int B, int T, const float* Y, int64_t ldy) {
+  DCF_CHECK(m && X && mask && Y && B >= 1 && T >= 1 && (int64_t)B * T < (1ll << 31), "%s: null argument or bad B / T", what);
+  DCF_CHECK(m->finalized, "%s: the model is not finalized", what);
+  const dcf_config& c = m->cfg;
+  DCF_CHECK(c.model_kind != 1 && dcf::vid_stride_of(c) == 1 && c.n_embd_convs == 2 && c.E == 256 && m->gemm_terms == dcf::GEMM_F16X3,
+            "%s: needs an early-fusion model with E = 256, vid_net.stride 1 and two embedding convolutions in the f16x3 mode", what);
+  DCF_CHECK(X != Y && ldx >= c.E && ldy >= c.E && ldx % 4 == 0 && ldy % 4 == 0, "%s: X and Y must differ, pitches multiples of 4 and >= E", what);
+  return 0;
+}
+
+int dcf_op_embd_chain(dcf_model* m, const float* X, int64_t ldx, const uint8_t* mask, int32_t B, int32_t T, int32_t ln_in,
+                      const float* pe, float* Y, int64_t ldy, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (embd_op_check(m, "dcf_op_embd_chain", X, ldx, mask, B, T, Y, ldy)) return -1;
+  DCF_CHECK(m->embd_chain_w1[0] && m->embd_chain_w1[1] && m->embd_chain_w2,
+            "dcf_op_embd_chain: the model has no images of the folded embedding stage (a folded weight left the scaled fp16 range)");
+  const int rows = B * T;
+  dcf::StreamScratch sc(st);
+  uint8_t* nbr = nullptr;
+  if (sc.take(&nbr, (size_t)rows)) return -1;
+  int rc = dcf::launch_rowflags(mask, nbr, T, rows, st);
+  if (rc == 0) rc = dcf::run_embd_chain(m, X, ldx, nbr, rows, T, ln_in != 0, pe, Y, ldy, st);
+  return sc.end(rc);
+}
+
+int dcf_op_embd_launches(dcf_model* m, const float* X, int64_t ldx, const uint8_t* mask, int32_t B, int32_t T, int32_t ln_in,
+                         const float* pe, float* Y, int64_t ldy, void* stream) {
+  using namespace dcf;
+  hipStream_t st = (hipStream_t)stream;
+  if (embd_op_check(m, "dcf_op_embd_launches", X, ldx, mask, B, T, Y, ldy)) return -1;
+  const int rows = B * T, E = m->cfg.E;
+  StreamScratch sc(st);
+  uint8_t* nbr = nullptr;
+  float *t0 = nullptr, *t1 = nullptr;
+  if (sc.take(&nbr, (size_t)rows) || sc.take(&t0, (size_t)rows * E) || sc.take(&t1, (size_t)rows * E)) return -1;
+  int rc = launch_rowflags(mask, nbr, T, rows, st);
+  const float* xin = X;
+  int64_t ldin = ldx;
+  if (rc == 0 && ln_in) {
+    LnArgs ln{}; ln.X = X; ln.ldx = ldx; ln.Y = t0; ln.ldy = E; ln.w = m->fus_out_w; ln.b = m->fus_out_b; ln.rows = rows; ln.C = E;
+    rc = launch_ln(ln, st);
+    xin = t0; ldin = E;
+  }
+  if (rc == 0) {
+    GemmArgs ge = gemm(xin, ldin, m->embd_fc_w, m->embd_fc_b, t1, E, rows, E, E);
+    ge.flags = G_AMASK; ge.rowmask = mask;
+    rc = run_gemm(m, &ge, 1, A_ROWS, st);
+  }
+  for (int i = 0; i < 2 && rc == 0; ++i) {
+    GemmArgs g = gemm(t1, E, m->embd_conv[i], nullptr, t0, E, rows, E, 3 * E);
+    g.cin = E; g.nbr = nbr;
+    rc = run_gemm(m, &g, 1, A_ROWS_TAP3, st);
+    if (rc) break;
+    LnArgs ln{}; ln.X = t0; ln.ldx = E; ln.Y = i == 1 ? Y : t1; ln.ldy = i == 1 ? ldy : E; ln.w = m->embd_ln_w[i]; ln.b = m->embd_ln_b[i];
+    ln.rows = rows; ln.C = E; ln.relu = 1;
+    if (i == 1 && pe) { ln.pe = pe; ln.mask = mask; ln.T = T; }
+    rc = launch_ln(ln, st);
+  }
+  return sc.end(rc);
 }
 
 }  // extern "C"
