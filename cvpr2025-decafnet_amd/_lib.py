@@ -1,10 +1,11 @@
-"""ctypes binding of libdecafnet_hip.so (the C ABI declared in include/decafnet_hip.h).
+"""ctypes binding of libdecafnet_hip.so (the C ABI declared in include/decafnet_hip.h and the extension headers beside it).
 
 The product path has no CPU fallback: if the shared object is missing or cannot be loaded,
 ``lib()`` raises and every operator fails loudly.
 """
 import ctypes
 import os
+from collections import namedtuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DCF_LIB_PATH: developer switch for A/B runs of two builds inside one GPU call (tools/); the product path is the in-tree build
@@ -38,7 +39,8 @@ OPTIM_NO_GRAD = 1             # DCF_OPTIM_NO_GRAD
 OPTIM_MODES = {'adamw': 0, 'adam': 1}
 
 
-# name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
+# Every table below maps name -> (restype, argtypes) and belongs to one header of include/; EXTENSIONS, after the last of them, is
+# the registry that says which.  The base table: ABI 12 (include/decafnet_hip.h).
 SIGNATURES = {
     'dcf_last_error': (ctypes.c_char_p, []),
     'dcf_abi_version': (i32, []),
@@ -136,8 +138,7 @@ SIGNATURES = {
     'dcf_optim_adam_step': (i32, [vp, c_i32p, i32, i64, vp, i32, c_f32p, i32, f32, vp]),
 }
 
-# the training extension (include/decafnet_hip_train.h, dcf_train_ext_version): same shared object, a table of its own -- ABI 12 and
-# SIGNATURES above are frozen (tests/test_step_grad_drop_cpu.py checks this table against its header)
+# the training extension: dropout and drop-path operators
 _DROP = [i32, i32, i32, i32, i64, i32, f32]                 # B, T, C, b0, seed, site, p
 TRAIN_SIGNATURES = {
     'dcf_train_ext_version': (i32, []),
@@ -149,24 +150,21 @@ TRAIN_SIGNATURES = {
 }
 
 
-# the data-parallel extension (include/decafnet_hip_dist.h, dcf_dist_ext_version): same shared object, a third table -- the two above
-# are frozen (tests/test_grad_bucket_cpu.py checks this table against its header)
+# the data-parallel extension
 DIST_SIGNATURES = {
     'dcf_dist_ext_version': (i32, []),
     'dcf_dist_pack_grads': (i32, [vp, c_i32p, i32, i64, f32, vp]),
 }
 
 
-# the attention-gradient extension (include/decafnet_hip_attn.h, dcf_attn_ext_version): same shared object, a fourth table -- the
-# three above are frozen (tests/test_global_attn_grad_cpu.py checks this table against its header)
+# the attention-gradient extension
 ATTN_SIGNATURES = {
     'dcf_attn_ext_version': (i32, []),
     'dcf_op_global_attn_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, vp]),
 }
 
 
-# the training-front-end extension (include/decafnet_hip_front.h, dcf_front_ext_version): same shared object, a fifth table -- the
-# four above are frozen (tests/test_front_grad_cpu.py checks this table against its header).  ``nq`` is a HOST array of int32.
+# the training-front-end extension.  ``nq`` is a HOST array of int32.
 FRONT_NO_SKIP = 1             # DCF_FRONT_NO_SKIP
 FRONT_SIGNATURES = {
     'dcf_front_ext_version': (i32, []),
@@ -175,8 +173,7 @@ FRONT_SIGNATURES = {
 }
 
 
-# the step-guard extension (include/decafnet_hip_guard.h, dcf_guard_ext_version): same shared object, a sixth table -- the five
-# above are frozen (tests/test_guard_cpu.py checks this table against its header)
+# the step-guard extension
 GUARD_APPLY, GUARD_SKIP = 0, 1    # DCF_GUARD_APPLY, DCF_GUARD_SKIP
 
 
@@ -195,9 +192,7 @@ GUARD_SIGNATURES = {
 }
 
 
-# the step-count extension (include/decafnet_hip_clock.h, dcf_clock_ext_version): same shared object, a seventh table -- the six
-# above are frozen (tests/test_clock_cpu.py checks this table against its header).  ``groups``, ``bc_tables`` and ``bc_len`` are HOST
-# arrays; ``steps`` is int64 in device memory.
+# the step-count extension.  ``groups``, ``bc_tables`` and ``bc_len`` are HOST arrays; ``steps`` is int64 in device memory.
 CLOCK_MAX_TABLE = 1 << 22     # the longest bias-correction table optim.AdamW(device_count=True) builds
 CLOCK_SIGNATURES = {
     'dcf_clock_ext_version': (i32, []),
@@ -205,9 +200,8 @@ CLOCK_SIGNATURES = {
 }
 
 
-# the half-feature extension (include/decafnet_hip_half.h, dcf_half_ext_version): same shared object, an eighth table -- the seven
-# above are frozen (tests/test_half_features_cpu.py checks this table against its header).  A half operand is the device address of
-# IEEE binary16 values (``const uint16_t*``); ``text`` / ``text_mask`` / ``text_len`` / ``nq_per_video`` are HOST arrays as in SIGNATURES.
+# the half-feature extension.  A half operand is the device address of IEEE binary16 values (``const uint16_t*``); ``text`` /
+# ``text_mask`` / ``text_len`` / ``nq_per_video`` are HOST arrays as in SIGNATURES.
 c_f16p = ctypes.c_void_p
 HALF_SIGNATURES = {
     'dcf_half_ext_version': (i32, []),
@@ -222,9 +216,8 @@ HALF_SIGNATURES = {
 }
 
 
-# the half-feature training-front-end extension (include/decafnet_hip_front_half.h, dcf_front_half_ext_version): same shared object, a
-# ninth table -- the eight above are frozen (tests/test_front_half_cpu.py checks this table against its header).  The operators of
-# FRONT_SIGNATURES with ``vid`` / ``shallow`` the device address of IEEE binary16 values; ``nq`` is a HOST array of int32.
+# the half-feature training-front-end extension.  The operators of FRONT_SIGNATURES with ``vid`` / ``shallow`` the device address of
+# IEEE binary16 values; ``nq`` is a HOST array of int32.
 FRONT_HALF_SIGNATURES = {
     'dcf_front_half_ext_version': (i32, []),
     'dcf_op_vidmap_shared_h': (i32, [c_f16p, c_f16p, c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_i32p, c_f32p, i32, i32, i32, i32, i32, vp]),
@@ -232,13 +225,37 @@ FRONT_HALF_SIGNATURES = {
 }
 
 
-# the embedding-stage extension (include/decafnet_hip_embd.h, dcf_embd_ext_version): same shared object, a tenth table -- the nine
-# above are frozen (tests/test_embd_chain_cpu.py checks this table against its header).  ``model`` is a finalized dcf_model.
+# the embedding-stage extension.  ``model`` is a finalized dcf_model.
 EMBD_SIGNATURES = {
     'dcf_embd_ext_version': (i32, []),
     'dcf_op_embd_chain': (i32, [vp, c_f32p, i64, c_u8p, i32, i32, i32, c_f32p, c_f32p, i64, vp]),
     'dcf_op_embd_launches': (i32, [vp, c_f32p, i64, c_u8p, i32, i32, i32, c_f32p, c_f32p, i64, vp]),
 }
+
+
+# The registry: one record per header of include/, all of them exports of the same shared object.  A released table and its header
+# are never edited; a new operator family gets a header and a table of its own, a version function that returns 1, and one record at
+# the end of this tuple.  lib() binds what the records list, tests/test_abi_headers.py checks every record against its header and the
+# built library, and tests/borders.py maps every key to its poisoned-border cases.
+Extension = namedtuple('Extension', 'key header version_symbol version version_macro includes table')
+
+
+def _ext(key, table, includes=('decafnet_hip.h',)):
+    return Extension(key, f'decafnet_hip_{key}.h', f'dcf_{key}_ext_version', 1, f'DCF_{key.upper()}_EXT_VERSION', includes, table)
+
+
+EXTENSIONS = (
+    Extension('base', 'decafnet_hip.h', 'dcf_abi_version', 12, None, (), SIGNATURES),
+    _ext('train', TRAIN_SIGNATURES),
+    _ext('dist', DIST_SIGNATURES),
+    _ext('attn', ATTN_SIGNATURES),
+    _ext('front', FRONT_SIGNATURES),
+    _ext('guard', GUARD_SIGNATURES),
+    _ext('clock', CLOCK_SIGNATURES, includes=('decafnet_hip.h', 'decafnet_hip_guard.h')),
+    _ext('half', HALF_SIGNATURES),
+    _ext('front_half', FRONT_HALF_SIGNATURES),
+    _ext('embd', EMBD_SIGNATURES),
+)
 
 
 def lib():
@@ -251,12 +268,15 @@ def lib():
             raise RuntimeError(f'{SO_PATH} is missing: build it with __graft_entry__.build() '
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(DIST_SIGNATURES.items()) + \
-                list(ATTN_SIGNATURES.items()) + list(FRONT_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(CLOCK_SIGNATURES.items()) + \
-                list(HALF_SIGNATURES.items()) + list(FRONT_HALF_SIGNATURES.items()) + list(EMBD_SIGNATURES.items()):
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
+        bound = set()
+        for ext in EXTENSIONS:
+            for name, (res, args) in ext.table.items():
+                if name in bound:
+                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS')
+                bound.add(name)
+                fn = getattr(h, name)
+                fn.restype = res
+                fn.argtypes = args
         _LIB = h
     return _LIB
 

@@ -1,73 +1,27 @@
-"""CPU checks that go with the step-count extension (include/decafnet_hip_clock.h): the header equals ``_lib.CLOCK_SIGNATURES`` and
-shares no name with the six frozen tables and headers; every declared symbol is exported; the host's bias-correction tables
+"""CPU checks that go with the step-count extension (include/decafnet_hip_clock.h; its header and table: tests/test_abi_headers.py): the
+names of ``_lib.CLOCK_SIGNATURES`` and the parameter order of dcf_clock_adam_step; the host's bias-correction tables
 (``optim.bias_correction_table``) entry by entry against the pair the host path passes by value (tests/clock_ref.py); and what
 ``optim.AdamW`` and ``train.TrainStep`` make of ``device_count`` without a GPU.  No GPU."""
 import copy
-import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, load_pkg
+import abi_headers as H
+from conftest import load_pkg
 import clock_ref as C
 
-HEADER = os.path.join(ROOT, 'include', 'decafnet_hip_clock.h')
-FROZEN = {'decafnet_hip.h': 'SIGNATURES', 'decafnet_hip_train.h': 'TRAIN_SIGNATURES', 'decafnet_hip_dist.h': 'DIST_SIGNATURES',
-          'decafnet_hip_attn.h': 'ATTN_SIGNATURES', 'decafnet_hip_front.h': 'FRONT_SIGNATURES', 'decafnet_hip_guard.h': 'GUARD_SIGNATURES'}
 NAMES = ['dcf_clock_adam_step', 'dcf_clock_ext_version']
-CTYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}
-
-
-def header_source():
-    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-
-
-def declared_symbols():
-    return sorted(set(re.findall(r'\b(dcf_[a-z0-9_]+)\s*\(', header_source())))
-
-
 # ---------------------------------------------------------------------------------------------- the ABI
-def test_clock_header_equals_the_table():
+def test_clock_table_names_parameter_order_and_source():
     pkg = load_pkg()
-    table = pkg._lib.CLOCK_SIGNATURES
-    assert sorted(table) == declared_symbols() == NAMES
-    src = header_source()
-    assert '#include "decafnet_hip.h"' in src and '#include "decafnet_hip_guard.h"' in src and '#define DCF_CLOCK_EXT_VERSION 1' in src
-    for name, (res, args) in table.items():
-        m = re.search(r'\bint\s+' + name + r'\s*\((.*?)\)\s*;', src, flags=re.S)
-        assert m and res is ctypes.c_int32, name
-        params = [p for p in m.group(1).split(',') if p.strip() and p.strip() != 'void']
-        assert len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):                    # integer widths and pointers, position by position
-            want = ctypes.c_void_p if '*' in p else CTYPES[p.split()[-2]]
-            assert a is want, (name, p.strip(), a)
-    order = [p.split()[-1].lstrip('*') for p in re.search(r'dcf_clock_adam_step\s*\((.*?)\)', src, flags=re.S).group(1).split(',')]
-    assert order == ['table', 'chunk_map', 'n_tensors', 'n_chunks', 'groups', 'n_groups', 'bc_tables', 'bc_len', 'steps', 'coef',
-                     'guard_state', 'with_ema', 'ema_beta', 'stream']
-
-
-def test_the_frozen_tables_and_headers_hold_no_name_of_the_new_table():
-    pkg = load_pkg()
-    for header, table in FROZEN.items():
-        frozen = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-        for name in pkg._lib.CLOCK_SIGNATURES:
-            assert name not in getattr(pkg._lib, table), (table, name)
-            assert not re.search(r'\b' + name + r'\s*\(', frozen), (header, name)
-
-
-def test_clock_symbols_are_exported_and_versions():
-    pkg = load_pkg()
+    assert sorted(pkg._lib.CLOCK_SIGNATURES) == NAMES
+    assert H.param_names('decafnet_hip_clock.h', 'dcf_clock_adam_step') == [
+        'table', 'chunk_map', 'n_tensors', 'n_chunks', 'groups', 'n_groups', 'bc_tables', 'bc_len', 'steps', 'coef', 'guard_state', 'with_ema',
+        'ema_beta', 'stream']
     assert 'optim_clock.hip' in pkg.build.SOURCES
-    h = ctypes.CDLL(pkg.build.build())
-    for s in declared_symbols():
-        assert hasattr(h, s), f'{s} declared in include/decafnet_hip_clock.h but not exported'
-    assert h.dcf_clock_ext_version() == 1
-    assert h.dcf_guard_ext_version() == 1 and h.dcf_front_ext_version() == 1 and h.dcf_attn_ext_version() == 1
-    assert h.dcf_dist_ext_version() == 1 and h.dcf_train_ext_version() == 1 and h.dcf_abi_version() == 12
 
 
 # ---------------------------------------------------------------------------------------------- the table builder

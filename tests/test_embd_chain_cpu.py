@@ -1,23 +1,17 @@
 """CPU checks that go with the embedding-stage extension (include/decafnet_hip_embd.h, csrc/embd_chain.h): the fold of vid_net.embd_fc
 (and of fusion.ln_out's affine) into the first embedding convolution is exact to fp64 rounding against the composition the reference
-writes, on ragged masks and at the first and last valid row of every sequence; the header equals ``_lib.EMBD_SIGNATURES`` and shares
-no name with the nine older tables and headers; every declared symbol is exported.  No GPU."""
+writes, on ragged masks and at the first and last valid row of every sequence; the names of ``_lib.EMBD_SIGNATURES`` and the
+parameter order of its two operators (its header and table: tests/test_abi_headers.py).  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT, load_pkg
+import abi_headers as H
+from conftest import load_pkg
 import embd_chain_ref as ER
 
-OLDER = {'decafnet_hip.h': 'SIGNATURES', 'decafnet_hip_train.h': 'TRAIN_SIGNATURES', 'decafnet_hip_dist.h': 'DIST_SIGNATURES',
-         'decafnet_hip_attn.h': 'ATTN_SIGNATURES', 'decafnet_hip_front.h': 'FRONT_SIGNATURES', 'decafnet_hip_guard.h': 'GUARD_SIGNATURES',
-         'decafnet_hip_clock.h': 'CLOCK_SIGNATURES', 'decafnet_hip_half.h': 'HALF_SIGNATURES',
-         'decafnet_hip_front_half.h': 'FRONT_HALF_SIGNATURES'}
 NAMES = ['dcf_embd_ext_version', 'dcf_op_embd_chain', 'dcf_op_embd_launches']
-CTYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}
 
 
 def random_params(E, seed):
@@ -82,53 +76,13 @@ def test_the_gated_bias_matters_at_sequence_edges_and_holes():
 
 
 # ---------------------------------------------------------------------------------------------- the ABI
-def source_of(header):
-    return re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-
-
-def declared_symbols():
-    return sorted(set(re.findall(r'\b(dcf_[a-z0-9_]+)\s*\(', source_of('decafnet_hip_embd.h'))))
-
-
-def params_of(name):
-    m = re.search(r'\bint\s+' + name + r'\s*\((.*?)\)\s*;', source_of('decafnet_hip_embd.h'), flags=re.S)
-    assert m, name
-    return [' '.join(q.split()) for q in m.group(1).split(',') if q.strip() and q.strip() != 'void']
-
-
-def test_embd_header_equals_the_table():
-    pkg = load_pkg()
-    table = pkg._lib.EMBD_SIGNATURES
-    assert sorted(table) == declared_symbols() == NAMES
-    src = source_of('decafnet_hip_embd.h')
-    assert '#include "decafnet_hip.h"' in src and '#define DCF_EMBD_EXT_VERSION 1' in src
-    for name, (res, args) in table.items():
-        params = params_of(name)
-        assert res is ctypes.c_int32 and len(params) == len(args), (name, len(params), len(args))
-        for q, a in zip(params, args):                    # integer widths and pointers, position by position
-            assert a is (ctypes.c_void_p if '*' in q else CTYPES[q.split()[-2]]), (name, q, a)
+def test_embd_table_names_and_parameter_order():
+    table = load_pkg()._lib.EMBD_SIGNATURES
+    assert sorted(table) == NAMES
     order = ['model', 'X', 'ldx', 'mask', 'B', 'T', 'ln_in', 'pe', 'Y', 'ldy', 'stream']
     for name in NAMES[1:]:
-        assert [q.split()[-1].lstrip('*') for q in params_of(name)] == order, name
+        assert H.param_names('decafnet_hip_embd.h', name) == order, name
     assert table['dcf_op_embd_chain'] == table['dcf_op_embd_launches']
-
-
-def test_the_older_tables_and_headers_hold_no_name_of_the_new_table():
-    pkg = load_pkg()
-    for header, table in OLDER.items():
-        older = source_of(header)
-        for name in pkg._lib.EMBD_SIGNATURES:
-            assert name not in getattr(pkg._lib, table), (table, name)
-            assert not re.search(r'\b' + name + r'\s*\(', older), (header, name)
-
-
-def test_embd_symbols_are_exported_and_versions():
-    pkg = load_pkg()
-    h = ctypes.CDLL(pkg.build.build())
-    for s in declared_symbols():
-        assert hasattr(h, s), f'{s} declared in include/decafnet_hip_embd.h but not exported'
-    assert h.dcf_embd_ext_version() == 1
-    assert h.dcf_front_half_ext_version() == 1 and h.dcf_abi_version() == 12
 
 
 def test_the_operators_refuse_a_null_model_before_a_launch():

@@ -1,69 +1,28 @@
-"""CPU checks that go with the training-front-end extension (include/decafnet_hip_front.h): the header equals ``_lib.FRONT_SIGNATURES``
-and shares no name with the four frozen tables and headers; the fp64 restatement of vid_map on shared products
+"""CPU checks that go with the training-front-end extension (include/decafnet_hip_front.h; its header and table:
+tests/test_abi_headers.py): the names of ``_lib.FRONT_SIGNATURES`` and the flag the header defines; the fp64 restatement of vid_map on shared products
 (tests/front_grad_ref.py) equals the dense formula and the reference's own fp64 yardstick on the fixtures
 (tests/golden/front_grad_<case>.npz) and central finite differences; the fixtures are what their generator says they are; and
 ``train.training_forward`` admits and refuses what its docstring says.  No GPU."""
-import ctypes
 import os
-import re
 
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT, load_pkg
+import abi_headers as H
+from conftest import GOLDEN, load_pkg
 import front_grad_ref as R
 
-HEADER = os.path.join(ROOT, 'include', 'decafnet_hip_front.h')
-FROZEN = {'decafnet_hip.h': 'SIGNATURES', 'decafnet_hip_train.h': 'TRAIN_SIGNATURES', 'decafnet_hip_dist.h': 'DIST_SIGNATURES',
-          'decafnet_hip_attn.h': 'ATTN_SIGNATURES'}
 NAMES = ['dcf_front_ext_version', 'dcf_op_vidmap_shared', 'dcf_op_vidmap_shared_bwd']
 LIMIT = 1 << 20
 E_REF_CAP = 2.0 ** -15
 
 
-def header_source():
-    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-
-
-def declared_symbols():
-    return sorted(set(re.findall(r'\b(dcf_[a-z0-9_]+)\s*\(', header_source())))
-
-
 # ---------------------------------------------------------------------------------------------- the ABI
-def test_front_header_equals_the_table():
+def test_front_table_names_flag_and_source():
     pkg = load_pkg()
-    table = pkg._lib.FRONT_SIGNATURES
-    assert sorted(table) == declared_symbols() == NAMES
-    src = header_source()
-    assert '#include "decafnet_hip.h"' in src and '#define DCF_FRONT_EXT_VERSION 1' in src
-    assert f'#define DCF_FRONT_NO_SKIP {pkg._lib.FRONT_NO_SKIP}' in src
-    for name, (res, args) in table.items():
-        m = re.search(r'\bint\s+' + name + r'\s*\((.*?)\)\s*;', src, flags=re.S)
-        assert m and res is ctypes.c_int32, name
-        params = [p for p in m.group(1).split(',') if p.strip() and p.strip() != 'void']
-        assert len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):                    # integer widths and pointers, position by position
-            want = (ctypes.c_void_p if '*' in p else {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}[p.split()[-2]])
-            assert a is want, (name, p.strip(), a)
-
-
-def test_the_frozen_tables_and_headers_hold_no_name_of_the_new_table():
-    pkg = load_pkg()
-    for header, table in FROZEN.items():
-        frozen = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-        for name in pkg._lib.FRONT_SIGNATURES:
-            assert name not in getattr(pkg._lib, table), (table, name)
-            assert not re.search(r'\b' + name + r'\s*\(', frozen), (header, name)
-
-
-def test_front_symbols_are_exported_and_versions():
-    pkg = load_pkg()
+    assert sorted(pkg._lib.FRONT_SIGNATURES) == NAMES
+    assert f'#define DCF_FRONT_NO_SKIP {pkg._lib.FRONT_NO_SKIP}' in H.source_of('decafnet_hip_front.h')
     assert 'front_grad.hip' in pkg.build.SOURCES
-    h = ctypes.CDLL(pkg.build.build())
-    for s in declared_symbols():
-        assert hasattr(h, s), f'{s} declared in include/decafnet_hip_front.h but not exported'
-    assert h.dcf_front_ext_version() == 1
-    assert h.dcf_attn_ext_version() == 1 and h.dcf_dist_ext_version() == 1 and h.dcf_train_ext_version() == 1 and h.dcf_abi_version() == 12
 
 
 # ---------------------------------------------------------------------------------------------- the fixtures

@@ -1,54 +1,32 @@
-"""CPU checks that go with the half-feature training-front-end extension (include/decafnet_hip_front_half.h): the header equals
-``_lib.FRONT_HALF_SIGNATURES`` and shares no name with the eight older tables and headers; every declared symbol is exported; what the
+"""CPU checks that go with the half-feature training-front-end extension (include/decafnet_hip_front_half.h; its header and table:
+tests/test_abi_headers.py): the names of ``_lib.FRONT_HALF_SIGNATURES`` and its parameters against the fp32 operators'; what the
 two operators and ``autograd.gated_vid_map`` refuse before a GPU is touched; and, on the emulation of tests/f16x3_ref.py, the property
 the half form of the weight-gradient kernel rests on: for binary16-representable features X the lo plane under the scale 2^4 is
 exactly zero, so ``r_lo . x_hi + r_hi . x_hi`` equals the three-product sum bit for bit -- and for features that are not representable
 it does not.  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT, load_pkg
+import abi_headers as H
+from conftest import load_pkg
 import f16x3_ref as F
 
-HEADER = os.path.join(ROOT, 'include', 'decafnet_hip_front_half.h')
-OLDER = {'decafnet_hip.h': 'SIGNATURES', 'decafnet_hip_train.h': 'TRAIN_SIGNATURES', 'decafnet_hip_dist.h': 'DIST_SIGNATURES',
-         'decafnet_hip_attn.h': 'ATTN_SIGNATURES', 'decafnet_hip_front.h': 'FRONT_SIGNATURES', 'decafnet_hip_guard.h': 'GUARD_SIGNATURES',
-         'decafnet_hip_clock.h': 'CLOCK_SIGNATURES', 'decafnet_hip_half.h': 'HALF_SIGNATURES'}
 NAMES = ['dcf_front_half_ext_version', 'dcf_op_vidmap_shared_bwd_h', 'dcf_op_vidmap_shared_h']
 PAIRS = {'dcf_op_vidmap_shared_h': 'dcf_op_vidmap_shared', 'dcf_op_vidmap_shared_bwd_h': 'dcf_op_vidmap_shared_bwd'}
-CTYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}
-
-
-def source_of(header):
-    return re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-
-
-def declared_symbols():
-    return sorted(set(re.findall(r'\b(dcf_[a-z0-9_]+)\s*\(', source_of('decafnet_hip_front_half.h'))))
 
 
 def params_of(name, header='decafnet_hip_front_half.h'):
-    m = re.search(r'\bint\s+' + name + r'\s*\((.*?)\)\s*;', source_of(header), flags=re.S)
-    assert m, name
-    return [' '.join(p.split()) for p in m.group(1).split(',') if p.strip() and p.strip() != 'void']
+    return H.params_of(header, name)[0]
 
 
 # ---------------------------------------------------------------------------------------------- the ABI
-def test_front_half_header_equals_the_table():
+def test_front_half_table_names_and_half_operands():
     pkg = load_pkg()
     table = pkg._lib.FRONT_HALF_SIGNATURES
-    assert sorted(table) == declared_symbols() == NAMES
-    src = source_of('decafnet_hip_front_half.h')
-    assert '#include "decafnet_hip.h"' in src and '#define DCF_FRONT_HALF_EXT_VERSION 1' in src
-    for name, (res, args) in table.items():
-        params = params_of(name)
-        assert res is ctypes.c_int32 and len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):                    # integer widths and pointers, position by position
-            assert a is (ctypes.c_void_p if '*' in p else CTYPES[p.split()[-2]]), (name, p, a)
+    assert sorted(table) == NAMES
+    assert 'front_grad.hip' in pkg.build.SOURCES                  # the operators live beside their fp32 forms: no new source file
     for name, base in PAIRS.items():
         assert table[name] == pkg._lib.FRONT_SIGNATURES[base], name
         mine, theirs = params_of(name), params_of(base, 'decafnet_hip_front.h')
@@ -64,27 +42,6 @@ def test_front_half_header_equals_the_table():
     assert order == ['vid', 'shallow', 'W', 'bias', 'gate', 'mask', 'correl', 'nq', 'Y', 'nvid', 'D', 'T', 'E', 'flags', 'stream']
     order = [p.split()[-1].lstrip('*') for p in params_of('dcf_op_vidmap_shared_bwd_h')]
     assert order == ['vid', 'shallow', 'gate', 'mask', 'correl', 'nq', 'dY', 'dW', 'db', 'nvid', 'D', 'T', 'E', 'flags', 'accumulate', 'stream']
-
-
-def test_the_older_tables_and_headers_hold_no_name_of_the_new_table():
-    pkg = load_pkg()
-    for header, table in OLDER.items():
-        older = source_of(header)
-        for name in pkg._lib.FRONT_HALF_SIGNATURES:
-            assert name not in getattr(pkg._lib, table), (table, name)
-            assert not re.search(r'\b' + name + r'\s*\(', older), (header, name)
-
-
-def test_front_half_symbols_are_exported_and_versions():
-    pkg = load_pkg()
-    assert 'front_grad.hip' in pkg.build.SOURCES                  # the operators live beside their fp32 forms: no new source file
-    h = ctypes.CDLL(pkg.build.build())
-    for s in declared_symbols():
-        assert hasattr(h, s), f'{s} declared in include/decafnet_hip_front_half.h but not exported'
-    assert h.dcf_front_half_ext_version() == 1
-    assert h.dcf_half_ext_version() == 1 and h.dcf_clock_ext_version() == 1 and h.dcf_guard_ext_version() == 1
-    assert h.dcf_front_ext_version() == 1 and h.dcf_attn_ext_version() == 1 and h.dcf_dist_ext_version() == 1
-    assert h.dcf_train_ext_version() == 1 and h.dcf_abi_version() == 12
 
 
 # ---------------------------------------------------------------------------------------------- refused before a launch

@@ -1,48 +1,8 @@
-"""tests/test_gpu_borders.py for the attention-gradient extension: every operator of ``_lib.ATTN_SIGNATURES`` on operands between
-poisoned borders (tests/arena.py) at the shapes of tests/attn_abi_cases.py -- a plain run, an arena run per fill; outputs bit-identical,
-borders and inputs untouched.  GPU only; no tolerance anywhere."""
-import pytest
+"""tests/test_gpu_borders.py for the attention-gradient extension: every case of tests/attn_abi_cases.py between poisoned borders
+(a plain run, an arena run per fill; outputs bit-identical, borders and inputs untouched), then what the extension's row of
+tests/borders.TABLE asserts of the plain run; and that every export of ``_lib.ATTN_SIGNATURES`` has a case or a reason.  GPU only;
+no tolerance anywhere."""
+from borders import completeness_test, ctx, export_test  # noqa: F401  (ctx: the module's fixture)
 
-import arena
-import attn_abi_cases
-from conftest import load_pkg
-
-pytestmark = pytest.mark.gpu
-
-
-class Ctx:
-    def __init__(self):
-        self.pkg = load_pkg()
-        self.lib = self.pkg._lib.lib()          # raises if the .so is missing: no silent fallback
-
-    def stream(self):
-        return self.pkg._lib.current_stream()
-
-
-@pytest.fixture(scope='module')
-def ctx():
-    return Ctx()
-
-
-@pytest.mark.parametrize('case', attn_abi_cases.CASES, ids=[f'{c.export}-{c.tag}' for c in attn_abi_cases.CASES])
-def test_attn_export_between_poisoned_borders(ctx, case):
-    specs, call = case.make()
-
-    def run(v):
-        rc = call(ctx, v)
-        ctx.pkg._lib.check(rc, case.export)    # a non-zero return code raises with dcf_last_error()
-        return rc
-
-    arena.run_three_ways(specs, run, 'cuda')
-
-
-def test_every_attn_export_has_a_case():
-    """every name of the extension's table has a poisoned-border case or is the version function"""
-    pkg = load_pkg()
-    names = list(pkg._lib.ATTN_SIGNATURES)
-    covered = {c.export for c in attn_abi_cases.CASES}
-    assert set(attn_abi_cases.EXCLUDED) == {'dcf_attn_ext_version'}
-    missing = [n for n in names if n not in covered and n not in attn_abi_cases.EXCLUDED]
-    assert not missing, f'attention-extension exports without a case: {missing}'
-    stale = [n for n in covered if n not in pkg._lib.ATTN_SIGNATURES]
-    assert not stale, f'not in ATTN_SIGNATURES: {stale}'
+test_attn_export_between_poisoned_borders = export_test('attn')
+test_every_attn_export_has_a_case = completeness_test('attn')

@@ -6,67 +6,23 @@ and every input untouched.  GPU only; no tolerance anywhere.
 
 What this cannot see: a stray read whose value a select discards, and the library's own scratch.  It bounds which memory can
 influence a result or be written; it is no proof of memory safety (profiles/abi_borders.md)."""
-import ctypes
-
 import pytest
 import torch
 
 import abi_cases
 import arena
+import borders
+from borders import ctx, export_test  # noqa: F401  (ctx: the module's fixture)
 from conftest import load_pkg
 
 pytestmark = pytest.mark.gpu
 
-
-class Ctx:
-    """what a case's call gets: the package, the library, the current stream and scratch models kept for the module"""
-
-    def __init__(self):
-        self.pkg = load_pkg()
-        self.lib = self.pkg._lib.lib()          # raises if the .so is missing: no silent fallback
-        self._models = {}
-
-    def stream(self):
-        return self.pkg._lib.current_stream()
-
-    def model(self, key, factory):
-        if key not in self._models:
-            self._models[key] = factory()      # (handle, the bound weights: alive as long as the handle)
-        return self._models[key][0]
-
-    def close(self):
-        torch.cuda.synchronize()
-        for h, _ in self._models.values():
-            self.lib.dcf_model_destroy(h)
-        self._models.clear()
+test_export_between_poisoned_borders = export_test('base')
 
 
-@pytest.fixture(scope='module')
-def ctx():
-    c = Ctx()
-    yield c
-    c.close()
-
-
-@pytest.mark.parametrize('case', abi_cases.CASES, ids=[f'{c.export}-{c.tag}' for c in abi_cases.CASES])
-def test_export_between_poisoned_borders(ctx, case):
-    made = case.make()
-    specs, call = made[0], made[1]
-    fixup = made[2] if len(made) > 2 else None
-    check = ctx.pkg._lib.check
-
-    def run(v):
-        rc = call(ctx, v)
-        check(rc, case.export)                 # a non-zero return code raises with dcf_last_error()
-        return rc
-
-    try:
-        for name, value in case.options:
-            check(ctx.lib.dcf_debug_set_option(name.encode(), value), 'dcf_debug_set_option')
-        arena.run_three_ways(specs, run, 'cuda', fixup)
-    finally:
-        for name, _ in case.options:
-            check(ctx.lib.dcf_debug_set_option(name.encode(), -1), 'dcf_debug_set_option')
+def test_every_extension_has_a_row_of_the_borders_table():
+    keys = [e.key for e in load_pkg()._lib.EXTENSIONS]
+    assert sorted(keys) == sorted(list(borders.TABLE) + list(borders.NO_CASE_TABLE))
 
 
 def test_every_export_is_assigned():

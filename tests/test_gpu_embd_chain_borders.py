@@ -8,6 +8,7 @@ import torch
 import arena
 import embd_chain_cases as C
 import embd_chain_ref as ER
+from conftest import load_pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -42,12 +43,6 @@ def test_embd_export_between_poisoned_borders(ctx, export, B, T, with_pe, ln_in)
 
 
 def test_every_embd_export_has_a_case():
-    pkg = ctx_pkg()
-    names = list(pkg._lib.EMBD_SIGNATURES)
+    names = list(load_pkg()._lib.EMBD_SIGNATURES)
     assert set(EXCLUDED) == {'dcf_embd_ext_version'}
     assert sorted(n for n in names if n not in EXCLUDED) == sorted(EXPORTS)
-
-
-def ctx_pkg():
-    from conftest import load_pkg
-    return load_pkg()

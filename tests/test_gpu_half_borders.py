@@ -1,74 +1,8 @@
-"""tests/test_gpu_borders.py for the half-feature extension: every export of ``_lib.HALF_SIGNATURES`` on operands between poisoned
-borders (tests/arena.py) at the shapes of tests/half_abi_cases.py -- a plain run, an arena run per fill; outputs bit-identical, borders
-and inputs untouched.  The half operands lie in the arena as the bytes of their binary16 values, so what surrounds them reads as half
-NaNs (fill 1) or zeros (fill 2); the forwards write their three outputs into the arena too.  GPU only; no tolerance anywhere."""
-import pytest
-import torch
+"""tests/test_gpu_borders.py for the half-feature extension: every case of tests/half_abi_cases.py between poisoned borders
+(a plain run, an arena run per fill; outputs bit-identical, borders and inputs untouched), then what the extension's row of
+tests/borders.TABLE asserts of the plain run; and that every export of ``_lib.HALF_SIGNATURES`` has a case or a reason.  GPU only;
+no tolerance anywhere."""
+from borders import completeness_test, ctx, export_test  # noqa: F401  (ctx: the module's fixture)
 
-import arena
-import half_abi_cases
-from conftest import load_pkg
-
-pytestmark = pytest.mark.gpu
-
-
-class Ctx:
-    """what a case's call gets: the package, the library, the current stream and the models kept for the module"""
-
-    def __init__(self):
-        self.pkg = load_pkg()
-        self.lib = self.pkg._lib.lib()          # raises if the .so is missing: no silent fallback
-        self._models = {}
-
-    def stream(self):
-        return self.pkg._lib.current_stream()
-
-    def model(self, key, factory):
-        if key not in self._models:
-            self._models[key] = factory()
-        return self._models[key]
-
-
-@pytest.fixture(scope='module')
-def ctx():
-    c = Ctx()
-    yield c
-    torch.cuda.synchronize()
-    c._models.clear()
-
-
-@pytest.mark.parametrize('case', half_abi_cases.CASES, ids=[f'{c.export}-{c.tag}' for c in half_abi_cases.CASES])
-def test_half_export_between_poisoned_borders(ctx, case):
-    specs, call = case.make()
-    check = ctx.pkg._lib.check
-    halves = [name for name, t, role, *rest in specs if rest and t.dtype == torch.uint8 and t.dim() == 2 and rest[0] == t.shape[-1]]
-    assert halves, 'every case of this extension has a half operand'
-
-    def run(v):
-        rc = call(ctx, v)
-        check(rc, case.export)                 # a non-zero return code raises with dcf_last_error()
-        return rc
-
-    try:
-        for name, value in case.options:
-            check(ctx.lib.dcf_debug_set_option(name.encode(), value), 'dcf_debug_set_option')
-        plain = arena.run_three_ways(specs, run, 'cuda')
-    finally:
-        for name, _ in case.options:
-            check(ctx.lib.dcf_debug_set_option(name.encode(), -1), 'dcf_debug_set_option')
-    for name, t in plain.items():              # the plain run computed something: no sentinel left, nothing non-finite
-        if t.is_floating_point():
-            assert bool(torch.isfinite(t).all()), name
-
-
-def test_every_half_export_has_a_case():
-    """every name of the extension's table has a poisoned-border case or a reason why it has none"""
-    pkg = load_pkg()
-    names = list(pkg._lib.HALF_SIGNATURES)
-    covered = {c.export for c in half_abi_cases.CASES}
-    assert set(half_abi_cases.EXCLUDED) == {'dcf_half_ext_version'}
-    missing = [n for n in names if n not in covered and n not in half_abi_cases.EXCLUDED]
-    assert not missing, f'half exports without a case: {missing}'
-    stale = [n for n in covered if n not in pkg._lib.HALF_SIGNATURES]
-    assert not stale, f'not in HALF_SIGNATURES: {stale}'
-    assert covered == {'dcf_forward_eval_h', 'dcf_forward_eval_videos_h', 'dcf_op_linear_cm_split_h', 'dcf_op_linear_cm_split_ld_h', 'dcf_op_sidekick_h'}
+test_half_export_between_poisoned_borders = export_test('half')
+test_every_half_export_has_a_case = completeness_test('half')

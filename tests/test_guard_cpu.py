@@ -1,83 +1,40 @@
-"""CPU checks that go with the step-guard extension (include/decafnet_hip_guard.h): the header equals ``_lib.GUARD_SIGNATURES`` and
-``_lib.DcfGuardState`` and shares no name with the five frozen tables and headers; every declared symbol is exported; the restatement
+"""CPU checks that go with the step-guard extension (include/decafnet_hip_guard.h; its header and table: tests/test_abi_headers.py): the
+names of ``_lib.GUARD_SIGNATURES``, the verdict values and ``_lib.DcfGuardState`` against the header; the restatement
 of the verdict rule (tests/guard_ref.py) on NaN, +-inf, an overflowing square and a NO_GRAD row; and what ``train.TrainStep`` makes of
 ``skip_nonfinite`` without a GPU.  No GPU."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, load_pkg
+import abi_headers as H
+from conftest import load_pkg
 import guard_ref as G
 
-HEADER = os.path.join(ROOT, 'include', 'decafnet_hip_guard.h')
-FROZEN = {'decafnet_hip.h': 'SIGNATURES', 'decafnet_hip_train.h': 'TRAIN_SIGNATURES', 'decafnet_hip_dist.h': 'DIST_SIGNATURES',
-          'decafnet_hip_attn.h': 'ATTN_SIGNATURES', 'decafnet_hip_front.h': 'FRONT_SIGNATURES'}
 NAMES = ['dcf_guard_adam_step', 'dcf_guard_arm', 'dcf_guard_disarm', 'dcf_guard_ext_version', 'dcf_guard_grad_norm']
-CTYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}
-
-
-def header_source():
-    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-
-
-def declared_symbols():
-    return sorted(set(re.findall(r'\b(dcf_[a-z0-9_]+)\s*\(', header_source())))
-
-
 # ---------------------------------------------------------------------------------------------- the ABI
-def test_guard_header_equals_the_table():
+def test_guard_table_names_verdicts_and_source():
     pkg = load_pkg()
-    table = pkg._lib.GUARD_SIGNATURES
-    assert sorted(table) == declared_symbols() == NAMES
-    src = header_source()
-    assert '#include "decafnet_hip.h"' in src and '#define DCF_GUARD_EXT_VERSION 1' in src
+    assert sorted(pkg._lib.GUARD_SIGNATURES) == NAMES
+    src = H.source_of('decafnet_hip_guard.h')
     assert f'#define DCF_GUARD_APPLY {pkg._lib.GUARD_APPLY}' in src and f'#define DCF_GUARD_SKIP {pkg._lib.GUARD_SKIP}' in src
-    for name, (res, args) in table.items():
-        m = re.search(r'\bint\s+' + name + r'\s*\((.*?)\)\s*;', src, flags=re.S)
-        assert m and res is ctypes.c_int32, name
-        params = [p for p in m.group(1).split(',') if p.strip() and p.strip() != 'void']
-        assert len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):                    # integer widths and pointers, position by position
-            want = ctypes.c_void_p if '*' in p else CTYPES[p.split()[-2]]
-            assert a is want, (name, p.strip(), a)
+    assert 'optim_guard.hip' in pkg.build.SOURCES
 
 
 def test_guard_state_record_equals_the_header():
     """field by field, in order; 48 bytes with every 64-bit counter on an 8-byte boundary; the host's numpy record is the same"""
     pkg = load_pkg()
-    body = re.search(r'typedef\s+struct\s+dcf_guard_state\s*\{(.*?)\}\s*dcf_guard_state\s*;', header_source(), flags=re.S).group(1)
+    body = re.search(r'typedef\s+struct\s+dcf_guard_state\s*\{(.*?)\}\s*dcf_guard_state\s*;', H.source_of('decafnet_hip_guard.h'), flags=re.S).group(1)
     fields = [tuple(d.split()) for d in body.split(';') if d.strip()]
     S = pkg._lib.DcfGuardState
-    assert [(n, CTYPES[t]) for t, n in fields] == [(n, t) for n, t in S._fields_]
+    assert [(n, H.SCALARS[t]) for t, n in fields] == [(n, t) for n, t in S._fields_]
     assert ctypes.sizeof(S) == 48 == pkg.optim._GUARD.itemsize
     for n, t in S._fields_:
         off = getattr(S, n).offset
         assert off == pkg.optim._GUARD.fields[n][1] and off % ctypes.sizeof(t) == 0, n
     assert {n for n, _ in S._fields_} - {'reserved0', 'reserved1'} == set(G.FIELDS)
-
-
-def test_the_frozen_tables_and_headers_hold_no_name_of_the_new_table():
-    pkg = load_pkg()
-    for header, table in FROZEN.items():
-        frozen = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-        for name in pkg._lib.GUARD_SIGNATURES:
-            assert name not in getattr(pkg._lib, table), (table, name)
-            assert not re.search(r'\b' + name + r'\s*\(', frozen), (header, name)
-
-
-def test_guard_symbols_are_exported_and_versions():
-    pkg = load_pkg()
-    assert 'optim_guard.hip' in pkg.build.SOURCES
-    h = ctypes.CDLL(pkg.build.build())
-    for s in declared_symbols():
-        assert hasattr(h, s), f'{s} declared in include/decafnet_hip_guard.h but not exported'
-    assert h.dcf_guard_ext_version() == 1
-    assert h.dcf_front_ext_version() == 1 and h.dcf_attn_ext_version() == 1 and h.dcf_dist_ext_version() == 1
-    assert h.dcf_train_ext_version() == 1 and h.dcf_abi_version() == 12
 
 
 # ---------------------------------------------------------------------------------------------- the restatement

@@ -1,59 +1,37 @@
-"""CPU checks that go with the half-feature extension (include/decafnet_hip_half.h): the header equals ``_lib.HALF_SIGNATURES`` and
-shares no name with the seven frozen tables and headers; every declared symbol is exported; the feature loaders' ``dtype``; what is
+"""CPU checks that go with the half-feature extension (include/decafnet_hip_half.h; its header and table: tests/test_abi_headers.py): the
+names of ``_lib.HALF_SIGNATURES``, its host arrays and half operands; the feature loaders' ``dtype``; what is
 refused before a GPU is touched; and, on the emulation of tests/f16x3_ref.py, the property the half A operand of the split tile GEMM
 rests on: for a binary16-representable operand the ``mid`` plane is exactly zero, so the product without the a_mid . w_hi term equals
 the full one -- and for an operand that is not representable it does not.  No GPU."""
 import ctypes
-import os
 import pickle
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, load_pkg
+import abi_headers as H
+from conftest import load_pkg
 import f16x3_ref as F
 
-HEADER = os.path.join(ROOT, 'include', 'decafnet_hip_half.h')
-FROZEN = {'decafnet_hip.h': 'SIGNATURES', 'decafnet_hip_train.h': 'TRAIN_SIGNATURES', 'decafnet_hip_dist.h': 'DIST_SIGNATURES',
-          'decafnet_hip_attn.h': 'ATTN_SIGNATURES', 'decafnet_hip_front.h': 'FRONT_SIGNATURES', 'decafnet_hip_guard.h': 'GUARD_SIGNATURES',
-          'decafnet_hip_clock.h': 'CLOCK_SIGNATURES'}
 NAMES = ['dcf_forward_eval_h', 'dcf_forward_eval_videos_h', 'dcf_half_ext_version', 'dcf_op_linear_cm_split_h', 'dcf_op_linear_cm_split_ld_h',
          'dcf_op_sidekick_h']
-CTYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}
-
-
-def header_source():
-    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-
-
-def declared_symbols():
-    return sorted(set(re.findall(r'\b(dcf_[a-z0-9_]+)\s*\(', header_source())))
 
 
 def params_of(name):
-    m = re.search(r'\bint\s+' + name + r'\s*\((.*?)\)\s*;', header_source(), flags=re.S)
-    assert m, name
-    return [p.strip() for p in m.group(1).split(',') if p.strip() and p.strip() != 'void']
+    return H.params_of('decafnet_hip_half.h', name)[0]
 
 
 # ---------------------------------------------------------------------------------------------- the ABI
-def test_half_header_equals_the_table():
+def test_half_table_names_host_arrays_and_half_operands():
     pkg = load_pkg()
     table = pkg._lib.HALF_SIGNATURES
-    assert sorted(table) == declared_symbols() == NAMES
-    src = header_source()
-    assert '#include "decafnet_hip.h"' in src and '#define DCF_HALF_EXT_VERSION 1' in src
-    for name, (res, args) in table.items():
-        params = params_of(name)
-        assert res is ctypes.c_int32 and len(params) == len(args), (name, len(params), len(args))
-        for p, a in zip(params, args):                    # integer widths and pointers, position by position
-            if '*' not in p:
-                assert a is CTYPES[p.split()[-2]], (name, p, a)
-            elif p.count('*') == 2 or 'int32_t*' in p.replace(' ', ''):
-                assert a in (ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32)), (name, p, a)      # HOST arrays
-            else:
+    assert sorted(table) == NAMES and 'half.hip' in pkg.build.SOURCES
+    for name, (_, args) in table.items():             # which pointers are HOST arrays and which device addresses
+        for p, a in zip(params_of(name), args):
+            if p.count('*') == 2 or 'int32_t*' in p.replace(' ', ''):
+                assert a in (ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32)), (name, p, a)
+            elif '*' in p:
                 assert a is ctypes.c_void_p, (name, p, a)
     # the half operands are the bits of binary16, and nothing else of the forwards changed type
     for name, base in (('dcf_forward_eval_h', 'dcf_forward_eval'), ('dcf_forward_eval_videos_h', 'dcf_forward_eval_videos'),
@@ -67,27 +45,6 @@ def test_half_header_equals_the_table():
     order = [p.split()[-1].lstrip('*') for p in params_of('dcf_op_linear_cm_split_ld_h')]
     assert order == ['A_cm', 'lda', 'W', 'bias', 'C', 'M', 'N', 'K', 'nterms', 'unscaled', 'stream']
     assert params_of('dcf_op_linear_cm_split_ld_h')[0].startswith('const uint16_t') and params_of('dcf_op_linear_cm_split_ld_h')[1] == 'int64_t lda'
-
-
-def test_the_frozen_tables_and_headers_hold_no_name_of_the_new_table():
-    pkg = load_pkg()
-    for header, table in FROZEN.items():
-        frozen = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-        for name in pkg._lib.HALF_SIGNATURES:
-            assert name not in getattr(pkg._lib, table), (table, name)
-            assert not re.search(r'\b' + name + r'\s*\(', frozen), (header, name)
-
-
-def test_half_symbols_are_exported_and_versions():
-    pkg = load_pkg()
-    assert 'half.hip' in pkg.build.SOURCES
-    h = ctypes.CDLL(pkg.build.build())
-    for s in declared_symbols():
-        assert hasattr(h, s), f'{s} declared in include/decafnet_hip_half.h but not exported'
-    assert h.dcf_half_ext_version() == 1
-    assert h.dcf_clock_ext_version() == 1 and h.dcf_guard_ext_version() == 1 and h.dcf_front_ext_version() == 1
-    assert h.dcf_attn_ext_version() == 1 and h.dcf_dist_ext_version() == 1 and h.dcf_train_ext_version() == 1
-    assert h.dcf_abi_version() == 12
 
 
 # ---------------------------------------------------------------------------------------------- the loaders

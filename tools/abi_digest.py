@@ -3,8 +3,8 @@ the library bit for bit (a refactor that must not change a result).
 
     python tools/abi_digest.py [--out DIR] [name=path/to/libdecafnet_hip.so ...]      # DIR: default build/digest of the package
 
-Cases: every entry of tests/abi_cases.CASES and of the extension tables in the same format (attn_, front_, train_abi_cases), run once
-on plain tensors (tests/arena.plain_operands: `out` operands start from the sentinel, so a part an export leaves alone hashes equal),
+Cases: every entry of every case table of tests/borders.TABLE (the base table of tests/abi_cases.py and the train, dist, attn, front,
+guard, clock, half and front_half extension tables in the same format), under the key `<export>-<tag>`, run once on plain tensors (tests/arena.plain_operands: `out` operands start from the sentinel, so a part an export leaves alone hashes equal),
 and MANY_PARTS below: for each user of the fixed-order blocked sum (blocked_sum, csrc/grad_common.h) the smallest shape whose number
 of partials lies in 9 .. 63 and the smallest with more than 64, so that all three levels of the tree carry data.  The part counts
 are read off the slicing constants of the kernels and recorded in the JSON.
@@ -62,13 +62,9 @@ def many_parts():
 def child(out_path):
     sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
     import torch
-    import abi_cases
     import arena
-    import attn_abi_cases
-    import front_abi_cases
-    import train_abi_cases
-    from test_gpu_borders import Ctx
-    ctx = Ctx()
+    import borders
+    ctx = borders.Ctx()
     check = ctx.pkg._lib.check
     digest, parts = {}, {}
 
@@ -76,7 +72,7 @@ def child(out_path):
         made = make()
         specs, call = made[0], made[1]
         views, keep = arena.plain_operands(specs, 'cuda')
-        if len(made) > 2:
+        if len(made) > 2 and made[2] is not None:
             made[2](views, lambda name, t: views[name].copy_(t))
         try:
             for name, value in options:
@@ -90,8 +86,8 @@ def child(out_path):
         digest[key] = {name: hashlib.sha256(views[name].contiguous().reshape(-1).view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
                        for name, _, role, *_ in specs if role != 'in'}
 
-    for table in (abi_cases, attn_abi_cases, front_abi_cases, train_abi_cases):
-        for c in table.CASES:
+    for row in borders.TABLE.values():
+        for c in row.cases.CASES:
             run(f'{c.export}-{c.tag}', c.export, c.make, c.options)
     for export, tag, n, make in many_parts():
         run(f'many-parts:{export}-{tag}', export, make)
