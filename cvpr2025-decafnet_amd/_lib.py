@@ -274,6 +274,23 @@ PENDING = (
 )
 
 
+# the evaluation-metric extension (include/decafnet_hip_eval.h, csrc/eval_metric.hip).  Every operand is device memory: ``segs`` /
+# ``meta`` / ``best`` fp32, ``counts`` / ``ranks`` int32, ``threshs`` float64, ``hits`` / ``n_queries`` int64 and accumulated into.
+c_f64p = ctypes.c_void_p
+EVAL_TABLE = {
+    'dcf_eval_ext_version': (i32, []),
+    'dcf_op_recall_update': (i32, [c_f32p, c_i32p, c_f32p, i32, i32, c_i32p, i32, c_f64p, i32, c_i64p, c_i64p, c_f32p, vp]),
+}
+
+
+# Bound by lib() after the records above and waiting for the same follow-up as PENDING: registration at the end of EXTENSIONS
+# together with a ``borders.TABLE`` row (the cases are tests/eval_abi_cases.py, run through the same driver by
+# tests/test_gpu_eval_metric.py).
+STAGED = (
+    Extension('eval', 'decafnet_hip_eval.h', 'dcf_eval_ext_version', 1, 'DCF_EVAL_EXT_VERSION', ('decafnet_hip.h',), EVAL_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -285,10 +302,10 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS + PENDING:
+        for ext in EXTENSIONS + PENDING + STAGED:
             for name, (res, args) in ext.table.items():
                 if name in bound:
-                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING')
+                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

@@ -17,7 +17,8 @@ annotation file and the per-video dict of the reference's video-centric dataset,
 The training side, further down: ``VideoCentricTrainData`` (what the reference's training dataset decides: groups, windows, targets;
 host code), ``collate_host`` (the Trainer's collate on CPU tensors), ``FeatureBank`` (the features of a training set in device memory,
 filled once) and ``TrainLoader`` (batches for ``train.TrainStep.step``, assembled on the GPU by dcf_op_assemble_rows,
-include/decafnet_hip_batch.h, or on the host route).
+include/decafnet_hip_batch.h, or on the host route); and ``EvalBank``, the validation set in device memory for the evaluations of a
+training run (``train.fit``), whose items ``GroundingEvaluator.prepare`` takes in place of host samples.
 """
 from __future__ import annotations
 
@@ -516,6 +517,110 @@ class FeatureBank:
             raise ValueError(f'{stream} of {key}: {r1 - r0} positions do not fit the batch buffer of {T_out} '
                              f'(where the reference\'s copy_ fails; shallow_window=\'same\' crops both streams)')
         return (first + r0) * self.width[stream], r1 - r0
+
+
+class EvalBank:
+    """The validation set in device memory, filled once from a ``VideoCentricEvalData``: the sibling of ``FeatureBank`` for the
+    evaluation a training run does between epochs.  The streams ``vid``, ``shallow`` and ``text`` are one device buffer each, rows as
+    the files store them (a float16 file stays float16 under ``feature_dtype='stored'``), with the loaders' own rules (sources aligned
+    and concatenated, ``downsample_rate`` for ``vid`` only, ``normalize_*``; token features uncut, as ``sample`` hands them on).
+    ``cls`` is the (N_queries, D) table of text-CLS rows in query order and ``meta`` the (N_queries, 8) fp32 table of
+    ``evaluator.query_meta`` -- ground truth, strides, fps, duration -- that dcf_op_recall_update reads; ``vid_stride`` is the
+    model's (``opt.model.vid_stride``), which the evaluator checks.
+
+    Iterating yields one dict per video, in the order of ``eval_data.videos``, that ``GroundingEvaluator.prepare`` / ``run`` take in
+    place of a host sample: the host scalars of ``VideoCentricEvalData.sample`` (fps, duration, segment, clip_size, clip_stride,
+    clip_id, ...), ``text`` as (C_t, L) views of the bank, ``text_cls`` and ``meta`` as slices of the tables, ``vid_len`` and
+    ``bank``.  ``prepare`` asks ``windows(clip_id, T)`` for the padded (1, D, T) windows and the mask: two launches of
+    dcf_op_assemble_rows on descriptors that were uploaded with the bank, so a video costs no upload at all.
+
+    Refused: ``ext_score_dir`` (NotImplementedError: external scores stay on the host route), a video whose ``vid`` and ``shallow``
+    streams differ in length (the host route pads them apart), a float16 / fp32 pair.  ``max_bytes`` / ``nbytes`` as ``FeatureBank``."""
+
+    STREAMS = FeatureBank.STREAMS
+
+    def __init__(self, eval_data, vid_stride=1, device='cuda', max_bytes=None):
+        from .evaluator import query_meta
+        ed = self.eval_data = eval_data
+        if ed.ext_score_dir is not None:
+            raise NotImplementedError(f'EvalBank: ext_score_dir = {ed.ext_score_dir!r} is not implemented: external scores are read '
+                                      f'per video on the host route (GroundingEvaluator.run on the VideoCentricEvalData itself)')
+        self.vid_stride = int(vid_stride)
+        host = {s: [] for s in self.STREAMS}
+        self.rows = {s: {} for s in self.STREAMS}
+        n = dict.fromkeys(self.STREAMS, 0)
+
+        def add(stream, key, cm):                                  # cm: (C, T) as the loaders return it -> rows (T, C)
+            a = cm.t().contiguous()
+            if host[stream] and (a.dtype != host[stream][0].dtype or a.size(1) != host[stream][0].size(1)):
+                raise ValueError(f'{stream} features of {key}: {a.dtype} x {a.size(1)} channels in a stream of {host[stream][0].dtype} x '
+                                 f'{host[stream][0].size(1)} (one dtype and one width per stream)')
+            host[stream].append(a)
+            self.rows[stream][key] = (n[stream], a.size(0))
+            n[stream] += a.size(0)
+
+        cls, meta, self.queries, q0 = [], [], {}, 0
+        for vid_id, v in ed.videos.items():
+            vid = load_video_features(ed.vid_dirs, vid_id, ed.vid_fmt, ed.ds, ed.normalize_vid, ed.feature_dtype)
+            shallow = load_video_features(ed.shallow_dirs, vid_id, ed.shallow_fmt, 1, ed.normalize_vid, ed.feature_dtype)
+            if vid.size(1) != shallow.size(1):
+                raise ValueError(f'video {vid_id}: vid has {vid.size(1)} clips and shallow_vid {shallow.size(1)}; the bank pads both to one length')
+            add('vid', vid_id, vid)
+            add('shallow', vid_id, shallow)
+            for t in v['text_ids']:
+                if t not in self.rows['text']:
+                    add('text', t, load_text_features(ed.text_dir, t, ed.normalize_text))
+            nq = len(v['segments'])
+            cls.append(ed.cls.lookup([v['annotations'][i]['sentence'] for i in range(nq)]))       # as ``sample`` indexes them
+            meta.append(query_meta(v['segments'], self.vid_stride, ed.clip_stride, ed.clip_size, v['fps'], v['duration']))
+            self.queries[vid_id] = (q0, nq)
+            q0 += nq
+        if not host['vid']:
+            raise ValueError('EvalBank: the evaluation split holds no video')
+        if (host['vid'][0].dtype == torch.float16) != (host['shallow'][0].dtype == torch.float16):
+            raise ValueError(f"vid is {host['vid'][0].dtype} and shallow_vid is {host['shallow'][0].dtype}: float16 clip features come as a pair")
+        cls, meta = torch.cat(cls), torch.from_numpy(np.concatenate(meta))
+        desc = {s: torch.tensor([[r0 * host[s][0].size(1), rows] for r0, rows in (self.rows[s][k] for k in ed.videos)], dtype=torch.int64)
+                for s in ('vid', 'shallow')}
+        tables = [cls, meta, desc['vid'], desc['shallow']]
+        need = sum(a.numel() * a.element_size() for s in self.STREAMS for a in host[s]) + sum(t.numel() * t.element_size() for t in tables)
+        if max_bytes is not None and need > max_bytes:
+            raise ValueError(f'EvalBank: the features need {need} bytes, max_bytes is {max_bytes} '
+                             f'(GroundingEvaluator.run on the VideoCentricEvalData takes the host route)')
+        self.device = torch.device(device)
+        self.data = {s: torch.cat(host[s]).to(self.device) for s in self.STREAMS}
+        self.cls, self.meta = cls.to(self.device), meta.to(self.device)
+        self.desc = {s: d.to(self.device) for s, d in desc.items()}
+        self.width = {s: self.data[s].size(1) for s in self.STREAMS}
+        self.index = {k: i for i, k in enumerate(ed.videos)}
+        self.nbytes = need
+
+    assemble = FeatureBank.assemble
+
+    def __len__(self):
+        return len(self.index)
+
+    def windows(self, vid_id, T):
+        """-> (vid (1, D, T), shallow (1, D, T), mask (1, T) bool): the video padded with zeros to T columns, the bits of
+        ``F.pad`` on the host sample"""
+        i, rows = self.index[vid_id], self.rows['vid'][vid_id][1]
+        if rows > T:
+            raise ValueError(f'video {vid_id}: {rows} clips do not fit a window of {T}')
+        vid, mask = self.assemble('vid', self.desc['vid'][i:i + 1], T)
+        shallow, _ = self.assemble('shallow', self.desc['shallow'][i:i + 1], T, want_mask=False)
+        return vid, shallow, mask
+
+    def item(self, vid_id):
+        ed, v = self.eval_data, self.eval_data.videos[vid_id]
+        q0, nq = self.queries[vid_id]
+        text = tuple(self.data['text'][r0:r0 + rows].t() for r0, rows in (self.rows['text'][t] for t in v['text_ids']))
+        return dict(fps=v['fps'], num_frames=v['num_frames'], duration=v['duration'], segment=v['segments'], clip_size=ed.clip_size,
+                    clip_stride=ed.clip_stride, clip_id=vid_id, text_id=tuple(range(nq)), vid_len=self.rows['vid'][vid_id][1], bank=self,
+                    text=text, text_cls=self.cls[q0:q0 + nq], meta=self.meta[q0:q0 + nq], ext_scores=None)
+
+    def __iter__(self):
+        for vid_id in self.index:
+            yield self.item(vid_id)
 
 
 class TrainLoader:

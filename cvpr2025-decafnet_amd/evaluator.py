@@ -7,6 +7,10 @@
 
     iou, RecallCounter  libs/train_utils.py:81-96 and the metric loop of Evaluator.run, worker_v2.py:857-878, 890-901
     load_features       feature-file formats of libs/data/dataset.py:128-135, 398-399 ((T, C) on disk -> (C, T))
+
+    query_meta, DeviceRecallCounter   the same metric accumulated in device memory by dcf_op_recall_update
+        (include/decafnet_hip_eval.h): ``run(dataset, counter=DeviceRecallCounter(...))`` enqueues forward, collect_segments,
+        batched NMS and the metric per video and reads nothing back before ``metrics()``
 """
 from __future__ import annotations
 
@@ -76,6 +80,91 @@ class RecallCounter:
             lines.append('-----')
             lines += [f'Rank@{k}, IoU@{t:.1f}: {m[i, j]:.2f}' for j, t in enumerate(self.iou_threshs)]
         return '\n'.join(lines + ['-----', ''])
+
+
+META_FIELDS = ('gt_start', 'gt_end', 'vid_stride', 'clip_stride', 'half_clip', 'fps', 'duration', 'convert')
+
+
+def query_meta(segment, vid_stride, clip_stride, clip_size, fps, duration, convert=True):
+    """The per-query record of dcf_op_recall_update, (n, 8) float32 in the order of ``META_FIELDS``: the ground truth rounded to
+    fp32 as ``RecallCounter.update`` rounds it, and the scalars of ``finish_proposals`` each rounded to fp32 as torch rounds a
+    Python scalar that meets an fp32 tensor (0.5 * clip_size is formed in double first, as there)."""
+    seg = np.asarray(segment, dtype=np.float64).reshape(-1, 2)
+    meta = np.empty((len(seg), 8), dtype=np.float32)
+    meta[:, :2] = seg
+    meta[:, 2:] = np.array([vid_stride, clip_stride, 0.5 * clip_size, fps, duration, 1.0 if convert else 0.0], dtype=np.float64)
+    return meta
+
+
+class DeviceRecallCounter:
+    """``RecallCounter`` with its table in device memory: ``update_device`` launches dcf_op_recall_update (include/decafnet_hip_eval.h)
+    on the current stream for the rows ``nms.batched_nms_queries`` left on the GPU, and nothing is read back until ``hits`` /
+    ``n_queries`` / ``metrics()`` / ``report()`` are asked for -- each of those is one 8 * (cells + 1)-byte copy that waits for the
+    current stream.  The adds are integer atomics, so lanes on several streams may share one counter; the reader's stream has to be
+    behind them (``GroundingEvaluator.run`` sees to it).  ``reset()`` zeroes the table on the stream."""
+
+    MAX = 8                                        # ranks and thresholds of one dcf_op_recall_update call
+
+    def __init__(self, ranks=(1, 5), iou_threshs=(0.3, 0.5), device='cuda'):
+        self.ranks = tuple(int(k) for k in ranks)
+        self.iou_threshs = np.asarray(iou_threshs, dtype=np.float64)
+        if not 1 <= len(self.ranks) <= self.MAX or not 1 <= len(self.iou_threshs) <= self.MAX or min(self.ranks) < 1:
+            raise ValueError(f'DeviceRecallCounter: ranks {self.ranks}, iou_threshs {tuple(self.iou_threshs)}: 1 to {self.MAX} of each, ranks >= 1')
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('DeviceRecallCounter counts on the MI355X only: RecallCounter is the host route')
+        self._ranks = torch.tensor(self.ranks, dtype=torch.int32, device=self.device)
+        self._threshs = torch.from_numpy(self.iou_threshs.copy()).to(self.device)
+        self._cells = len(self.ranks) * len(self.iou_threshs)
+        self._table = torch.zeros(self._cells + 1, dtype=torch.int64, device=self.device)      # hits, then n_queries
+
+    def reset(self):
+        self._table.zero_()
+        return self
+
+    def update_device(self, segs, counts, meta, best=None):
+        """segs (nq, M, 2) fp32 and counts (nq) int32 as ``batched_nms_queries`` returns them, meta (nq, 8) fp32 (``query_meta``), all on
+        the GPU; ``best``: an (nq, n_ranks) fp32 tensor to receive the best IoU per rank, or None.  No host wait."""
+        from . import _lib
+        nq, M = segs.shape[0], segs.shape[1]
+        if segs.dim() != 3 or segs.shape[2] != 2 or counts.shape != (nq,) or meta.shape != (nq, 8):
+            raise ValueError(f'update_device: segs {tuple(segs.shape)}, counts {tuple(counts.shape)}, meta {tuple(meta.shape)}')
+        if segs.dtype != torch.float32 or meta.dtype != torch.float32 or not (segs.is_cuda and counts.is_cuda and meta.is_cuda):
+            raise ValueError('update_device: segs and meta are fp32 tensors on the GPU')
+        if best is not None and (best.shape != (nq, len(self.ranks)) or best.dtype != torch.float32 or not best.is_contiguous()):
+            raise ValueError(f'update_device: best is a contiguous fp32 tensor of shape ({nq}, {len(self.ranks)})')
+        if nq == 0:
+            return
+        segs, counts, meta = segs.contiguous(), counts.to(torch.int32).contiguous(), meta.contiguous()
+        _lib.check(_lib.lib().dcf_op_recall_update(_lib.ptr(segs), _lib.ptr(counts), _lib.ptr(meta), nq, M, _lib.ptr(self._ranks),
+                                                   len(self.ranks), _lib.ptr(self._threshs), len(self.iou_threshs), _lib.ptr(self._table),
+                                                   _lib.ptr(self._table[self._cells:]), _lib.ptr(best), _lib.current_stream()),
+                   'dcf_op_recall_update')
+
+    def add_misses(self, n):
+        """n queries without a proposal: misses at every cell (on the stream)"""
+        self._table[self._cells:] += int(n)
+
+    def _read(self):
+        t = self._table.cpu()                      # the one host read
+        return t[:self._cells].numpy().reshape(len(self.ranks), len(self.iou_threshs)).astype(np.float64), int(t[self._cells])
+
+    @property
+    def hits(self):
+        return self._read()[0]
+
+    @property
+    def n_queries(self):
+        return self._read()[1]
+
+    counts = hits                                  # the reference's attribute names, as on RecallCounter
+    text_cnt = n_queries
+
+    def metrics(self):
+        hits, n = self._read()
+        return hits / max(n, 1)
+
+    report = RecallCounter.report
 
 
 def load_features(path_without_ext: str, fmt: str = 'npy', dtype=np.float32):
@@ -205,6 +294,18 @@ class GroundingEvaluator:
             t, m = model_.encode_text(tok, m)
             texts.append(t)
             tmasks.append(m)
+        bank = data.get('bank') if isinstance(data, dict) else None
+        if bank is not None:
+            # an item of data.EvalBank: the features never left the GPU.  The padded windows and the mask are one ragged transpose
+            # each (dcf_op_assemble_rows) out of the bank, the tokens and text_cls are views of it; nothing is uploaded
+            if bank.vid_stride != self.vid_stride:
+                raise ValueError(f'the EvalBank was filled for vid_stride {bank.vid_stride}, the model has {self.vid_stride}')
+            if self.feature_dtype is not None and bank.data['vid'].dtype != self.feature_dtype:
+                raise ValueError(f"feature_dtype='float16' rounds host features; the EvalBank holds {bank.data['vid'].dtype} as stored")
+            T = padded_length(data['vid_len'], self.max_vid_len, self.num_fpn_levels, self.mha_win_size, self.vid_stride)
+            window, shallow_window, mask = bank.windows(data['clip_id'], T)
+            self.time_dict['prepare'].append(time.perf_counter() - t0)
+            return (window, shallow_window, mask, tuple(texts), data['text_cls'], tuple(tmasks)), T, None
         vid, shallow = data['vid'], data['shallow_vid']
         if self.feature_dtype is not None:
             name = data.get('clip_id', '?') if isinstance(data, dict) else '?'
@@ -321,14 +422,98 @@ class GroundingEvaluator:
         """Evaluator.run (worker_v2.py:815-910) over an iterable of per-video dicts (keys as in
         libs/data/dataset.py:977-994: vid, shallow_vid, text, text_cls, segment, fps, clip_stride, clip_size, duration).
         ``batch_videos > 1``: consecutive videos of the same padded length (every video up to max_vid_len is one) share a
-        forward (``model.forward_videos``); same proposals, fewer and larger kernel launches."""
+        forward (``model.forward_videos``); same proposals, fewer and larger kernel launches.
+        ``counter``: a ``DeviceRecallCounter`` takes the device route (``_run_on_device``): forward, collect_segments, batched NMS and
+        dcf_op_recall_update are enqueued per video, in each of the three modes, and nothing is waited for before the counter is read;
+        ``dataset`` may then be a ``data.EvalBank``, whose videos never leave the GPU."""
         self._own_carry()
         try:
             return self._run(dataset, counter, n_streams, batch_videos)
         finally:
             self._own_carry(False)
 
+    # ---- the device route: nothing is waited for per video ---------------------------------------------------------------------
+    def _count_on_device(self, flat, T, data, window_ext, counter):
+        """collect_segments + batched NMS + dcf_op_recall_update for every query of a video, enqueued on the current stream: no
+        pinned copy, no event, no result list"""
+        logits, offsets, masks = flat
+        assert window_ext is None or self.vid_stride == 1, 'ext_scores are per input clip: the reference multiplies them at level 0 (worker_v2.py:1150-1156)'
+        segs, scores, counts = _nms.collect_segments(logits, offsets, masks, T // self.vid_stride, self.num_fpn_levels, self.pre_nms_thresh,
+                                                     self.pre_nms_topk, self.seg_len_thresh, ext_scores=window_ext)
+        nq = segs.shape[0]
+        if self.nms_cfg.get('max_num_segs', 0) <= 0:    # keeps nothing (nms.py:144-146): every query is a miss
+            counter.add_misses(nq)
+            return
+        s_all, _, k_all = _nms.batched_nms_queries(segs, scores, counts, **self.nms_cfg)
+        meta = data.get('meta')
+        if meta is None:                                # a host sample: its 32 bytes per query are the one upload
+            meta = torch.from_numpy(query_meta(data['segment'], self.vid_stride, data['clip_stride'], data['clip_size'], data['fps'],
+                                               data['duration'])).to(s_all.device, non_blocking=True)
+        if meta.shape[0] != nq:
+            raise ValueError(f'{nq} queries for {meta.shape[0]} ground-truth segments')
+        counter.update_device(s_all, k_all, meta)
+
+    def _pass_on_device(self, dataset, counter, n_streams, batch_videos):
+        """one pass over the dataset in the mode ``run`` was asked for -> the models that ran"""
+        if batch_videos > 1:
+            pending = []                              # (data, args, T, ext)
+
+            def flush():
+                if not pending:
+                    return
+                T = pending[0][2]
+                self.model.forward_videos([p[1] for p in pending])
+                logits, offsets, masks = self.model._last_flat
+                q = 0
+                for data, args, _, ext in pending:
+                    n = len(args[3])
+                    self._count_on_device((logits[q:q + n], offsets[q:q + n], masks[q:q + n]), T, data, ext, counter)
+                    q += n
+                pending.clear()
+
+            for data in dataset:
+                args, T, ext = self.prepare(data)
+                if pending and (pending[0][2] != T or len(pending) == batch_videos):
+                    flush()
+                pending.append((data, args, T, ext))
+            flush()
+            return [self.model]
+        if n_streams <= 1:
+            for data in dataset:
+                flat, T = self.forward(data)
+                self._count_on_device(flat, T, data, self._window_ext, counter)
+            return [self.model]
+        # one model replica and one HIP stream per lane; the lanes share the counter (integer atomics), and the caller's stream waits
+        # for every lane at the end -- on the device, not on the host
+        lanes = [(self.model if i == 0 else self.model.replica(), torch.cuda.Stream()) for i in range(n_streams)]
+        main = torch.cuda.current_stream()
+        for _, stream in lanes:
+            stream.wait_stream(main)                  # behind the counter's reset and whatever made the weights
+        for i, data in enumerate(dataset):
+            mdl, stream = lanes[i % n_streams]
+            with torch.cuda.stream(stream):
+                flat, T = self.forward(data, mdl)
+                self._count_on_device(flat, T, data, self._window_ext, counter)
+        for _, stream in lanes:
+            main.wait_stream(stream)
+        return [m for m, _ in lanes]
+
+    def _run_on_device(self, dataset, counter, n_streams, batch_videos):
+        """``run`` with a ``DeviceRecallCounter``.  The one-pass LayerNorm guard cannot be polled per video without a wait: it is
+        checked once after the last video, and if it tripped the models run two-pass launches from then on, the counter is reset and
+        the whole pass is repeated once."""
+        if iter(dataset) is dataset:
+            raise TypeError('run(counter=DeviceRecallCounter): the dataset is an iterator; the pass may have to be repeated, hand over an iterable')
+        models = self._pass_on_device(dataset, counter, n_streams, batch_videos)
+        if self._carry_tripped(models):
+            counter.reset()
+            models = self._pass_on_device(dataset, counter, n_streams, batch_videos)
+        self._check_numerics(models)
+        return counter
+
     def _run(self, dataset, counter, n_streams, batch_videos):
+        if isinstance(counter, DeviceRecallCounter):
+            return self._run_on_device(dataset, counter, n_streams, batch_videos)
         counter = counter or RecallCounter(self.opt['eval'].get('ranks', (1, 5)), self.opt['eval'].get('iou_threshs', (0.3, 0.5)))
         if batch_videos > 1:
             pending = []                              # (data, args, T, ext)

@@ -41,7 +41,12 @@ Data.  ``data.TrainLoader`` finds the step's batches: the reference's sampling d
 the features in a device-resident ``data.FeatureBank``, a batch assembled by dcf_op_assemble_rows (include/decafnet_hip_batch.h).
 ``run_epoch(ts, loader, epoch)`` is the loop body of ``Trainer.run`` (worker_v2.py:309-325) on them.
 
-Not here: logging, AMP, graph capture of the step, SGD, gradient compression, the detection of parameters that no
+The run.  ``fit(ts, loader, root, ...)`` is ``Trainer.run`` itself: ``run_epoch`` per epoch, ``checkpoint`` where the reference
+checkpoints (``models/last.pth``, ``models/{epoch}-{itr}.pth``, ``states/last.pth``) and, every ``eval_run`` epochs or iterations, the
+EMA copy evaluated on the validation split -- from a ``data.EvalBank`` with an ``evaluator.DeviceRecallCounter`` (dcf_op_recall_update,
+include/decafnet_hip_eval.h) without a host read per video -- and resuming from the two ``last.pth`` files.
+
+Not here: logging, the validation loss, AMP, graph capture of the step, SGD, gradient compression, the detection of parameters that no
 rank used.
 
 The front end.  ``training_forward(..., front_end='dense')`` makes the network's input as the reference does: the features of a video
@@ -55,6 +60,7 @@ path alone, whatever ``front_end`` says: the score channel is a rank-1 term ther
 training branch, model.py:606-612, never reads it), and so does ``cdrop``: a per-sample channel mask cannot share products.
 """
 import copy
+import os
 
 import torch
 
@@ -302,6 +308,89 @@ def run_epoch(ts, loader, epoch=None):
     ts.epoch = epoch + 1
     sums['steps'] = steps
     return sums
+
+
+EVAL_BY = ('epoch', 'itr')
+
+
+def checkpoint(ts, root):
+    """Trainer.checkpoint (worker_v2.py:675-692) from ``ts.state()``: ``<root>/models/last.pth`` and ``models/{epoch}-{itr}.pth``
+    ({'model', 'model_ema'}) and ``<root>/states/last.pth`` ({'optimizer', 'scheduler', 'epoch', 'itr'} plus the additions
+    ``TrainStep.state`` documents).  -> the three paths.  The layout ``GroundingEvaluator.from_checkpoint`` reads."""
+    model_ckpt, state_ckpt = ts.state()
+    model_dir, state_dir = os.path.join(root, 'models'), os.path.join(root, 'states')
+    os.makedirs(model_dir, exist_ok=True)
+    os.makedirs(state_dir, exist_ok=True)
+    paths = (os.path.join(model_dir, 'last.pth'), os.path.join(model_dir, f'{ts.epoch}-{ts.itr}.pth'), os.path.join(state_dir, 'last.pth'))
+    torch.save(model_ckpt, paths[0])
+    torch.save(model_ckpt, paths[1])
+    torch.save(state_ckpt, paths[2])
+    return paths
+
+
+def evaluate(ts, evaluator, eval_data, counter=None):
+    """The EMA copy (``ts.ema.module``: its own module, in eval mode, with an engine of its own) through ``evaluator`` on ``eval_data``
+    -> the counter.  A ``data.EvalBank`` without a counter gets an ``evaluator.DeviceRecallCounter``: the pass then reads nothing back
+    before the counter's accessors.  The training model, its mode, its dropout generator and its engines are not touched; the
+    evaluator's own model is put back afterwards."""
+    from . import data as _data, evaluator as E
+    opt_eval = ts.opt['eval']
+    if counter is None:
+        ranks, threshs = opt_eval.get('ranks', (1, 5)), opt_eval.get('iou_threshs', (0.3, 0.5))
+        dev = next(ts.ema.module.parameters()).device
+        counter = E.DeviceRecallCounter(ranks, threshs, dev) if isinstance(eval_data, _data.EvalBank) else E.RecallCounter(ranks, threshs)
+    ev = evaluator if evaluator is not None else E.GroundingEvaluator(ts.opt, ts.ema.module)
+    own, ev.model = ev.model, ts.ema.module
+    try:
+        return ev.run(eval_data, counter=counter)
+    finally:
+        ev.model = own
+
+
+def fit(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_by='epoch', eval_run=0, resume=True):
+    """``Trainer.run`` (worker_v2.py:307-364) with its checkpoints and evaluations, without its logging: ``run_epoch`` per epoch until
+    ``ts.epoch`` reaches ``num_epochs`` (None: ``opt.train.epochs``).  Where the reference calls ``evaluate(ct)`` -- after every epoch
+    with ``eval_by='epoch'`` (ct = the epoch count), after every iteration divisible by ``eval_run`` with ``eval_by='itr'`` (the step
+    loop is written out for it; ct = ``ts.itr``) -- ``checkpoint(ts, root)`` runs, and when ``eval_run > 0`` and ct is divisible by it
+    the EMA copy is evaluated on ``eval_data`` (``evaluate`` above) and ``counter.report()`` goes to ``<root>/eval_{epoch}_{itr}.txt``.
+    ``eval_run=0``: checkpoints per epoch, no evaluation (``eval_by='itr'`` then never checkpoints: the reference divides by it).
+    ``resume=True``: when ``models/last.pth`` and ``states/last.pth`` both exist they are loaded first (train.py:66-69) and the loop
+    continues at ``ts.epoch``; a checkpoint taken inside an epoch restarts that epoch, as in the reference.  The data loader's
+    random streams are not part of a checkpoint.  -> [(epoch, itr, metrics)] of the evaluations.
+    Not here: the validation loss, W&B and loss meters, more than one rank (NotImplementedError before anything is launched)."""
+    if getattr(ts, 'world', 1) > 1:
+        raise NotImplementedError(f'fit: a DataParallelTrainStep of world {ts.world} is not implemented: checkpoints and the evaluation '
+                                  f'belong to rank 0 and need a barrier')
+    if eval_by not in EVAL_BY:
+        raise ValueError(f'fit: eval_by = {eval_by!r} (one of {EVAL_BY})')
+    eval_run = int(eval_run)
+    if eval_run < 0 or (eval_run > 0 and eval_data is None):
+        raise ValueError(f'fit: eval_run = {eval_run} needs eval_run >= 0 and, to evaluate, eval_data')
+    num_epochs = int(ts.opt['train']['epochs'] if num_epochs is None else num_epochs)
+    last = os.path.join(root, 'models', 'last.pth'), os.path.join(root, 'states', 'last.pth')
+    if resume and all(os.path.exists(p) for p in last):
+        ts.load_state(*(torch.load(p, map_location='cpu', weights_only=False) for p in last))
+    results = []
+
+    def evaluate_at(ct):
+        checkpoint(ts, root)
+        if eval_run > 0 and ct % eval_run == 0:
+            counter = evaluate(ts, evaluator, eval_data)
+            with open(os.path.join(root, f'eval_{ts.epoch}_{ts.itr}.txt'), 'w') as fh:
+                fh.write(counter.report())
+            results.append((ts.epoch, ts.itr, counter.metrics()))
+
+    while ts.epoch < num_epochs:
+        if eval_by == 'itr':
+            for batch, targets in loader.epoch(ts.epoch):
+                ts.step(batch, targets)
+                if eval_run > 0 and ts.itr % eval_run == 0:          # worker_v2.py:340
+                    evaluate_at(ts.itr)
+            ts.epoch += 1
+        else:
+            run_epoch(ts, loader)
+            evaluate_at(ts.epoch)                                    # worker_v2.py:345-347
+    return results
 
 
 class DataParallelTrainStep(TrainStep):
