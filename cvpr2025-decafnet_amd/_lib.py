@@ -291,6 +291,24 @@ STAGED = (
 )
 
 
+# the multi-rank-fit extension (include/decafnet_hip_fit.h, csrc/fit.hip).  ``rows`` fp32, ``offsets`` int64, ``per_video`` / ``out2``
+# float64 and ``slot`` fp32 are device memory; ``state`` is the dcf_guard_state of the ARMED guard.
+GUARD_REMOTE = 0x100          # DCF_GUARD_REMOTE: the bit of the conv-gradient word that says "raised on some rank"
+FIT_TABLE = {
+    'dcf_fit_ext_version': (i32, []),
+    'dcf_op_loss_table_mean': (i32, [c_f32p, c_i64p, i32, c_f64p, c_f64p, vp]),
+    'dcf_guard_word_publish': (i32, [vp, c_f32p, vp]),
+    'dcf_guard_word_merge': (i32, [vp, c_f32p, vp]),
+}
+
+
+# Bound by lib() after STAGED and waiting for the same follow-up: registration at the end of EXTENSIONS together with a
+# ``borders.TABLE`` row (the cases are tests/fit_abi_cases.py, run through the same driver by tests/test_gpu_loss_table.py).
+FIT = (
+    Extension('fit', 'decafnet_hip_fit.h', 'dcf_fit_ext_version', 1, 'DCF_FIT_EXT_VERSION', ('decafnet_hip.h', 'decafnet_hip_guard.h'), FIT_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -302,10 +320,10 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS + PENDING + STAGED:
+        for ext in EXTENSIONS + PENDING + STAGED + FIT:
             for name, (res, args) in ext.table.items():
                 if name in bound:
-                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED')
+                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED / _lib.FIT')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

@@ -196,6 +196,15 @@ class VideoCentricEvalData:
                     clip_size=self.clip_size, clip_stride=self.clip_stride, clip_id=vid_id, text_id=tuple(range(n)),
                     vid=vid, shallow_vid=shallow, text=text, text_cls=text_cls, ext_scores=ext)
 
+    def targets(self, vid_id: str, vid_stride: int = 1):
+        """The ground truth of the video's queries on the feature grid, as ``Evaluator._calc_loss`` sees it: (n, 2) float32.
+        clip(seg * fps, 0, num_frames) / clip_stride - 0.5 * clip_size / clip_stride in float64, stored as float32
+        (dataset.py:706-712), then divided by ``vid_stride`` in float32 (worker_v2.py:1037).  ``sample`` does not carry it."""
+        v = self.videos[vid_id]
+        seg = np.asarray(v['segments'], dtype=np.float64).reshape(-1, 2)
+        seg = np.clip(seg * v['fps'], a_min=0, a_max=v['num_frames']) / self.clip_stride - 0.5 * self.clip_size / self.clip_stride
+        return torch.from_numpy(np.ascontiguousarray(seg.astype(np.float32))) / vid_stride
+
     def __iter__(self) -> Iterator[dict]:
         for vid_id in self.videos:
             yield self.sample(vid_id)
@@ -621,6 +630,39 @@ class EvalBank:
     def __iter__(self):
         for vid_id in self.index:
             yield self.item(vid_id)
+
+    @property
+    def targets(self):
+        """(N_queries, 2) fp32 on the device, in query order: ``eval_data.targets(vid_id, vid_stride)`` of every video, what the
+        validation loss is computed against (``evaluator.DeviceLossMeter``).  Made at the first use and kept; 8 bytes per query that
+        ``nbytes`` does not count."""
+        if getattr(self, '_targets', None) is None:
+            rows = [self.eval_data.targets(vid_id, self.vid_stride) for vid_id in self.index]
+            self._targets = torch.cat(rows).to(self.device)
+        return self._targets
+
+    def subset(self, indices):
+        """An iterable view of the videos at ``indices`` (positions in the bank's order, each at most once), in the order given: the
+        same item dicts, nothing copied.  What a rank evaluates of a sharded validation set (``train.fit_parallel``)."""
+        return EvalBankSubset(self, indices)
+
+
+class EvalBankSubset:
+    """``EvalBank.subset``: iterating yields ``bank.item`` of the chosen videos, with the keys ``EvalBank`` yields and no other."""
+
+    def __init__(self, bank, indices):
+        ids = list(bank.index)
+        idx = [int(i) for i in indices]
+        if any(i != j for i, j in zip(idx, indices)) or any(not 0 <= i < len(ids) for i in idx) or len(set(idx)) != len(idx):
+            raise ValueError(f'EvalBank.subset: indices {list(indices)} must be distinct integers in [0, {len(ids)})')
+        self.bank, self.indices, self._ids = bank, tuple(idx), [ids[i] for i in idx]
+
+    def __len__(self):
+        return len(self._ids)
+
+    def __iter__(self):
+        for vid_id in self._ids:
+            yield self.bank.item(vid_id)
 
 
 class TrainLoader:

@@ -167,6 +167,93 @@ class DeviceRecallCounter:
     report = RecallCounter.report
 
 
+LOSS_KEYS = ('cls_loss', 'reg_loss')
+
+
+class DeviceLossMeter:
+    """The validation loss ``Evaluator.run`` logs (worker_v2.py:856, 903-906: ``_calc_loss`` per video, then the mean over the videos)
+    without a host read per video.  Holds, on the bank's device, ``rows`` (N_queries, 4) fp32, zeroed -- one row (focal1, focal2, iou,
+    n_pos) per query, in the bank's query order --, ``offsets`` (V + 1) int64 from ``bank.queries`` and ``bank.targets``.
+
+    ``update_device(flat, T, data)`` is ONE dcf_point_objective call on what the evaluation forward left on the device, with the
+    parameters of ``calc_loss`` (one classification head, alpha 0.5, smoothing 0.2, GIoU, centre sampling from ``opt.train``), whose
+    ``rows_out`` is the video's slice of the table.  Videos own disjoint slices: lanes on several streams and several ranks fill one
+    table without atomics, and a sum of the ranks' tables adds zeros, which is exact.  ``losses()`` is one launch of
+    dcf_op_loss_table_mean (include/decafnet_hip_fit.h) and one 16-byte read.
+
+    ``opt``: the ``config.make_opt`` tree; None: ``GroundingEvaluator.run`` hands over its own at the first pass."""
+
+    def __init__(self, bank, opt=None):
+        if bank.device.type != 'cuda':
+            raise RuntimeError('DeviceLossMeter computes on the MI355X only: calc_loss per video is the host route')
+        self.bank, self.device, self.opt = bank, bank.device, opt
+        ends = np.cumsum([0] + [nq for _, nq in (bank.queries[k] for k in bank.index)])
+        if [q0 for q0, _ in (bank.queries[k] for k in bank.index)] != ends[:-1].tolist():
+            raise ValueError('DeviceLossMeter: bank.queries is not the bank\'s videos back to back')
+        self.offsets = torch.from_numpy(ends.astype(np.int64)).to(self.device)
+        self.targets = bank.targets
+        self.rows = torch.zeros(int(ends[-1]), 4, dtype=torch.float32, device=self.device)
+        self._out = torch.empty(2, dtype=torch.float64, device=self.device)
+
+    def use(self, opt):
+        """take ``opt`` where the meter was made without one"""
+        if self.opt is None:
+            self.opt = opt
+        return self
+
+    def reset(self):
+        self.rows.zero_()
+        return self
+
+    def update_device(self, flat, T, data):
+        """``flat``: (logits (nq, S), offsets (nq, S, 2), masks (nq, S)) of the video's queries as the evaluation forward leaves them,
+        ``T`` the padded input length, ``data`` the video's item of the bank.  No host wait.  Refused before the launch, with the
+        video's name: what dcf_point_objective would refuse (``T // vid_stride`` beyond pt_gen's max_seq_len or no pyramid)."""
+        from . import _lib
+        if self.opt is None:
+            raise ValueError('DeviceLossMeter: no opt (DeviceLossMeter(bank, opt), or hand the meter to GroundingEvaluator.run)')
+        logits, offsets, masks = flat
+        name = data['clip_id']
+        q0, nq = self.bank.queries[name]
+        mo, tr = self.opt['model'], self.opt['train']
+        (rr, sigma, msl), use_offset = _loss.pt_gen_params(self.opt)
+        Tp, L = T // int(mo.get('vid_stride', 1)), int(mo['num_fpn_levels'])
+        S = sum(Tp >> l for l in range(L))
+        if Tp > msl:
+            raise ValueError(f'video {name}: T // vid_stride = {Tp} points at level 0, pt_gen.max_seq_len is {msl}: dcf_point_objective '
+                             f'refuses the layout')
+        if not 1 <= L <= 16 or Tp < 1 or Tp >= 1 << 23 or Tp % (1 << (L - 1)):
+            raise ValueError(f'video {name}: T // vid_stride = {Tp} with {L} levels is not a PtGenerator layout')
+        if logits.shape != (nq, S) or offsets.shape != (nq, S, 2) or masks.shape != (nq, S):
+            raise ValueError(f'video {name}: logits {tuple(logits.shape)}, offsets {tuple(offsets.shape)}, masks {tuple(masks.shape)} for '
+                             f'{nq} queries of {S} points')
+        if logits.dtype != torch.float32 or offsets.dtype != torch.float32 or masks.dtype != torch.bool or \
+                not (logits.is_contiguous() and offsets.is_contiguous() and masks.is_contiguous()) or logits.device != self.rows.device:
+            raise ValueError(f'video {name}: the forward\'s outputs are contiguous fp32 / bool tensors on {self.device}')
+        if nq == 0:
+            return
+        _lib.check(_lib.lib().dcf_point_objective(
+            None, _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks), _lib.ptr(self.targets[q0:q0 + nq]), nq, Tp, L, rr, sigma,
+            int(use_offset), msl, int(tr.get('center_sampling', 'radius') == 'radius'), float(tr['center_sampling_radius']), 0.5, 0.2, 0, 1e-8,
+            None, 1.0, 1.0, _lib.ptr(self.rows[q0:q0 + nq]), None, _lib.current_stream()), 'dcf_point_objective')
+
+    def losses(self, per_video=False):
+        """-> {'cls_loss', 'reg_loss'} as Python floats: one launch, one 16-byte read that waits for the current stream.
+        ``per_video=True``: -> (that, the (V, 2) float64 array of the per-video means), a second read."""
+        from . import _lib
+        pv = torch.empty(len(self.offsets) - 1, 2, dtype=torch.float64, device=self.device) if per_video else None
+        _lib.check(_lib.lib().dcf_op_loss_table_mean(_lib.ptr(self.rows), _lib.ptr(self.offsets), len(self.offsets) - 1, _lib.ptr(pv),
+                                                     _lib.ptr(self._out), _lib.current_stream()), 'dcf_op_loss_table_mean')
+        out = self._out.cpu()                          # the one host read
+        stats = {k: float(out[i]) for i, k in enumerate(LOSS_KEYS)}
+        return (stats, pv.cpu().numpy()) if per_video else stats
+
+    @staticmethod
+    def line(stats):
+        """the loss line of the evaluation report (worker_v2.py:903-906)"""
+        return ''.join(f'{k}: {v:.3f}; ' for k, v in stats.items())
+
+
 def load_features(path_without_ext: str, fmt: str = 'npy', dtype=np.float32):
     """One feature file as the reference stores it ((T, C) on disk: npy / pt / pk0 / pk1 / pk_avg, libs/data/dataset.py:107-135)
     returned channel-major (C, T) like ``_load_vid_feats`` (:398-399).  Multi-source videos: ``data.load_video_features``.
@@ -418,25 +505,33 @@ class GroundingEvaluator:
             self._check_numerics([self.model])
         return res
 
-    def run(self, dataset, counter: RecallCounter = None, n_streams: int = 1, batch_videos: int = 1):
+    def run(self, dataset, counter: RecallCounter = None, n_streams: int = 1, batch_videos: int = 1, loss_meter=None):
         """Evaluator.run (worker_v2.py:815-910) over an iterable of per-video dicts (keys as in
         libs/data/dataset.py:977-994: vid, shallow_vid, text, text_cls, segment, fps, clip_stride, clip_size, duration).
         ``batch_videos > 1``: consecutive videos of the same padded length (every video up to max_vid_len is one) share a
         forward (``model.forward_videos``); same proposals, fewer and larger kernel launches.
         ``counter``: a ``DeviceRecallCounter`` takes the device route (``_run_on_device``): forward, collect_segments, batched NMS and
         dcf_op_recall_update are enqueued per video, in each of the three modes, and nothing is waited for before the counter is read;
-        ``dataset`` may then be a ``data.EvalBank``, whose videos never leave the GPU."""
+        ``dataset`` may then be a ``data.EvalBank``, whose videos never leave the GPU.
+        ``loss_meter``: a ``DeviceLossMeter`` of the bank the videos come from; on the device route, in each of the three modes, every
+        video's forward is followed by ``loss_meter.update_device`` beside the counting.  The host route refuses it (ValueError:
+        ``calc_loss`` per video is the host's validation loss)."""
+        if loss_meter is not None and not isinstance(counter, DeviceRecallCounter):
+            raise ValueError('run(loss_meter=...): the meter fills its table on the device route, run(counter=DeviceRecallCounter(...)); '
+                             'calc_loss per video is the host route')
         self._own_carry()
         try:
-            return self._run(dataset, counter, n_streams, batch_videos)
+            return self._run(dataset, counter, n_streams, batch_videos, loss_meter)
         finally:
             self._own_carry(False)
 
     # ---- the device route: nothing is waited for per video ---------------------------------------------------------------------
-    def _count_on_device(self, flat, T, data, window_ext, counter):
+    def _count_on_device(self, flat, T, data, window_ext, counter, loss_meter=None):
         """collect_segments + batched NMS + dcf_op_recall_update for every query of a video, enqueued on the current stream: no
-        pinned copy, no event, no result list"""
+        pinned copy, no event, no result list; with a ``loss_meter`` the video's rows of the validation loss first"""
         logits, offsets, masks = flat
+        if loss_meter is not None:
+            loss_meter.update_device(flat, T, data)
         assert window_ext is None or self.vid_stride == 1, 'ext_scores are per input clip: the reference multiplies them at level 0 (worker_v2.py:1150-1156)'
         segs, scores, counts = _nms.collect_segments(logits, offsets, masks, T // self.vid_stride, self.num_fpn_levels, self.pre_nms_thresh,
                                                      self.pre_nms_topk, self.seg_len_thresh, ext_scores=window_ext)
@@ -453,7 +548,7 @@ class GroundingEvaluator:
             raise ValueError(f'{nq} queries for {meta.shape[0]} ground-truth segments')
         counter.update_device(s_all, k_all, meta)
 
-    def _pass_on_device(self, dataset, counter, n_streams, batch_videos):
+    def _pass_on_device(self, dataset, counter, n_streams, batch_videos, loss_meter=None):
         """one pass over the dataset in the mode ``run`` was asked for -> the models that ran"""
         if batch_videos > 1:
             pending = []                              # (data, args, T, ext)
@@ -467,7 +562,7 @@ class GroundingEvaluator:
                 q = 0
                 for data, args, _, ext in pending:
                     n = len(args[3])
-                    self._count_on_device((logits[q:q + n], offsets[q:q + n], masks[q:q + n]), T, data, ext, counter)
+                    self._count_on_device((logits[q:q + n], offsets[q:q + n], masks[q:q + n]), T, data, ext, counter, loss_meter)
                     q += n
                 pending.clear()
 
@@ -481,7 +576,7 @@ class GroundingEvaluator:
         if n_streams <= 1:
             for data in dataset:
                 flat, T = self.forward(data)
-                self._count_on_device(flat, T, data, self._window_ext, counter)
+                self._count_on_device(flat, T, data, self._window_ext, counter, loss_meter)
             return [self.model]
         # one model replica and one HIP stream per lane; the lanes share the counter (integer atomics), and the caller's stream waits
         # for every lane at the end -- on the device, not on the host
@@ -493,27 +588,31 @@ class GroundingEvaluator:
             mdl, stream = lanes[i % n_streams]
             with torch.cuda.stream(stream):
                 flat, T = self.forward(data, mdl)
-                self._count_on_device(flat, T, data, self._window_ext, counter)
+                self._count_on_device(flat, T, data, self._window_ext, counter, loss_meter)
         for _, stream in lanes:
             main.wait_stream(stream)
         return [m for m, _ in lanes]
 
-    def _run_on_device(self, dataset, counter, n_streams, batch_videos):
+    def _run_on_device(self, dataset, counter, n_streams, batch_videos, loss_meter=None):
         """``run`` with a ``DeviceRecallCounter``.  The one-pass LayerNorm guard cannot be polled per video without a wait: it is
-        checked once after the last video, and if it tripped the models run two-pass launches from then on, the counter is reset and
-        the whole pass is repeated once."""
+        checked once after the last video, and if it tripped the models run two-pass launches from then on, the counter (and the loss
+        meter) is reset and the whole pass is repeated once."""
         if iter(dataset) is dataset:
             raise TypeError('run(counter=DeviceRecallCounter): the dataset is an iterator; the pass may have to be repeated, hand over an iterable')
-        models = self._pass_on_device(dataset, counter, n_streams, batch_videos)
+        if loss_meter is not None:
+            loss_meter.use(self.opt)
+        models = self._pass_on_device(dataset, counter, n_streams, batch_videos, loss_meter)
         if self._carry_tripped(models):
             counter.reset()
-            models = self._pass_on_device(dataset, counter, n_streams, batch_videos)
+            if loss_meter is not None:
+                loss_meter.reset()
+            models = self._pass_on_device(dataset, counter, n_streams, batch_videos, loss_meter)
         self._check_numerics(models)
         return counter
 
-    def _run(self, dataset, counter, n_streams, batch_videos):
+    def _run(self, dataset, counter, n_streams, batch_videos, loss_meter=None):
         if isinstance(counter, DeviceRecallCounter):
-            return self._run_on_device(dataset, counter, n_streams, batch_videos)
+            return self._run_on_device(dataset, counter, n_streams, batch_videos, loss_meter)
         counter = counter or RecallCounter(self.opt['eval'].get('ranks', (1, 5)), self.opt['eval'].get('iou_threshs', (0.3, 0.5)))
         if batch_videos > 1:
             pending = []                              # (data, args, T, ext)

@@ -44,9 +44,12 @@ the features in a device-resident ``data.FeatureBank``, a batch assembled by dcf
 The run.  ``fit(ts, loader, root, ...)`` is ``Trainer.run`` itself: ``run_epoch`` per epoch, ``checkpoint`` where the reference
 checkpoints (``models/last.pth``, ``models/{epoch}-{itr}.pth``, ``states/last.pth``) and, every ``eval_run`` epochs or iterations, the
 EMA copy evaluated on the validation split -- from a ``data.EvalBank`` with an ``evaluator.DeviceRecallCounter`` (dcf_op_recall_update,
-include/decafnet_hip_eval.h) without a host read per video -- and resuming from the two ``last.pth`` files.
+include/decafnet_hip_eval.h) without a host read per video -- and resuming from the two ``last.pth`` files.  ``fit_parallel`` is the same
+loop on a process group: rank 0 checkpoints, every rank evaluates its share of the bank and the tables are summed over the ranks, the
+validation loss comes from an ``evaluator.DeviceLossMeter`` (dcf_op_loss_table_mean, include/decafnet_hip_fit.h), and
+``DataParallelTrainStep(..., agree_skips=True)`` keeps the ranks' skips equal.
 
-Not here: logging, the validation loss, AMP, graph capture of the step, SGD, gradient compression, the detection of parameters that no
+Not here: logging, AMP, graph capture of the step, SGD, gradient compression, the detection of parameters that no
 rank used.
 
 The front end.  ``training_forward(..., front_end='dense')`` makes the network's input as the reference does: the features of a video
@@ -61,6 +64,7 @@ training branch, model.py:606-612, never reads it), and so does ``cdrop``: a per
 """
 import copy
 import os
+from collections import namedtuple
 
 import torch
 
@@ -328,21 +332,23 @@ def checkpoint(ts, root):
     return paths
 
 
-def evaluate(ts, evaluator, eval_data, counter=None):
+def evaluate(ts, evaluator, eval_data, counter=None, meter=None):
     """The EMA copy (``ts.ema.module``: its own module, in eval mode, with an engine of its own) through ``evaluator`` on ``eval_data``
-    -> the counter.  A ``data.EvalBank`` without a counter gets an ``evaluator.DeviceRecallCounter``: the pass then reads nothing back
-    before the counter's accessors.  The training model, its mode, its dropout generator and its engines are not touched; the
-    evaluator's own model is put back afterwards."""
+    -> the counter.  A ``data.EvalBank`` (or a ``subset`` of one) without a counter gets an ``evaluator.DeviceRecallCounter``: the pass
+    then reads nothing back before the counter's accessors.  ``meter``: an ``evaluator.DeviceLossMeter`` of that bank, filled beside
+    the counter (``GroundingEvaluator.run(loss_meter=)``).  The training model, its mode, its dropout generator and its engines are
+    not touched; the evaluator's own model is put back afterwards."""
     from . import data as _data, evaluator as E
     opt_eval = ts.opt['eval']
     if counter is None:
         ranks, threshs = opt_eval.get('ranks', (1, 5)), opt_eval.get('iou_threshs', (0.3, 0.5))
         dev = next(ts.ema.module.parameters()).device
-        counter = E.DeviceRecallCounter(ranks, threshs, dev) if isinstance(eval_data, _data.EvalBank) else E.RecallCounter(ranks, threshs)
+        banked = isinstance(eval_data, (_data.EvalBank, _data.EvalBankSubset))
+        counter = E.DeviceRecallCounter(ranks, threshs, dev) if banked else E.RecallCounter(ranks, threshs)
     ev = evaluator if evaluator is not None else E.GroundingEvaluator(ts.opt, ts.ema.module)
     own, ev.model = ev.model, ts.ema.module
     try:
-        return ev.run(eval_data, counter=counter)
+        return ev.run(eval_data, counter=counter) if meter is None else ev.run(eval_data, counter=counter, loss_meter=meter)
     finally:
         ev.model = own
 
@@ -357,19 +363,13 @@ def fit(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_
     ``resume=True``: when ``models/last.pth`` and ``states/last.pth`` both exist they are loaded first (train.py:66-69) and the loop
     continues at ``ts.epoch``; a checkpoint taken inside an epoch restarts that epoch, as in the reference.  The data loader's
     random streams are not part of a checkpoint.  -> [(epoch, itr, metrics)] of the evaluations.
-    Not here: the validation loss, W&B and loss meters, more than one rank (NotImplementedError before anything is launched)."""
+    Not here: the validation loss, W&B and loss meters, more than one rank (NotImplementedError before anything is launched;
+    ``fit_parallel`` is the loop for those)."""
     if getattr(ts, 'world', 1) > 1:
         raise NotImplementedError(f'fit: a DataParallelTrainStep of world {ts.world} is not implemented: checkpoints and the evaluation '
-                                  f'belong to rank 0 and need a barrier')
-    if eval_by not in EVAL_BY:
-        raise ValueError(f'fit: eval_by = {eval_by!r} (one of {EVAL_BY})')
-    eval_run = int(eval_run)
-    if eval_run < 0 or (eval_run > 0 and eval_data is None):
-        raise ValueError(f'fit: eval_run = {eval_run} needs eval_run >= 0 and, to evaluate, eval_data')
-    num_epochs = int(ts.opt['train']['epochs'] if num_epochs is None else num_epochs)
-    last = os.path.join(root, 'models', 'last.pth'), os.path.join(root, 'states', 'last.pth')
-    if resume and all(os.path.exists(p) for p in last):
-        ts.load_state(*(torch.load(p, map_location='cpu', weights_only=False) for p in last))
+                                  f'belong to rank 0 and need a barrier (train.fit_parallel is the loop for a process group)')
+    eval_run = _fit_arguments('fit', eval_by, eval_run, eval_data)
+    _resume(ts, root, resume)
     results = []
 
     def evaluate_at(ct):
@@ -380,6 +380,30 @@ def fit(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_
                 fh.write(counter.report())
             results.append((ts.epoch, ts.itr, counter.metrics()))
 
+    _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at)
+    return results
+
+
+def _fit_arguments(who, eval_by, eval_run, eval_data):
+    """the argument checks ``fit`` and ``fit_parallel`` share -> eval_run as an int"""
+    if eval_by not in EVAL_BY:
+        raise ValueError(f'{who}: eval_by = {eval_by!r} (one of {EVAL_BY})')
+    eval_run = int(eval_run)
+    if eval_run < 0 or (eval_run > 0 and eval_data is None):
+        raise ValueError(f'{who}: eval_run = {eval_run} needs eval_run >= 0 and, to evaluate, eval_data')
+    return eval_run
+
+
+def _resume(ts, root, resume):
+    """train.py:66-69: both ``last.pth`` files into ``ts`` where both exist and ``resume`` says so"""
+    last = os.path.join(root, 'models', 'last.pth'), os.path.join(root, 'states', 'last.pth')
+    if resume and all(os.path.exists(p) for p in last):
+        ts.load_state(*(torch.load(p, map_location='cpu', weights_only=False) for p in last))
+
+
+def _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at):
+    """the loop of ``Trainer.run`` (worker_v2.py:307-347): ``evaluate_at(ct)`` where the reference calls ``evaluate(ct)``"""
+    num_epochs = int(ts.opt['train']['epochs'] if num_epochs is None else num_epochs)
     while ts.epoch < num_epochs:
         if eval_by == 'itr':
             for batch, targets in loader.epoch(ts.epoch):
@@ -390,6 +414,96 @@ def fit(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_
         else:
             run_epoch(ts, loader)
             evaluate_at(ts.epoch)                                    # worker_v2.py:345-347
+
+
+EvalResult = namedtuple('EvalResult', 'epoch itr metrics loss')
+
+
+def fit_parallel(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_by='epoch', eval_run=0, resume=True,
+                 val_loss=False, eval_shard=True):
+    """``fit`` on a ``TrainStep`` or a ``DataParallelTrainStep`` of any world: ``Trainer.run`` under DistributedDataParallel.  The
+    arguments of ``fit`` and two more.  ``val_loss=True``: every evaluation also computes the validation loss ``Evaluator.run`` logs, on
+    the device (``evaluator.DeviceLossMeter``; ``eval_data`` is then a ``data.EvalBank``).  ``eval_shard``: below.
+    -> [EvalResult(epoch, itr, metrics, loss)], ``loss`` None or {'cls_loss', 'reg_loss'} as Python floats.  The report file is
+    ``counter.report()``, followed with ``val_loss=True`` by the loss line as the reference forms it (worker_v2.py:903-906).
+    With a world-1 step and ``val_loss=False`` the loop launches and writes exactly what ``fit`` does.
+
+    With a world above 1 (``ts.group`` is the process group; every rank calls this with the same arguments):
+      * Refused with ValueError before anything is launched: a ``loader`` whose ``rank`` / ``world_size`` are not those of the group;
+        ``skip_nonfinite=True`` without ``agree_skips=True`` (over many epochs a rank that skips alone parts from the others);
+        ``eval_run > 0`` without ``eval_data``.
+      * Resume: every rank loads both ``last.pth`` files, then a barrier (worker_v2.py:273-275).
+      * Checkpoint: rank 0 alone calls ``ts.state()`` and writes the three files; the other ranks write nothing and read nothing back.
+        Then a barrier, as in ``Trainer.evaluate`` (worker_v2.py:359-364).
+      * ``eval_shard=True``: rank r evaluates the videos ``dist.assign_units(clips per video, world)[r]`` of the ``EvalBank``
+        (``EvalBank.subset``) into its own ``DeviceRecallCounter`` and, with ``val_loss``, its own ``DeviceLossMeter``; the counter's
+        int64 table and the meter's fp32 row table are then each summed over the ranks with ONE all-reduce (``dist._all_reduce_sum``:
+        nccl on the device, gloo staged through the host).  Integer sums are exact and every row of the loss table is non-zero on one
+        rank at most, so every rank holds the tables of one pass over the whole set and returns the same results; rank 0 writes
+        ``eval_{epoch}_{itr}.txt``.  The EMA copies are bit-equal over the ranks, so this is the evaluation of one model.
+      * ``eval_shard=False``: rank 0 evaluates alone and the others wait at the barrier, as the reference does; they return no
+        results.
+      * Every rank issues the same collectives in the same order: the step's own, then a barrier per checkpoint, then at most two
+        all-reduces per evaluation.
+      * The one-pass LayerNorm guard (``GroundingEvaluator._run_on_device``): a rank whose guard trips resets its own counter and meter
+        and repeats its own share before the reduce.  The two-pass repeat therefore covers a share, not the whole set: after a trip
+        the videos of the other shares were evaluated with one-pass launches, and results may differ in the last bits between world
+        sizes.
+
+    Not here: W&B and the training-loss meters, AMP."""
+    from . import data as _data, evaluator as E
+    world = getattr(ts, 'world', 1)
+    group = getattr(ts, 'group', None)
+    eval_run = _fit_arguments('fit_parallel', eval_by, eval_run, eval_data)
+    rank = 0
+    if world > 1:
+        import torch.distributed as dist
+        rank = dist.get_rank(group)
+        if (getattr(loader, 'rank', None), getattr(loader, 'world_size', None)) != (rank, world):
+            raise ValueError(f'fit_parallel: the loader is rank {getattr(loader, "rank", None)} of {getattr(loader, "world_size", None)}, the '
+                             f'step\'s group makes this rank {rank} of {world}: TrainLoader(rank=, world_size=) shards the training data')
+        if ts.skip_nonfinite and not getattr(ts, 'agree_skips', False):
+            raise ValueError('fit_parallel: skip_nonfinite=True on several ranks needs agree_skips=True: the conv-gradient word is '
+                             'rank-local, and a rank that skips alone parts from the others for the rest of the run')
+    sharded = world > 1 and bool(eval_shard)
+    if eval_run > 0 and (val_loss or sharded) and not isinstance(eval_data, _data.EvalBank):
+        raise ValueError(f'fit_parallel: {"val_loss=True" if val_loss else "eval_shard=True"} evaluates a data.EvalBank on the device, '
+                         f'eval_data is {type(eval_data).__name__}')
+    barrier = (lambda: dist.barrier(group)) if world > 1 else (lambda: None)
+    _resume(ts, root, resume)
+    if resume:
+        barrier()                                                    # worker_v2.py:273-275
+    share = eval_data
+    if sharded and eval_run > 0:
+        clips = [eval_data.rows['vid'][k][1] for k in eval_data.index]
+        share = eval_data.subset(D.assign_units(clips, world)[rank])
+    meter = E.DeviceLossMeter(eval_data, ts.opt) if val_loss and eval_run > 0 else None
+    results = []
+
+    def evaluate_at(ct):
+        if rank == 0:
+            checkpoint(ts, root)
+        due = eval_run > 0 and ct % eval_run == 0
+        if due and sharded:                                          # every rank its share, after the checkpoint's barrier
+            barrier()
+            counter = evaluate(ts, evaluator, share, meter=None if meter is None else meter.reset())
+            D._all_reduce_sum(counter._table, group, ts._backend)
+            if meter is not None:
+                D._all_reduce_sum(meter.rows, group, ts._backend)
+            report(counter)
+            return
+        if due and rank == 0:                                        # worker_v2.py:359-364: rank 0 alone, the others wait
+            report(evaluate(ts, evaluator, eval_data, meter=None if meter is None else meter.reset()))
+        barrier()
+
+    def report(counter):
+        loss = None if meter is None else meter.losses()
+        if rank == 0:
+            with open(os.path.join(root, f'eval_{ts.epoch}_{ts.itr}.txt'), 'w') as fh:
+                fh.write(counter.report() + ('' if loss is None else E.DeviceLossMeter.line(loss)))
+        results.append(EvalResult(ts.epoch, ts.itr, counter.metrics(), loss))
+
+    _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at)
     return results
 
 
@@ -417,12 +531,23 @@ class DataParallelTrainStep(TrainStep):
     sits in a gradient of that rank and so in the average, except where a later mask multiplies it away -- then that rank alone would
     skip and the ranks would part.  Equal ``skipped`` counts in ``guard.report()`` of all ranks show that it has not happened.
 
+    ``agree_skips=True`` closes that hole (with ``skip_nonfinite=True`` and a world above 1; otherwise it launches nothing): the
+    loss-norm all-reduce carries two floats instead of one, [norm, flag].  Before it dcf_guard_word_publish writes 1.0 into the flag
+    where this rank's conv-gradient word is set, after it dcf_guard_word_merge ORs ``DCF_GUARD_REMOTE`` into the word where the summed
+    flag is not zero (include/decafnet_hip_fit.h).  The guarded norm that follows then skips on every rank and records the bit in
+    ``conv_flag``.  The number of collectives is unchanged, and so is the norm: a count of positive points, summed as fp32, which is exact
+    below 2^24 points per step over all ranks.  ``False`` -- the default -- launches exactly what
+    was launched before the option existed.
+
     ``device_count=True``: as in ``TrainStep``; every rank keeps its own counts, which agree as long as the verdicts do.
 
     Backends: nccl (RCCL), one GPU per rank; gloo stages every bucket through the host and is a flow check for a one-GPU box."""
 
     def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES, front_end='dense',
-                 skip_nonfinite=False, device_count=False):
+                 skip_nonfinite=False, device_count=False, agree_skips=False):
+        if not isinstance(agree_skips, bool):
+            raise ValueError(f'DataParallelTrainStep: agree_skips = {agree_skips!r} (True or False)')
+        self.agree_skips = agree_skips
         self.group = process_group
         self.world, self._backend = D._group_info(process_group)
         super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch, front_end=front_end,
@@ -442,6 +567,16 @@ class DataParallelTrainStep(TrainStep):
         self.reducer.finalize()
 
     def _norm_over_ranks(self, norm):
+        if self.world > 1 and self.agree_skips and self.guard is not None:
+            # [norm, flag]: the same collective, one float more.  The norm is a count of positive points that the objective formed in
+            # fp32; fp32 adds integers exactly below 2^24, so the sum is the integer sum it was
+            lib, st, state = _lib.lib(), _lib.current_stream(), self.guard._on(norm.device)
+            pair = torch.empty(2, dtype=torch.float32, device=norm.device)
+            pair[0].copy_(norm.reshape(()))
+            _lib.check(lib.dcf_guard_word_publish(state, _lib.ptr(pair[1:]), st), 'dcf_guard_word_publish')
+            D._all_reduce_sum(pair, self.group, self._backend)
+            _lib.check(lib.dcf_guard_word_merge(state, _lib.ptr(pair[1:]), st), 'dcf_guard_word_merge')
+            return pair[0].to(norm.dtype).reshape(norm.shape)
         if self.world > 1:
             norm = norm.clone()
             D._all_reduce_sum(norm, self.group, self._backend)
