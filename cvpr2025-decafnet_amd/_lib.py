@@ -309,6 +309,24 @@ FIT = (
 )
 
 
+# the training-log extension (include/decafnet_hip_steplog.h, csrc/steplog.hip).  ``vals`` is a HOST array of device pointers to fp32
+# scalars; ``stats`` / ``out`` float64 and ``counts`` int64 are device memory.
+STEPLOG_MAX_KEYS = 16         # DCF_STEPLOG_MAX_KEYS
+STEPLOG_COLS = 6              # DCF_STEPLOG_COLS
+STEPLOG_TABLE = {
+    'dcf_steplog_ext_version': (i32, []),
+    'dcf_op_steplog_add': (i32, [ctypes.POINTER(vp), i32, c_f64p, c_i64p, vp]),
+    'dcf_op_steplog_flush': (i32, [c_f64p, c_i64p, i32, c_f64p, vp]),
+}
+
+
+# Bound by lib() after FIT and waiting for the same follow-up: registration at the end of EXTENSIONS together with a
+# ``borders.TABLE`` row (the cases are tests/steplog_abi_cases.py, run through the same driver by tests/test_gpu_steplog.py).
+STEPLOG = (
+    Extension('steplog', 'decafnet_hip_steplog.h', 'dcf_steplog_ext_version', 1, 'DCF_STEPLOG_EXT_VERSION', ('decafnet_hip.h',), STEPLOG_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -320,10 +338,11 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS + PENDING + STAGED + FIT:
+        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG:
             for name, (res, args) in ext.table.items():
                 if name in bound:
-                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED / _lib.FIT')
+                    raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED / _lib.FIT / '
+                                       f'_lib.STEPLOG')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

@@ -407,6 +407,20 @@ class VideoCentricTrainData:
                     text=tuple(self.token_features(v['text_ids'][i]) for i in seg_idx),
                     text_cls=self.cls.lookup(self.sentences(vid_id, seg_idx)))
 
+    # ---- the random streams ----------------------------------------------------------------------------------------------------
+    def rng_state(self):
+        """the state of both generators of the RNG contract, as plain picklable Python / numpy objects"""
+        return {'random': self.rng.getstate(), 'numpy': self.np_rng.get_state()}
+
+    def set_rng_state(self, state):
+        """put back what ``rng_state`` returned: the next ``decide`` draws what it would have drawn then"""
+        if not isinstance(state, dict) or set(state) != {'random', 'numpy'}:
+            raise ValueError("set_rng_state: a dict with the keys 'random' and 'numpy', as rng_state() returns it")
+        r = state['random']
+        self.rng.setstate((r[0], tuple(r[1]), r[2]))                          # a list after a round trip through some formats
+        self.np_rng.set_state(state['numpy'])
+        return self
+
     # ---- order -----------------------------------------------------------------------------------------------------------------
     def order(self, epoch, rank=0, world_size=1):
         """this project's shuffling rule (class docstring) -> the sample indices of ``rank`` in ``epoch``, a list of ints"""
@@ -675,7 +689,12 @@ class TrainLoader:
     (``vid`` and ``shallow`` into ``input_vid_len`` columns, the token features into ``max_text_len``) plus an index_select on the
     CLS table: no feature byte crosses the host.  ``bank=None``: ``collate_host`` and ``.cuda()``, the same bits.  ``text_size``
     stays on the host either way, where the step reads it.  ``input_vid_len``: the batch's columns, the Trainer's model max_vid_len *
-    vid_stride (worker_v2.py:286; default: the data's max_vid_len); ``vid_stride`` divides the targets (worker_v2.py:417)."""
+    vid_stride (worker_v2.py:286; default: the data's max_vid_len); ``vid_stride`` divides the targets (worker_v2.py:417).
+
+    ``state()`` / ``load_state()``: the random streams of ``train_data`` for a checkpoint.  While the generator of ``epoch(e)`` has
+    not finished, the state is the snapshot taken when it started -- a checkpoint inside an epoch restarts that epoch
+    (``train.fit``), so the restarted epoch draws what the interrupted one drew -- and afterwards it is the live state.  The order of
+    the samples needs no state: it is a function of the seed and the epoch."""
 
     def __init__(self, train_data, bank, batch_size, microbatch_size=None, rank=0, world_size=1, input_vid_len=None, vid_stride=1,
                  device='cuda', num_trials=5000):
@@ -691,9 +710,21 @@ class TrainLoader:
         self.vid_stride = vid_stride
         self.rank, self.world_size, self.num_trials = rank, world_size, num_trials
         self.device = torch.device(device) if bank is None else bank.device
+        self._epoch_start = None                                              # the streams at the start of an unfinished epoch
 
     def __len__(self):
         return len(self.td) // self.world_size // self.batch_size
+
+    def state(self):
+        """-> {'rng': ``train_data.rng_state()``}: as it was at the start of the epoch that is under way, else as it is now"""
+        return {'rng': self.td.rng_state() if self._epoch_start is None else self._epoch_start}
+
+    def load_state(self, state):
+        if not isinstance(state, dict) or 'rng' not in state:
+            raise ValueError("TrainLoader.load_state: a dict with the key 'rng', as state() returns it")
+        self.td.set_rng_state(state['rng'])
+        self._epoch_start = None
+        return self
 
     def _host(self, e, ids):
         samples = [self.td.sample(e, i, self.num_trials) for i in ids]
@@ -732,6 +763,7 @@ class TrainLoader:
     def epoch(self, e):
         make = self._host if self.bank is None else self._banked
         order = self.td.order(e, self.rank, self.world_size)
+        self._epoch_start = self.td.rng_state()
         for k in range(len(self)):
             ids = order[k * self.batch_size:(k + 1) * self.batch_size]
             if self.microbatch_size is None:
@@ -739,3 +771,4 @@ class TrainLoader:
             else:
                 parts = [make(e, ids[i:i + self._mb]) for i in range(0, self.batch_size, self._mb)]
                 yield [p[0] for p in parts], [p[1] for p in parts]
+        self._epoch_start = None

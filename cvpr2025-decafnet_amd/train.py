@@ -49,8 +49,14 @@ loop on a process group: rank 0 checkpoints, every rank evaluates its share of t
 validation loss comes from an ``evaluator.DeviceLossMeter`` (dcf_op_loss_table_mean, include/decafnet_hip_fit.h), and
 ``DataParallelTrainStep(..., agree_skips=True)`` keeps the ranks' skips equal.
 
-Not here: logging, AMP, graph capture of the step, SGD, gradient compression, the detection of parameters that no
-rank used.
+The log.  ``fit(..., log_interval=N)`` writes the Trainer's lines to ``<root>/log.txt`` from a ``StepLog``: the loss meters live in
+device memory (dcf_op_steplog_add / dcf_op_steplog_flush, include/decafnet_hip_steplog.h), the step adds to them with one launch and
+waits for nothing, and a line is written once its numbers have landed.  ``fit(..., data_state=True)`` puts the data loader's random
+streams into the checkpoint (``states/data_last.pth``), so that a resumed run with ``crop_ratio`` draws the windows, and logs the
+losses, of the uninterrupted one.  Both are off by default.
+
+Not here: W&B and TensorBoard themselves, AMP, graph capture of the step, SGD, gradient compression, the detection
+of parameters that no rank used.
 
 The front end.  ``training_forward(..., front_end='dense')`` makes the network's input as the reference does: the features of a video
 once per query, transposed, times the gate, concatenated with the shallow features, and ``masked_conv1d`` on that (B', T, Cin)
@@ -299,19 +305,158 @@ class TrainStep:
         return self
 
 
-def run_epoch(ts, loader, epoch=None):
-    """One epoch of ``Trainer.run`` (worker_v2.py:309-325) without its logging and evaluation: ``ts.step`` on every batch of
-    ``loader.epoch(epoch)`` (a ``data.TrainLoader``; ``epoch`` None: ``ts.epoch``), then ``ts.epoch = epoch + 1``.
+def run_epoch(ts, loader, epoch=None, log=None):
+    """One epoch of ``Trainer.run`` (worker_v2.py:309-325) without its evaluation: ``ts.step`` on every batch of
+    ``loader.epoch(epoch)`` (a ``data.TrainLoader``; ``epoch`` None: ``ts.epoch``), then ``ts.epoch = epoch + 1``.  ``log``: a
+    ``StepLog`` that is updated after every step (None, the default: nothing more is launched).
     -> the running sums of what the steps returned (cls, reg, total, grad_norm) as device tensors, and 'steps', an int.  No host read."""
     epoch = ts.epoch if epoch is None else int(epoch)
     sums, steps = {}, 0
     for batch, targets in loader.epoch(epoch):
-        for k, v in ts.step(batch, targets).items():
+        out = ts.step(batch, targets)
+        if log is not None:
+            log.update(out)
+        for k, v in out.items():
             sums[k] = v if k not in sums else sums[k] + v
         steps += 1
     ts.epoch = epoch + 1
     sums['steps'] = steps
     return sums
+
+
+STEP_KEYS = ('cls', 'reg', 'total', 'grad_norm')                     # what ``TrainStep.step`` returns
+LOG_STATS = ('mean', 'finite_mean', 'min', 'max', 'last', 'n_finite')  # the columns of a row of dcf_op_steplog_flush
+
+
+def time_str(t):
+    """libs/train_utils.py:56-61"""
+    if t >= 3600:
+        return '{:.1f}h'.format(t / 3600)
+    if t > 60:
+        return '{:.1f}m'.format(t / 60)
+    return '{:.1f}s'.format(t)
+
+
+def log_line(itr, num_itrs, keys, means, seconds):
+    """the line of ``Trainer.log`` (worker_v2.py:705-720): the iteration in the width of ``num_itrs``, ``key mean | `` per key in the
+    order of ``keys``, then ``time_str`` of the seconds per step"""
+    t = len(str(num_itrs))
+    return f'[{itr:0{t}d}/{num_itrs:0{t}d}] ' + ''.join(f'{k} {m:.3f} | ' for k, m in zip(keys, means)) + time_str(seconds)
+
+
+def _log_arguments(who, log_interval, log_keys):
+    """the checks ``StepLog``, ``fit`` and ``fit_parallel`` share -> (log_interval as an int, the keys as a tuple)"""
+    if isinstance(log_interval, bool) or int(log_interval) != log_interval or int(log_interval) < 0:
+        raise ValueError(f'{who}: log_interval = {log_interval!r} (an int >= 0; 0: no log)')
+    keys = (log_keys,) if isinstance(log_keys, str) else tuple(log_keys)
+    bad = [k for k in keys if k not in STEP_KEYS]
+    if bad or not keys or len(set(keys)) != len(keys) or len(keys) > _lib.STEPLOG_MAX_KEYS:
+        raise ValueError(f'{who}: log_keys = {log_keys!r}: a non-empty selection without repeats of what the step returns, {STEP_KEYS}')
+    return int(log_interval), keys
+
+
+class StepLog:
+    """The Trainer's loss meters and log lines (worker_v2.py:326-335, 705-720) without a host wait in the loop.
+
+    The reference calls ``v.detach().item()`` on every loss of every step: a wait per step, which ``TrainStep.step`` is built to avoid.
+    Here the meters are two small tables in device memory (include/decafnet_hip_steplog.h).  ``update(step_out)``, called after
+    ``ts.step`` on the stream the step ran on, adds the step's values with ONE launch (dcf_op_steplog_add gathers the ``keys`` from
+    their separate allocations).  When ``ts.itr == 1 or ts.itr % log_interval == 0`` (worker_v2.py:334) it also makes one
+    dcf_op_steplog_flush (read-and-reset, in stream order), one ``non_blocking`` copy of the (K + 1, 6) result into a pinned buffer and
+    one timing event, queues ``(itr, buffer, event)`` and goes on.  ``poll()`` -- every ``update`` ends with one -- writes the lines of
+    all entries at the head of the queue whose event has completed, in order, and never waits; ``drain()`` waits for the last event
+    and writes everything; ``close()`` drains.
+
+    The line is the reference's: ``[{itr}/{num_itrs}] `` in the width of ``num_itrs``, ``{key} {mean:.3f} | `` per key in ``keys``
+    order (any selection of cls, reg, total, grad_norm), then ``time_str`` of the seconds per step.  The mean is AverageMeter's:
+    ``sum / steps`` with the sum taken in step order in double, the bits of ``sum += float(v)``.  Seconds per step is DEVICE time: the
+    time between this flush's event and the previous one's (for the first line: the event recorded at construction) over the
+    interval's steps.  The reference's host clock around a step would measure enqueueing here.
+
+    The line is appended to ``path`` (None: no file; the loops pass ``<root>/log.txt``, worker_v2.py:263), so a resumed run continues
+    the file; it is printed with ``echo=True``; and ``on_line(itr, {key: {'mean', 'finite_mean', 'min', 'max', 'last', 'n_finite'}},
+    steps, seconds)`` is where a W&B or TensorBoard user attaches (neither is imported here).  ``finite_mean`` / ``min`` / ``max``
+    cover the finite values alone (NaN where there is none): what a run under ``skip_nonfinite`` wants to see beside a mean that one
+    NaN poisons, as in the reference.
+
+    A partial interval is not part of a checkpoint: a resumed run starts its meters empty."""
+
+    def __init__(self, ts, num_itrs, path=None, log_interval=100, keys=('cls', 'reg', 'total'), echo=False, on_line=None):
+        log_interval, self.keys = _log_arguments('StepLog', log_interval, keys)
+        if log_interval < 1:
+            raise ValueError(f'StepLog: log_interval = {log_interval!r} (>= 1)')
+        if on_line is not None and not callable(on_line):
+            raise ValueError(f'StepLog: on_line = {on_line!r} is not callable')
+        self.ts, self.num_itrs, self.path, self.log_interval, self.echo, self.on_line = ts, int(num_itrs), path, log_interval, echo, on_line
+        self.device = ts._params[0].device
+        if self.device.type != 'cuda':
+            raise RuntimeError('StepLog: the meters live on the MI355X: move the model to the GPU first')
+        K = len(self.keys)
+        self._lib = _lib.lib()
+        self._stats = torch.zeros(K, _lib.STEPLOG_COLS, dtype=torch.float64, device=self.device)
+        self._counts = torch.zeros(K + 1, dtype=torch.int64, device=self.device)
+        self._out = torch.empty(K + 1, _lib.STEPLOG_COLS, dtype=torch.float64, device=self.device)
+        self._free = [self._pinned() for _ in range(2)]
+        self._pending = []                                                # (itr, pinned buffer, event), oldest first
+        self._vals = (_lib.vp * K)()
+        self._last_event = torch.cuda.Event(enable_timing=True)
+        self._last_event.record()
+        self.lines = 0                                                     # lines written so far
+
+    def _pinned(self):
+        return torch.empty(len(self.keys) + 1, _lib.STEPLOG_COLS, dtype=torch.float64).pin_memory()
+
+    def update(self, step_out):
+        """the values of one step (what ``ts.step`` returned) into the meters; a flush where the reference logs; then ``poll()``"""
+        st, K = _lib.current_stream(), len(self.keys)
+        for i, k in enumerate(self.keys):
+            v = step_out[k]
+            if v.dtype != torch.float32 or v.numel() != 1 or v.device != self.device:
+                raise ValueError(f'StepLog.update: {k!r} is {v.dtype} of {tuple(v.shape)} on {v.device}: one fp32 scalar on {self.device}')
+            self._vals[i] = v.data_ptr()
+        _lib.check(self._lib.dcf_op_steplog_add(self._vals, K, _lib.ptr(self._stats), _lib.ptr(self._counts), st), 'dcf_op_steplog_add')
+        itr = self.ts.itr
+        if itr == 1 or itr % self.log_interval == 0:                       # worker_v2.py:334
+            _lib.check(self._lib.dcf_op_steplog_flush(_lib.ptr(self._stats), _lib.ptr(self._counts), K, _lib.ptr(self._out), st),
+                       'dcf_op_steplog_flush')
+            buf = self._free.pop() if self._free else self._pinned()
+            buf.copy_(self._out, non_blocking=True)                        # stream order: before the next flush rewrites ``_out``
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            self._pending.append((itr, buf, event))
+        self.poll()
+
+    def poll(self):
+        """write the lines whose numbers have landed, oldest first; never waits -> how many were written"""
+        n = 0
+        while self._pending and self._pending[0][2].query():
+            self._write(*self._pending.pop(0))
+            n += 1
+        return n
+
+    def drain(self):
+        """wait for the last pending flush and write every line -> how many were written"""
+        if self._pending:
+            self._pending[-1][2].synchronize()
+        return self.poll()
+
+    close = drain
+
+    def _write(self, itr, buf, event):
+        rows = buf.tolist()
+        self._free.append(buf)
+        steps = int(rows[-1][0])
+        seconds = self._last_event.elapsed_time(event) * 1e-3 / max(steps, 1)
+        self._last_event = event
+        line = log_line(itr, self.num_itrs, self.keys, [r[0] for r in rows[:-1]], seconds)
+        if self.path is not None:
+            with open(self.path, 'a') as fh:
+                fh.write(line + '\n')
+        if self.echo:
+            print(line, flush=True)
+        self.lines += 1
+        if self.on_line is not None:
+            self.on_line(itr, {k: dict(zip(LOG_STATS, r)) for k, r in zip(self.keys, rows)}, steps, seconds)
 
 
 EVAL_BY = ('epoch', 'itr')
@@ -353,35 +498,93 @@ def evaluate(ts, evaluator, eval_data, counter=None, meter=None):
         ev.model = own
 
 
-def fit(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_by='epoch', eval_run=0, resume=True):
-    """``Trainer.run`` (worker_v2.py:307-364) with its checkpoints and evaluations, without its logging: ``run_epoch`` per epoch until
+def fit(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_by='epoch', eval_run=0, resume=True, log_interval=0,
+        log_keys=('cls', 'reg', 'total'), on_line=None, data_state=False):
+    """``Trainer.run`` (worker_v2.py:307-364) with its checkpoints, evaluations and log: ``run_epoch`` per epoch until
     ``ts.epoch`` reaches ``num_epochs`` (None: ``opt.train.epochs``).  Where the reference calls ``evaluate(ct)`` -- after every epoch
     with ``eval_by='epoch'`` (ct = the epoch count), after every iteration divisible by ``eval_run`` with ``eval_by='itr'`` (the step
     loop is written out for it; ct = ``ts.itr``) -- ``checkpoint(ts, root)`` runs, and when ``eval_run > 0`` and ct is divisible by it
     the EMA copy is evaluated on ``eval_data`` (``evaluate`` above) and ``counter.report()`` goes to ``<root>/eval_{epoch}_{itr}.txt``.
     ``eval_run=0``: checkpoints per epoch, no evaluation (``eval_by='itr'`` then never checkpoints: the reference divides by it).
     ``resume=True``: when ``models/last.pth`` and ``states/last.pth`` both exist they are loaded first (train.py:66-69) and the loop
-    continues at ``ts.epoch``; a checkpoint taken inside an epoch restarts that epoch, as in the reference.  The data loader's
-    random streams are not part of a checkpoint.  -> [(epoch, itr, metrics)] of the evaluations.
-    Not here: the validation loss, W&B and loss meters, more than one rank (NotImplementedError before anything is launched;
-    ``fit_parallel`` is the loop for those)."""
+    continues at ``ts.epoch``; a checkpoint taken inside an epoch restarts that epoch, as in the reference.
+    -> [(epoch, itr, metrics)] of the evaluations.
+    ``log_interval > 0``: the Trainer's log.  A ``StepLog`` with ``num_itrs = num_epochs * len(loader)``, ``path = <root>/log.txt``,
+    ``keys = log_keys`` and ``on_line`` is updated after every step -- one small launch per step, one more and a 192-byte asynchronous
+    copy per logged iteration, no host wait -- and drained before every checkpoint (which reads the device anyway) and before the
+    return.  ``log_interval=0``, the default: nothing of it is constructed, launched or written.  A negative interval and a key the
+    step does not return are refused with ValueError before anything is opened.
+    ``data_state=True``: the data loader's random streams become part of a checkpoint.  ``checkpoint`` is followed by
+    ``<root>/states/data_last.pth`` (``loader.state()``: inside an epoch the streams as they were at its start, since a resumed run
+    restarts that epoch), and a resume loads the file where it exists, so that with ``crop_ratio`` set the resumed run draws the
+    windows of the uninterrupted one.  ``False``, the default: the files under ``root`` are what they were, and the streams start over.
+    Not here: the validation loss, W&B itself, more than one rank (NotImplementedError before anything is launched; ``fit_parallel``
+    is the loop for those)."""
+    log_interval, log_keys = _log_arguments('fit', log_interval, log_keys)
     if getattr(ts, 'world', 1) > 1:
         raise NotImplementedError(f'fit: a DataParallelTrainStep of world {ts.world} is not implemented: checkpoints and the evaluation '
                                   f'belong to rank 0 and need a barrier (train.fit_parallel is the loop for a process group)')
     eval_run = _fit_arguments('fit', eval_by, eval_run, eval_data)
-    _resume(ts, root, resume)
+    if _resume(ts, root, resume) and data_state:
+        _resume_data(loader, root)
+    log = _make_log(ts, loader, root, num_epochs, log_interval, log_keys, on_line)
     results = []
 
     def evaluate_at(ct):
+        if log is not None:
+            log.drain()
         checkpoint(ts, root)
+        if data_state:
+            _checkpoint_data(root, [loader.state()])
         if eval_run > 0 and ct % eval_run == 0:
             counter = evaluate(ts, evaluator, eval_data)
             with open(os.path.join(root, f'eval_{ts.epoch}_{ts.itr}.txt'), 'w') as fh:
                 fh.write(counter.report())
             results.append((ts.epoch, ts.itr, counter.metrics()))
 
-    _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at)
+    _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at, log)
     return results
+
+
+DATA_STATE = os.path.join('states', 'data_last.pth')
+
+
+def _make_log(ts, loader, root, num_epochs, log_interval, log_keys, on_line):
+    """the ``StepLog`` of a fit, or None with ``log_interval == 0``"""
+    if log_interval == 0:
+        return None
+    num_epochs = int(ts.opt['train']['epochs'] if num_epochs is None else num_epochs)
+    os.makedirs(root, exist_ok=True)
+    return StepLog(ts, num_epochs * len(loader), os.path.join(root, 'log.txt'), log_interval, log_keys, on_line=on_line)
+
+
+def _checkpoint_data(root, states):
+    """``<root>/states/data_last.pth``: the ``TrainLoader.state()`` of every rank, in rank order"""
+    os.makedirs(os.path.join(root, 'states'), exist_ok=True)
+    torch.save({'world_size': len(states), 'ranks': list(states)}, os.path.join(root, DATA_STATE))
+
+
+def _gather_data_states(loader, rank, world, group):
+    """``loader.state()`` of every rank, in rank order, on rank 0 and None on the others: one ``gather_object`` where the group has
+    several ranks (every rank calls this), nothing collective on one"""
+    if world == 1:
+        return [loader.state()]
+    import torch.distributed as dist
+    states = [None] * world if rank == 0 else None
+    dist.gather_object(loader.state(), states, dst=0 if group is None else dist.get_global_rank(group, 0), group=group)
+    return states
+
+
+def _resume_data(loader, root, rank=0, world=1):
+    """this rank's entry of ``states/data_last.pth`` into ``loader``, where the file exists (a run resumed from checkpoints that were
+    written without ``data_state`` starts its streams over, as before)"""
+    path = os.path.join(root, DATA_STATE)
+    if not os.path.exists(path):
+        return
+    saved = torch.load(path, map_location='cpu', weights_only=False)
+    if saved['world_size'] != world:
+        raise ValueError(f'{path} holds the data streams of {saved["world_size"]} ranks, this run has {world}')
+    loader.load_state(saved['ranks'][rank])
 
 
 def _fit_arguments(who, eval_by, eval_run, eval_data):
@@ -395,38 +598,47 @@ def _fit_arguments(who, eval_by, eval_run, eval_data):
 
 
 def _resume(ts, root, resume):
-    """train.py:66-69: both ``last.pth`` files into ``ts`` where both exist and ``resume`` says so"""
+    """train.py:66-69: both ``last.pth`` files into ``ts`` where both exist and ``resume`` says so -> whether they were loaded"""
     last = os.path.join(root, 'models', 'last.pth'), os.path.join(root, 'states', 'last.pth')
     if resume and all(os.path.exists(p) for p in last):
         ts.load_state(*(torch.load(p, map_location='cpu', weights_only=False) for p in last))
+        return True
+    return False
 
 
-def _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at):
-    """the loop of ``Trainer.run`` (worker_v2.py:307-347): ``evaluate_at(ct)`` where the reference calls ``evaluate(ct)``"""
+def _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at, log=None):
+    """the loop of ``Trainer.run`` (worker_v2.py:307-347): ``evaluate_at(ct)`` where the reference calls ``evaluate(ct)``, ``log``
+    (a ``StepLog`` or None) updated after every step and closed at the end"""
     num_epochs = int(ts.opt['train']['epochs'] if num_epochs is None else num_epochs)
     while ts.epoch < num_epochs:
         if eval_by == 'itr':
             for batch, targets in loader.epoch(ts.epoch):
-                ts.step(batch, targets)
+                out = ts.step(batch, targets)
+                if log is not None:
+                    log.update(out)
                 if eval_run > 0 and ts.itr % eval_run == 0:          # worker_v2.py:340
                     evaluate_at(ts.itr)
             ts.epoch += 1
         else:
-            run_epoch(ts, loader)
+            run_epoch(ts, loader, log=log)
             evaluate_at(ts.epoch)                                    # worker_v2.py:345-347
+    if log is not None:
+        log.close()
 
 
 EvalResult = namedtuple('EvalResult', 'epoch itr metrics loss')
 
 
 def fit_parallel(ts, loader, root, num_epochs=None, evaluator=None, eval_data=None, eval_by='epoch', eval_run=0, resume=True,
-                 val_loss=False, eval_shard=True):
+                 val_loss=False, eval_shard=True, log_interval=0, log_keys=('cls', 'reg', 'total'), on_line=None, data_state=False):
     """``fit`` on a ``TrainStep`` or a ``DataParallelTrainStep`` of any world: ``Trainer.run`` under DistributedDataParallel.  The
     arguments of ``fit`` and two more.  ``val_loss=True``: every evaluation also computes the validation loss ``Evaluator.run`` logs, on
     the device (``evaluator.DeviceLossMeter``; ``eval_data`` is then a ``data.EvalBank``).  ``eval_shard``: below.
     -> [EvalResult(epoch, itr, metrics, loss)], ``loss`` None or {'cls_loss', 'reg_loss'} as Python floats.  The report file is
     ``counter.report()``, followed with ``val_loss=True`` by the loss line as the reference forms it (worker_v2.py:903-906).
-    With a world-1 step and ``val_loss=False`` the loop launches and writes exactly what ``fit`` does.
+    With a world-1 step and ``val_loss=False`` the loop launches and writes exactly what ``fit`` does, with the log and the data
+    state on in both as well.
+    ``log_interval`` / ``log_keys`` / ``on_line`` / ``data_state``: as in ``fit``.
 
     With a world above 1 (``ts.group`` is the process group; every rank calls this with the same arguments):
       * Refused with ValueError before anything is launched: a ``loader`` whose ``rank`` / ``world_size`` are not those of the group;
@@ -445,15 +657,20 @@ def fit_parallel(ts, loader, root, num_epochs=None, evaluator=None, eval_data=No
         results.
       * Every rank issues the same collectives in the same order: the step's own, then a barrier per checkpoint, then at most two
         all-reduces per evaluation.
+      * The log: rank 0 alone owns a ``StepLog``, and it logs its own losses, as the reference does ("only track loss from rank 0 to
+        avoid sync overhead"): no collective is added, and the other ranks construct and launch nothing.
+      * ``data_state=True``: at every checkpoint ``loader.state()`` of every rank is gathered to rank 0 (one ``gather_object``, issued
+        by every rank before the checkpoint's barrier) and written as one entry per rank; on resume every rank reads its own entry.
       * The one-pass LayerNorm guard (``GroundingEvaluator._run_on_device``): a rank whose guard trips resets its own counter and meter
         and repeats its own share before the reduce.  The two-pass repeat therefore covers a share, not the whole set: after a trip
         the videos of the other shares were evaluated with one-pass launches, and results may differ in the last bits between world
         sizes.
 
-    Not here: W&B and the training-loss meters, AMP."""
+    Not here: W&B itself, losses reduced over the ranks, AMP."""
     from . import data as _data, evaluator as E
     world = getattr(ts, 'world', 1)
     group = getattr(ts, 'group', None)
+    log_interval, log_keys = _log_arguments('fit_parallel', log_interval, log_keys)
     eval_run = _fit_arguments('fit_parallel', eval_by, eval_run, eval_data)
     rank = 0
     if world > 1:
@@ -470,9 +687,11 @@ def fit_parallel(ts, loader, root, num_epochs=None, evaluator=None, eval_data=No
         raise ValueError(f'fit_parallel: {"val_loss=True" if val_loss else "eval_shard=True"} evaluates a data.EvalBank on the device, '
                          f'eval_data is {type(eval_data).__name__}')
     barrier = (lambda: dist.barrier(group)) if world > 1 else (lambda: None)
-    _resume(ts, root, resume)
+    if _resume(ts, root, resume) and data_state:
+        _resume_data(loader, root, rank, world)
     if resume:
         barrier()                                                    # worker_v2.py:273-275
+    log = _make_log(ts, loader, root, num_epochs, log_interval, log_keys, on_line) if rank == 0 else None
     share = eval_data
     if sharded and eval_run > 0:
         clips = [eval_data.rows['vid'][k][1] for k in eval_data.index]
@@ -481,8 +700,14 @@ def fit_parallel(ts, loader, root, num_epochs=None, evaluator=None, eval_data=No
     results = []
 
     def evaluate_at(ct):
+        if log is not None:
+            log.drain()
         if rank == 0:
             checkpoint(ts, root)
+        if data_state:
+            states = _gather_data_states(loader, rank, world, group)
+            if rank == 0:
+                _checkpoint_data(root, states)
         due = eval_run > 0 and ct % eval_run == 0
         if due and sharded:                                          # every rank its share, after the checkpoint's barrier
             barrier()
@@ -503,7 +728,7 @@ def fit_parallel(ts, loader, root, num_epochs=None, evaluator=None, eval_data=No
                 fh.write(counter.report() + ('' if loss is None else E.DeviceLossMeter.line(loss)))
         results.append(EvalResult(ts.epoch, ts.itr, counter.metrics(), loss))
 
-    _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at)
+    _fit_loop(ts, loader, num_epochs, eval_by, eval_run, evaluate_at, log)
     return results
 
 
