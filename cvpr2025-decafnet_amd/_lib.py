@@ -327,6 +327,30 @@ STEPLOG = (
 )
 
 
+# the attention-map-dropout extension (include/decafnet_hip_attn_drop.h, csrc/attn_drop.hip): the three attention cores -- sliding
+# window, global self attention (window = 0 of the local export, with a backward export of its own) and cross attention -- with
+# dropout on the map, forward and backward, and channel dropout.  Every operator takes b0, seed, site, p after the arguments of its dropout-free
+# form, in the order dcf_op_dropout has them.
+_ADROP = [i32, i64, i32, f32]                               # b0, seed, site, p
+ATTN_DROP_TABLE = {
+    'dcf_attn_drop_ext_version': (i32, []),
+    'dcf_op_local_attn_drop': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, i32, i32, i32, i32, i32] + _ADROP + [vp]),
+    'dcf_op_local_attn_drop_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32] + _ADROP + [vp]),
+    'dcf_op_global_attn_drop_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32] + _ADROP + [vp]),
+    'dcf_op_xattn_drop': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, i32, i32, i32, i32, i32] + _ADROP + [vp]),
+    'dcf_op_xattn_drop_bwd': (i32, [c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32] + _ADROP + [vp]),
+    'dcf_op_channel_dropout': (i32, [c_f32p, c_f32p, i32, i32, i32] + _ADROP + [vp]),
+}
+
+
+# Bound by lib() after STEPLOG and waiting for the same follow-up: registration at the end of EXTENSIONS together with a
+# ``borders.TABLE`` row (the cases are tests/attn_drop_abi_cases.py, run through the same driver by tests/test_gpu_attn_drop_borders.py).
+ATTN_DROP = (
+    Extension('attn_drop', 'decafnet_hip_attn_drop.h', 'dcf_attn_drop_ext_version', 1, 'DCF_ATTN_DROP_EXT_VERSION', ('decafnet_hip.h',),
+              ATTN_DROP_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -338,11 +362,11 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG:
+        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG + ATTN_DROP:
             for name, (res, args) in ext.table.items():
                 if name in bound:
                     raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED / _lib.FIT / '
-                                       f'_lib.STEPLOG')
+                                       f'_lib.STEPLOG / _lib.ATTN_DROP')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

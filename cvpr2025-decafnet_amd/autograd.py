@@ -35,9 +35,15 @@ reference's batch, ``proj_pdrop`` and ``path_pdrop``, and the site group / layer
 layers itself).  The keep bits are those of the training forward (``model.enable_dropout``; csrc/dropout.h: Philox4x32-10 on
 (key, site, element)), so nothing is saved for the backward: it recomputes them (csrc/drop_grad.hip, include/decafnet_hip_train.h --
 ``dropout``, ``gelu_dropout`` and the residual with both of its dropouts, dcf_op_dropout / dcf_op_gelu_dropout / dcf_op_drop_residual
-and their ``_bwd``).  ``drop=None``, or a spec whose two probabilities are 0, is the code path without dropout: the same operators, the
-same bits.  Attention-map dropout, channel dropout and dropout in the text encoder are not implemented.  ``forward(..., eval=False)``
-still returns plain tensors: the training forward with a graph is ``train.training_forward``.
+and their ``_bwd``).  ``drop=None``, or a spec whose probabilities are 0, is the code path without dropout: the same operators, the
+same bits.  ``DropSpec.attn_p`` is the rate of the dropout on the attention map (blocks.py:368): ``window_attention``, ``masked_mha``,
+``conv_attn_layer`` and ``transformer_encoder`` hand it to kernels that draw the keep bits where the map element is formed, forward and
+backward (csrc/attn_drop.hip, include/decafnet_hip_attn_drop.h: dcf_op_local_attn_drop and its ``_bwd``); ``channel_dropout`` is
+nn.Dropout1d on the clip features (dcf_op_channel_dropout).  ``global_attention`` and ``cross_attention`` take the same ``drop``
+(dcf_op_local_attn_drop with window = 0, dcf_op_global_attn_drop_bwd, dcf_op_xattn_drop and its ``_bwd``), stride-0 blocks take
+``drop`` under group DROP_G_TEXT (``text_transformer``), and ``fuse_and_predict`` takes ``fusion_drop`` for the second fusion
+(DROP_G_FUSION2).  ``forward(..., eval=False)`` still returns plain tensors: the training forward with a graph is
+``train.training_forward``.
 
 ``refine_in`` and ``tcn_layer`` are the forward / backward pairs of csrc/refine_grad.hip (dcf_op_refine_in, dcf_op_tcn_layer and their
 ``_bwd``): the stacking of the nearest-upsampled first-pass logits fused with refine.conv_1x1 (model.py:449-455) and one
@@ -240,6 +246,40 @@ class _WindowAttentionFn(torch.autograd.Function):
         return gq, gk, gv, None, None, None
 
 
+class _WindowAttentionDropFn(torch.autograd.Function):
+    """_WindowAttentionFn over dcf_op_local_attn_drop / dcf_op_local_attn_drop_bwd: it saves what that one saves and no mask of the
+    map; the backward draws the keep bits again from (key, site, b0)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, n_heads, window, key, site, p, b0):
+        qd, kd, vd = (_rows(z, 'window_attention') for z in (q, k, v))
+        B, T, C = qd.shape
+        if kd.shape != qd.shape or vd.shape != qd.shape:
+            raise ValueError(f'window_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
+        if window <= 0 or window % 2 == 0:
+            raise ValueError(f'window_attention: window = {window} must be odd and positive (global attention is global_attention)')
+        m = _mask_rows(mask, B, T)
+        if m is None:
+            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)       # the forward core reads its mask unconditionally
+        o = torch.empty_like(qd)
+        ctx.geom = (B, T, C, int(n_heads), int(window), int(b0), int(key), int(site), float(p))
+        _lib.check(_lib.lib().dcf_op_local_attn_drop(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), *ctx.geom,
+                                                     _lib.current_stream()), 'dcf_op_local_attn_drop')
+        ctx.save_for_backward(qd, kd, vd, m)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, m = ctx.saved_tensors
+        go = go.float().contiguous()
+        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
+        if gq is not None or gk is not None or gv is not None:
+            _lib.check(_lib.lib().dcf_op_local_attn_drop_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq),
+                                                             _lib.ptr(gk), _lib.ptr(gv), *ctx.geom, _lib.current_stream()),
+                       'dcf_op_local_attn_drop_bwd')
+        return (gq, gk, gv) + (None,) * 7
+
+
 _GLOBAL_HEAD_DIMS = (32, 64)     # the head dimensions of k_global_attn and of its backward
 
 
@@ -282,6 +322,44 @@ class _GlobalAttentionFn(torch.autograd.Function):
             _lib.check(_lib.lib().dcf_op_global_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
                                                          _lib.ptr(gv), B, T, C, ctx.n_heads, _lib.current_stream()), 'dcf_op_global_attn_bwd')
         return gq, gk, gv, None, None
+
+
+class _GlobalAttentionDropFn(torch.autograd.Function):
+    """_GlobalAttentionFn over dcf_op_local_attn_drop(window = 0) / dcf_op_global_attn_drop_bwd; no mask of the map is saved"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, n_heads, key, site, p, b0):
+        limit = _global_head_limit(q.size(-1), int(n_heads))
+        if limit:
+            raise ValueError(f'global_attention: {limit}')
+        qd, kd, vd = (_rows(z, 'global_attention') for z in (q, k, v))
+        B, T, C = qd.shape
+        if kd.shape != qd.shape or vd.shape != qd.shape:
+            raise ValueError(f'global_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
+        if C > 1024:
+            raise ValueError(f'global_attention: C = {C} (at most 1024)')
+        m = _byte_mask(mask, B, T, 'global_attention')
+        if m is None:
+            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)
+        o = torch.empty_like(qd)
+        ctx.tail = (int(b0), int(key), int(site), float(p))
+        _lib.check(_lib.lib().dcf_op_local_attn_drop(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, C, int(n_heads), 0,
+                                                     *ctx.tail, _lib.current_stream()), 'dcf_op_local_attn_drop')
+        ctx.save_for_backward(qd, kd, vd, m)
+        ctx.n_heads = int(n_heads)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, m = ctx.saved_tensors
+        B, T, C = q.shape
+        go = go.float().contiguous()
+        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
+        if gq is not None or gk is not None or gv is not None:
+            _lib.check(_lib.lib().dcf_op_global_attn_drop_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq),
+                                                              _lib.ptr(gk), _lib.ptr(gv), B, T, C, ctx.n_heads, *ctx.tail, _lib.current_stream()),
+                       'dcf_op_global_attn_drop_bwd')
+        return (gq, gk, gv) + (None,) * 6
 
 
 def masked_conv1d(x, mask, weight, bias=None, stride=1):
@@ -411,27 +489,38 @@ def conv_head(x, mask, head, level=None):
     return masked_conv1d(x, mask, out.weight, out.bias).squeeze(-1)
 
 
-def window_attention(q, k, v, mask, n_heads, window):
+def window_attention(q, k, v, mask, n_heads, window, drop=None, sub=None):
     """The sliding-window attention core of MaskedMHA (blocks.py:204-325, :357-373) on token-major ``q`` / ``k`` / ``v`` (B, T, C), heads
     concatenated along C: softmax over the keys |j - t| <= window // 2 of the sequence, d^-1/4 on q and on k, -1e4 on padded keys,
-    zero rows at padded queries -> (B, T, C).  ``mask``: (B, T) or (B, 1, T) bool, None = all valid; ``window`` odd and positive."""
-    return _WindowAttentionFn.apply(q, k, v, mask, n_heads, window)
+    zero rows at padded queries -> (B, T, C).  ``mask``: (B, T) or (B, 1, T) bool, None = all valid; ``window`` odd and positive.
+    ``drop`` with ``attn_p > 0``: nn.Dropout(attn_p) on the (B, H, T, window) softmax map (blocks.py:368) at site ``sub`` (DROP_ATTN) of
+    the block ``drop`` names, drawn inside the kernels, forward and backward; with ``attn_p = 0`` the launches are those without it."""
+    drop = _active(drop, 'window_attention')
+    if drop is None or drop.attn_p == 0.0:
+        return _WindowAttentionFn.apply(q, k, v, mask, n_heads, window)
+    return _WindowAttentionDropFn.apply(q, k, v, mask, n_heads, window, drop.key, drop.site(DROP_ATTN if sub is None else sub), drop.attn_p,
+                                        drop.b0)
 
 
-def global_attention(q, k, v, mask, n_heads):
+def global_attention(q, k, v, mask, n_heads, drop=None, sub=None):
     """The global self-attention core of MaskedMHA (blocks.py:374-389 with q, k and v of one sequence) on token-major ``q`` / ``k`` / ``v``
     (B, T, C), heads concatenated along C: softmax over the valid keys of the sequence, d^-1/4 on q and on k, masked keys filled with
     -inf -> (B, T, C).  ``mask``: (B, T) or (B, 1, T), None = all valid.  It masks keys only: a padded query row has an output and takes
     a gradient like any other; a padded key takes none.  A sequence without a valid key gives zeros (the reference: NaN) and zero
-    gradients.  Any T, head dimension 32 or 64, C <= 1024 (dcf_op_local_attn with window = 0, dcf_op_global_attn_bwd)."""
-    return _GlobalAttentionFn.apply(q, k, v, mask, n_heads)
+    gradients.  Any T, head dimension 32 or 64, C <= 1024 (dcf_op_local_attn with window = 0, dcf_op_global_attn_bwd).  ``drop`` with
+    ``attn_p > 0``: nn.Dropout(attn_p) on the (B, H, T, T) map (blocks.py:388) at site ``sub`` (DROP_ATTN), drawn inside the kernels."""
+    drop = _active(drop, 'global_attention')
+    if drop is None or drop.attn_p == 0.0:
+        return _GlobalAttentionFn.apply(q, k, v, mask, n_heads)
+    return _GlobalAttentionDropFn.apply(q, k, v, mask, n_heads, drop.key, drop.site(DROP_ATTN if sub is None else sub), drop.attn_p, drop.b0)
 
 
-def masked_mha(q_in, k_in, v_in, mask, mha):
-    """MaskedMHA.forward (blocks.py:327-393; self-attention, no dropout) on token-major inputs (B, T, C), with ``mha`` a
+def masked_mha(q_in, k_in, v_in, mask, mha, drop=None):
+    """MaskedMHA.forward (blocks.py:327-393; self-attention, no proj_drop) on token-major inputs (B, T, C), with ``mha`` a
     modeling.MaskedMHA: proj(window_attention(query(q_in), key(k_in), value(v_in))) for ``window_size > 0``, and
     proj(global_attention(...)) for ``window_size = 0`` (head dimension 32 or 64).  The four projections are k = 1 convolutions that
-    do not mask their input (the reference's are plain nn.Conv1d)."""
+    do not mask their input (the reference's are plain nn.Conv1d).  ``drop``: its ``attn_p`` is the rate of attn_drop (:368, :388) on the
+    map of either core."""
     if mha.window_size < 0:
         raise ValueError(f'masked_mha: window_size = {mha.window_size} (odd and positive, or 0 for global attention)')
     if mha.window_size == 0:
@@ -442,9 +531,9 @@ def masked_mha(q_in, k_in, v_in, mask, mha):
     k = masked_conv1d(k_in, None, mha.key.weight, mha.key.bias)
     v = masked_conv1d(v_in, None, mha.value.weight, mha.value.bias)
     if mha.window_size == 0:
-        ctx = global_attention(q, k, v, mask, mha.n_heads)
+        ctx = global_attention(q, k, v, mask, mha.n_heads, **_drop_kw(drop))
     else:
-        ctx = window_attention(q, k, v, mask, mha.n_heads, mha.window_size)
+        ctx = window_attention(q, k, v, mask, mha.n_heads, mha.window_size, **_drop_kw(drop))
     return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
 
 
@@ -582,26 +671,30 @@ class _LayerScaleResidualFn(torch.autograd.Function):
 # site groups and subs of csrc/dropout.h (site = group << 16 | layer << 4 | sub)
 DROP_G_FUSION, DROP_G_STEM, DROP_G_BRANCH, DROP_G_REFINE = 1, 2, 3, 4
 DROP_PROJ, DROP_FFN_HID, DROP_FFN_OUT, DROP_PATH_ATTN, DROP_PATH_FFN, DROP_TCN = 0, 1, 2, 3, 4, 5
+# the sites of include/decafnet_hip_attn_drop.h: the attention map of a block, and channel dropout on the clip features
+DROP_G_TEXT, DROP_G_FUSION2, DROP_G_INPUT = 5, 6, 7       # the text encoder's blocks; the fusion applied again per pyramid level; the clips
+DROP_ATTN, DROP_CHANNEL = 6, 7
 
 
-class DropSpec(namedtuple('DropSpec', 'seed b0 proj_p path_p group layer', defaults=(0, 0.0, 0.0, 0, 0))):
+class DropSpec(namedtuple('DropSpec', 'seed b0 proj_p path_p group layer attn_p', defaults=(0, 0.0, 0.0, 0, 0, 0.0))):
     """Dropout of one block: the 64-bit key ``seed`` (``model.last_dropout_seed``), ``b0`` the index of the first sequence in the
-    reference's batch, ``proj_p`` (proj_drop and the FFN's two dropouts) and ``path_p`` (drop-path), each in [0, 1), and the block's
-    site ``group`` (DROP_G_*) and ``layer``.  Immutable; ``at(group, layer)`` is the same spec at another block."""
+    reference's batch, ``proj_p`` (proj_drop and the FFN's two dropouts) and ``path_p`` (drop-path), each in [0, 1), the block's
+    site ``group`` (DROP_G_*) and ``layer``, and last ``attn_p``, the rate of the dropout on the attention map (sub DROP_ATTN), in
+    [0, 1) too.  Immutable; ``at(group, layer)`` is the same spec at another block."""
     __slots__ = ()
 
-    def __new__(cls, seed, b0=0, proj_p=0.0, path_p=0.0, group=0, layer=0):
-        proj_p, path_p = float(proj_p), float(path_p)
-        for name, p in (('proj_p', proj_p), ('path_p', path_p)):
+    def __new__(cls, seed, b0=0, proj_p=0.0, path_p=0.0, group=0, layer=0, attn_p=0.0):
+        proj_p, path_p, attn_p = float(proj_p), float(path_p), float(attn_p)
+        for name, p in (('proj_p', proj_p), ('path_p', path_p), ('attn_p', attn_p)):
             if not 0.0 <= p < 1.0:
                 raise ValueError(f'DropSpec: {name} = {p} must lie in [0, 1)')
         if int(b0) < 0 or not 0 <= int(group) < 1 << 15 or not 0 <= int(layer) < 1 << 12:
             raise ValueError(f'DropSpec: b0 = {b0}, group = {group}, layer = {layer} out of range')
-        return super().__new__(cls, int(seed) & ((1 << 64) - 1), int(b0), proj_p, path_p, int(group), int(layer))
+        return super().__new__(cls, int(seed) & ((1 << 64) - 1), int(b0), proj_p, path_p, int(group), int(layer), attn_p)
 
     @property
     def active(self):
-        return self.proj_p > 0.0 or self.path_p > 0.0
+        return self.proj_p > 0.0 or self.path_p > 0.0 or self.attn_p > 0.0
 
     def at(self, group, layer):
         return self._replace(group=int(group), layer=int(layer))
@@ -613,6 +706,11 @@ class DropSpec(namedtuple('DropSpec', 'seed b0 proj_p path_p group layer', defau
     def key(self):
         """the key's 64 bits as the int64 the C ABI takes"""
         return self.seed - (1 << 64) if self.seed >= 1 << 63 else self.seed
+
+
+def _drop_kw(drop):
+    """the ``drop`` keyword of an inner call, passed on only where there is one: without dropout the calls are what they were"""
+    return {} if drop is None else {'drop': drop}
 
 
 def _active(drop, name):
@@ -732,6 +830,35 @@ def dropout(x, drop, sub):
     return _DropoutFn.apply(x, drop.key, drop.site(sub), drop.proj_p, drop.b0)
 
 
+class _ChannelDropoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, key, site, p, b0):
+        xd = _rows(x, 'channel_dropout')
+        B, T, C = xd.shape
+        y = torch.empty_like(xd)
+        ctx.geom = (B, T, C, b0, key, site, p)
+        _lib.check(_lib.lib().dcf_op_channel_dropout(_lib.ptr(xd), _lib.ptr(y), *ctx.geom, _lib.current_stream()), 'dcf_op_channel_dropout')
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = gy.float().contiguous()
+        gx = torch.empty_like(gy)
+        _lib.check(_lib.lib().dcf_op_channel_dropout(_lib.ptr(gy), _lib.ptr(gx), *ctx.geom, _lib.current_stream()), 'dcf_op_channel_dropout')
+        return gx, None, None, None, None
+
+
+def channel_dropout(x, drop):
+    """nn.Dropout1d(drop.proj_p) (model.py:614) on token-major ``x`` (B, T, C) of the reference's (B, C, T) tensor: one keep decision
+    per (sample, channel), element index ``(b0 + b) * C + c``, at sub DROP_CHANNEL of the group / layer ``drop`` names (the clip
+    features before vid_map: ``DropSpec(seed, b0, proj_p=cdrop, group=DROP_G_INPUT)``).  The backward is the same operator on the
+    gradient."""
+    drop = _active(drop, 'channel_dropout')
+    if drop is None or drop.proj_p == 0.0:
+        return x
+    return _ChannelDropoutFn.apply(x, drop.key, drop.site(DROP_CHANNEL), drop.proj_p, drop.b0)
+
+
 def gelu_dropout(x, drop, sub=DROP_FFN_HID):
     """``dropout(gelu(x))`` of FFN.forward (blocks.py:535-536) in one pass, forward and backward, with the bits of the two operators in
     a row; without an active ``drop`` it is ``gelu``."""
@@ -763,9 +890,9 @@ def ffn(x, ffn_module, drop=None):
     return masked_conv1d(gelu_dropout(h, drop), None, ffn_module.proj.weight, ffn_module.proj.bias)
 
 
-def conv_attn_layer(x, mask, layer):
-    """ConvAttNLayer.forward (blocks.py:462-473; no dropout) on token-major ``x`` (B, T, C), with ``layer`` a modeling.ConvAttNLayer of
-    stride 1 or 2: q / k / v = {q,k,v}_norm({q,k,v}_conv(x, mask)), then the MaskedMHA under the strided mask, local (``window_size > 0``)
+def conv_attn_layer(x, mask, layer, drop=None):
+    """ConvAttNLayer.forward (blocks.py:462-473) on token-major ``x`` (B, T, C), with ``layer`` a modeling.ConvAttNLayer of stride 1 or 2;
+    of ``drop`` the layer takes the map dropout of ``masked_mha`` alone: q / k / v = {q,k,v}_norm({q,k,v}_conv(x, mask)), then the MaskedMHA under the strided mask, local (``window_size > 0``)
     or global (``window_size = 0``, head dimension 32 or 64) -> ((B, T / stride, C), ``mask[:, ::stride]``)."""
     if not hasattr(layer, 'q_conv'):
         raise ValueError('conv_attn_layer: stride 0 (no depthwise convolutions: the text encoder) has no backward here')
@@ -780,7 +907,7 @@ def conv_attn_layer(x, mask, layer):
     q = channel_layer_norm(q, layer.q_norm.weight, layer.q_norm.bias)
     k = channel_layer_norm(k, layer.k_norm.weight, layer.k_norm.bias)
     v = channel_layer_norm(v, layer.v_norm.weight, layer.v_norm.bias)
-    return masked_mha(q, k, v, mask, layer.attn), mask
+    return masked_mha(q, k, v, mask, layer.attn, **_drop_kw(drop)), mask
 
 
 def transformer_encoder(x, mask, block, drop=None, narrow_heads=False):
@@ -796,7 +923,8 @@ def transformer_encoder(x, mask, block, drop=None, narrow_heads=False):
     with the convolution's mask ``mask[:, ::2]``, not with the pooled one (:586); the output is not masked, so padded rows hold
     ``drop_path_attn.scale * attn.proj.bias``.  ``drop`` (stride 1 / 2 only; group DROP_G_STEM or DROP_G_BRANCH): proj_drop
     (blocks.py:392, sub 0) and drop_path_attn (3) in the first residual, the FFN's dropouts (1, 2) and drop_path_ffn (4), on the
-    (B, C, T / stride) tensors of the reference.  No attention-map dropout."""
+    (B, C, T / stride) tensors of the reference, and with ``drop.attn_p`` attn_drop on the attention map (blocks.py:368 / :388, sub 6).
+    A stride-0 block takes the same sites (group DROP_G_TEXT)."""
     if block.stride not in (0, 1, 2):
         raise ValueError(f'transformer_encoder: stride = {block.stride} (0: the text encoder, 1 or 2: the video encoder)')
     if block.stride == 0 and block.window_size != 0:
@@ -818,18 +946,16 @@ def transformer_encoder(x, mask, block, drop=None, narrow_heads=False):
         if limit:
             raise ValueError(f'transformer_encoder: stride = 0 (global self-attention of the text encoder): {limit}')
     drop = _active(drop, 'transformer_encoder')
-    if drop is not None and block.stride == 0:
-        raise ValueError('transformer_encoder: stride = 0 (the text encoder) takes no dropout')
     if mask is None:
         mask = torch.ones(B, T, dtype=torch.bool, device=x.device)
     x = _LayerScaleResidualFn.apply(x, None, None, mask, None)
     if block.stride == 0:
         mask = _mask_rows(mask, B, T)
         q = channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias)
-        skip, h = x, xattn_mha(q, q, mask, block.attn.attn)
+        skip, h = x, xattn_mha(q, q, mask, block.attn.attn, **_drop_kw(drop))
     else:
         skip = masked_max_pool1d(x, mask)[0] if block.stride == 2 else x
-        h, mask = conv_attn_layer(channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias), mask, block.attn)
+        h, mask = conv_attn_layer(channel_layer_norm(x, block.ln_attn.weight, block.ln_attn.bias), mask, block.attn, **_drop_kw(drop))
     x = layer_scale_residual(skip, h, block.drop_path_attn.scale, r_mask=mask, drop=drop, subs=(DROP_PROJ, DROP_PATH_ATTN))
     h = ffn(channel_layer_norm(x, block.ln_ffn.weight, block.ln_ffn.bias), block.ffn, drop)
     return layer_scale_residual(x, h, block.drop_path_ffn.scale, h_mask=mask, drop=drop), mask
@@ -854,12 +980,12 @@ def _global_attention_limit(Lk, C, n_heads):
     return _cross_attention_limit(Lk, C, n_heads)
 
 
-def _narrow_head_attention(q, k, v, kv_mask, n_heads):
+def _narrow_head_attention(q, k, v, kv_mask, n_heads, drop=None):
     """``cross_attention`` for heads of d = 8 channels, narrower than the kernels' narrowest (16): every head is laid into the first d of
     16 channels, the rest zero, which leaves q . k and the values untouched; the kernels scale q and k by 16^-1/4 each where the
     reference has d^-1/4, so q and k are multiplied by (16 / d)^1/4 first.  The layout steps are torch's and differentiable; the
     attention and its backward are the same HIP kernels.  The text encoder of a model with text_net heads of 8 channels is where
-    this occurs: at most 64 keys."""
+    this occurs: at most 64 keys.  The channels are padded, not the keys: the element index of the map's dropout is unchanged."""
     B, T, C = q.shape
     d = C // n_heads
     gain = (_WIDE_HEAD / d) ** 0.25
@@ -868,7 +994,7 @@ def _narrow_head_attention(q, k, v, kv_mask, n_heads):
         z = z.reshape(z.size(0), z.size(1), n_heads, d)
         return torch.nn.functional.pad(z if g is None else z * g, (0, _WIDE_HEAD - d)).reshape(z.size(0), z.size(1), n_heads * _WIDE_HEAD)
 
-    o = cross_attention(widen(q, gain), widen(k, gain), widen(v, None), kv_mask, n_heads)
+    o = cross_attention(widen(q, gain), widen(k, gain), widen(v, None), kv_mask, n_heads, **_drop_kw(drop))
     return o.reshape(B, T, n_heads, _WIDE_HEAD)[..., :d].reshape(B, T, C)
 
 
@@ -905,6 +1031,40 @@ class _CrossAttentionFn(torch.autograd.Function):
         return gq, gk, gv, None, None
 
 
+class _CrossAttentionDropFn(torch.autograd.Function):
+    """_CrossAttentionFn over dcf_op_xattn_drop / dcf_op_xattn_drop_bwd; no mask of the map is saved"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kv_mask, n_heads, key, site, p, b0):
+        qd, kd, vd = (_rows(z, 'cross_attention') for z in (q, k, v))
+        B, T, C = qd.shape
+        Lk = kd.size(1)
+        if kd.shape != (B, Lk, C) or vd.shape != kd.shape:
+            raise ValueError(f'cross_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree ((B, T, C) and (B, Lk, C))')
+        limit = _cross_attention_limit(Lk, C, n_heads)
+        if limit:
+            raise ValueError(limit)
+        m = _byte_mask(kv_mask, B, Lk, 'cross_attention')
+        if m is None:
+            m = torch.ones(B, Lk, dtype=torch.bool, device=qd.device)
+        o = torch.empty_like(qd)
+        ctx.geom = (B, T, Lk, C, int(n_heads), int(b0), int(key), int(site), float(p))
+        _lib.check(_lib.lib().dcf_op_xattn_drop(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), *ctx.geom,
+                                                _lib.current_stream()), 'dcf_op_xattn_drop')
+        ctx.save_for_backward(qd, kd, vd, m)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, m = ctx.saved_tensors
+        go = go.float().contiguous()
+        gq, gk, gv = (torch.empty_like(z) if need else None for z, need in zip((q, k, v), ctx.needs_input_grad[:3]))
+        if gq is not None or gk is not None or gv is not None:
+            _lib.check(_lib.lib().dcf_op_xattn_drop_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
+                                                        _lib.ptr(gv), *ctx.geom, _lib.current_stream()), 'dcf_op_xattn_drop_bwd')
+        return (gq, gk, gv) + (None,) * 6
+
+
 class _AdaLnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, h, norm):
@@ -933,12 +1093,16 @@ class _AdaLnFn(torch.autograd.Function):
         return gx, None, gh, None
 
 
-def cross_attention(q, k, v, kv_mask, n_heads):
+def cross_attention(q, k, v, kv_mask, n_heads, drop=None, sub=None):
     """The global cross-attention core of MaskedMHA (blocks.py:374-389) on token-major ``q`` (B, T, C) and ``k`` / ``v`` (B, Lk, C), heads
     concatenated along C: softmax over the valid keys of the sequence, d^-1/4 on q and on k, masked keys filled with -inf -> (B, T, C).
     ``kv_mask``: (B, Lk) or (B, 1, Lk), None = all valid; every sequence needs a valid key.  There is no query mask.  Lk from 1 to 64,
-    head dimension 16, 32, 64 or 128."""
-    return _CrossAttentionFn.apply(q, k, v, kv_mask, n_heads)
+    head dimension 16, 32, 64 or 128.  ``drop`` with ``attn_p > 0``: nn.Dropout(attn_p) on the (B, H, T, Lk) map (blocks.py:388) at site
+    ``sub`` (DROP_ATTN), drawn inside the kernels, forward and backward."""
+    drop = _active(drop, 'cross_attention')
+    if drop is None or drop.attn_p == 0.0:
+        return _CrossAttentionFn.apply(q, k, v, kv_mask, n_heads)
+    return _CrossAttentionDropFn.apply(q, k, v, kv_mask, n_heads, drop.key, drop.site(DROP_ATTN if sub is None else sub), drop.attn_p, drop.b0)
 
 
 def adaln_modulate(x, mask, h, norm=True):
@@ -953,14 +1117,14 @@ def _repeat(x, kv_size, n):
     return x.repeat_interleave(torch.as_tensor(kv_size, device=x.device), dim=0, output_size=n)
 
 
-def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None):
+def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None, drop=None):
     """MaskedMHA.forward in its global branch as the fusion calls it (blocks.py:327-356, :374-393; k = v = kv, no dropout) on token-major
     ``q_in`` (B, T, Cq) and ``kv_in`` (B', Lk, Ckv), with ``mha`` a modeling.MaskedMHA of ``window_size = 0``:
     proj(cross_attention(query(q_in), key(kv_in), value(kv_in))) -> (B', T, out_dim).  ``kv_size`` (B,): how many of the B' key
     sequences belong to each query sequence; the PROJECTED query is repeated to match (:352-355).  Heads of 8 channels, narrower than
     ``cross_attention`` admits, run as zero-padded heads of 16 (``_narrow_head_attention``).  Self-attention (``q_in is kv_in``, no
     ``kv_size``) over more than 64 positions on heads of 32 or 64 channels runs on ``global_attention``, which has no limit on the
-    length; up to 64 positions nothing changes."""
+    length; up to 64 positions nothing changes.  ``drop``: its ``attn_p`` is the rate of attn_drop (:388) on the map."""
     if mha.window_size != 0:
         raise ValueError('xattn_mha: a MaskedMHA with window_size = 0 is required (the local branch is masked_mha)')
     q = masked_conv1d(q_in, None, mha.query.weight, mha.query.bias)
@@ -970,19 +1134,19 @@ def xattn_mha(q_in, kv_in, kv_mask, mha, kv_size=None):
         q = _repeat(q, kv_size, k.size(0))
     narrow = q.size(2) % mha.n_heads == 0 and q.size(2) // mha.n_heads == 8
     if q_in is kv_in and kv_size is None and k.size(1) > 64 and _global_head_limit(q.size(2), mha.n_heads) is None:
-        ctx = global_attention(q, k, v, kv_mask, mha.n_heads)
+        ctx = global_attention(q, k, v, kv_mask, mha.n_heads, **_drop_kw(drop))
     else:
-        ctx = (_narrow_head_attention if narrow else cross_attention)(q, k, v, kv_mask, mha.n_heads)
+        ctx = (_narrow_head_attention if narrow else cross_attention)(q, k, v, kv_mask, mha.n_heads, **_drop_kw(drop))
     return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
 
 
-def conv_xattn_layer(q, q_mask, kv, kv_mask, layer, kv_size=None):
-    """ConvXAttNLayer.forward (blocks.py:513-520; stride 1, no dropout) on token-major ``q`` (B, T, C) and ``kv`` (B', Lk, Ckv), with
+def conv_xattn_layer(q, q_mask, kv, kv_mask, layer, kv_size=None, drop=None):
+    """ConvXAttNLayer.forward (blocks.py:513-520; stride 1; of ``drop`` the map dropout of ``xattn_mha`` alone) on token-major ``q`` (B, T, C) and ``kv`` (B', Lk, Ckv), with
     ``layer`` a modeling.ConvXAttNLayer: xattn(q_norm(q_conv(q, q_mask)), kv) -> ((B', T, out_dim), the mask repeated like the batch)."""
     B, T, _ = q.shape
     (qc,), _ = depthwise_conv1d(q, q_mask, [layer.q_conv.conv.weight], 1)
     qc = channel_layer_norm(qc, layer.q_norm.weight, layer.q_norm.bias)
-    out = xattn_mha(qc, kv, kv_mask, layer.xattn, kv_size)
+    out = xattn_mha(qc, kv, kv_mask, layer.xattn, kv_size, **_drop_kw(drop))
     q_mask = _mask_rows(q_mask, B, T)
     if kv_size is not None and q_mask is not None and out.size(0) != q_mask.size(0):
         q_mask = _repeat(q_mask, kv_size, out.size(0))
@@ -996,12 +1160,14 @@ def transformer_decoder(q, q_mask, kv, kv_mask, block, kv_size=None, drop=None):
     queries (:641-642); the residual is masked again, normalised without affine parameters ('adaln') or left as it is ('affine'), and
     modulated by the two halves of the cross-attention output (:643-645); the FFN branch is masked, the output is not, so padded rows
     hold the shift.  ``drop`` (group DROP_G_FUSION): proj_drop on the (B', 2E, T) scale / shift tensor before the modulation (sub 0),
-    the FFN's dropouts (1, 2) and drop_path_ffn (4); the decoder has no drop_path_attn."""
+    the FFN's dropouts (1, 2) and drop_path_ffn (4), and with ``drop.attn_p`` attn_drop on the cross-attention map (6); the decoder has no
+    drop_path_attn."""
     B, T, _ = q.shape
     q_mask = torch.ones(B, T, dtype=torch.bool, device=q.device) if q_mask is None else _mask_rows(q_mask, B, T)
     q = _LayerScaleResidualFn.apply(q, None, None, q_mask, None)
     h, mask = conv_xattn_layer(channel_layer_norm(q, block.ln_xattn_q.weight, block.ln_xattn_q.bias), q_mask,
-                               channel_layer_norm(kv, block.ln_xattn_kv.weight, block.ln_xattn_kv.bias), kv_mask, block.xattn, kv_size)
+                               channel_layer_norm(kv, block.ln_xattn_kv.weight, block.ln_xattn_kv.bias), kv_mask, block.xattn, kv_size,
+                               **_drop_kw(_active(drop, 'transformer_decoder')))
     if kv_size is not None and q.size(0) != h.size(0):
         q = _repeat(q, kv_size, h.size(0))
     drop = _active(drop, 'transformer_decoder')
@@ -1010,10 +1176,11 @@ def transformer_decoder(q, q_mask, kv, kv_mask, block, kv_size=None, drop=None):
     return layer_scale_residual(q, h, block.drop_path_ffn.scale, h_mask=mask, drop=drop), mask
 
 
-def xattn_fusion(vid, vid_mask, text, text_mask, fusion, kv_size=None, drop=None):
+def xattn_fusion(vid, vid_mask, text, text_mask, fusion, kv_size=None, drop=None, group=DROP_G_FUSION, layer0=0):
     """XAttNFusion._forward (fusion.py:56-66) on token-major ``vid`` (B, T, E) and ``text`` (B', Lk, TE), with ``fusion`` a
     modeling.XAttNFusion: its decoder layers, ln_out, and the repeat by ``kv_size`` when no layer expanded the batch
-    -> (fused (B', T, E), mask (B', T)).  ``drop``: decoder layer i is layer i of group DROP_G_FUSION."""
+    -> (fused (B', T, E), mask (B', T)).  ``drop``: decoder layer i is layer ``layer0 + i`` of ``group`` (DROP_G_FUSION, layer0 = 0; the
+    fusion applied again to pyramid level l is DROP_G_FUSION2 with layer0 = l * n_layers: ``fuse_and_predict``)."""
     B, T, _ = vid.shape
     vid_mask = torch.ones(B, T, dtype=torch.bool, device=vid.device) if vid_mask is None else _mask_rows(vid_mask, B, T)
     drop = _active(drop, 'xattn_fusion')
@@ -1021,7 +1188,7 @@ def xattn_fusion(vid, vid_mask, text, text_mask, fusion, kv_size=None, drop=None
         if drop is None:
             vid, vid_mask = transformer_decoder(vid, vid_mask, text, text_mask, layer, kv_size)
         else:
-            vid, vid_mask = transformer_decoder(vid, vid_mask, text, text_mask, layer, kv_size, drop=drop.at(DROP_G_FUSION, i))
+            vid, vid_mask = transformer_decoder(vid, vid_mask, text, text_mask, layer, kv_size, drop=drop.at(group, layer0 + i))
     vid = channel_layer_norm(vid, fusion.ln_out.weight, fusion.ln_out.bias)
     if kv_size is not None and vid.size(0) != text.size(0):
         vid, vid_mask = _repeat(vid, kv_size, text.size(0)), _repeat(vid_mask, kv_size, text.size(0))
@@ -1159,14 +1326,15 @@ def tcn(logits1, mask0, tcn_module, dropout=None):
     return x if mask0 is None else _LayerScaleResidualFn.apply(x, None, None, _mask_rows(mask0, B, T0), None)
 
 
-def fuse_and_predict(fpn, fpn_masks, model, dropout=None, text=None, text_mask=None, kv_size=None):
+def fuse_and_predict(fpn, fpn_masks, model, dropout=None, text=None, text_mask=None, kv_size=None, fusion_drop=None):
     """PtTransformerEarlyFusionIterative.fuse_and_predict (model.py:442-471) on token-major pyramid levels ``fpn[l]`` (B, T0 >> l, E) with
     masks ``fpn_masks[l]`` (B, T0 >> l) or (B, 1, T0 >> l), ``model`` a modeling.PtTransformerEarlyFusionIterative -> (logits1, logits2,
     offsets, masks), tuples over the levels of (B', T_l), (B', T_l), (B', T_l, 2) and (B', T_l) bool: what ``loss.PointObjective`` takes.
     With ``model.second_fusion`` every level first goes through ``xattn_fusion`` against ``text`` (B', Lk, TE) / ``text_mask`` /
     ``kv_size``.  To the letter: the refined map is pooled down the pyramid with ``fpn_masks[i - 1]``, the pooled mask is discarded, and
     the heads see ``fpn_masks[i]``.  ``dropout``: None or (seed, p, b0) for the refinement TCN, the seed as ``model.enable_dropout``
-    hands it out (``model.last_dropout_seed``)."""
+    hands it out (``model.last_dropout_seed``).  ``fusion_drop`` (with ``model.second_fusion``): the fusion's dropouts at level l under
+    group DROP_G_FUSION2, layer ``l * n_layers + i`` -- the modules are the first fusion's, called again, so the call is part of the site."""
     n_levels = len(model.refine.layers)
     if len(fpn) != n_levels or len(fpn_masks) != n_levels:
         raise ValueError(f'fuse_and_predict: {len(fpn)} levels and {len(fpn_masks)} masks for a model of {n_levels} pyramid levels')
@@ -1184,7 +1352,12 @@ def fuse_and_predict(fpn, fpn_masks, model, dropout=None, text=None, text_mask=N
     if model.second_fusion:
         if text is None:
             raise ValueError('fuse_and_predict: a model with second_fusion needs the text')
-        fused = [xattn_fusion(x, m, text, text_mask, model.fusion, kv_size) for x, m in zip(fpn, masks)]
+        n_layers = len(model.fusion.layers)
+        fusion_drop = _active(fusion_drop, 'fuse_and_predict')
+        if fusion_drop is not None and n_levels * n_layers > 1 << 12:
+            raise ValueError(f'fuse_and_predict: {n_levels} levels x {n_layers} fusion layers do not fit the 4096 layers of a site group')
+        second = lambda l: {} if fusion_drop is None else dict(drop=fusion_drop, group=DROP_G_FUSION2, layer0=l * n_layers)
+        fused = [xattn_fusion(x, m, text, text_mask, model.fusion, kv_size, **second(l)) for l, (x, m) in enumerate(zip(fpn, masks))]
         fpn, masks = [f[0] for f in fused], [f[1] for f in fused]
     logits1 = [conv_head(x, m, model.cls_head) for x, m in zip(fpn, masks)]
     refined = tcn(torch.cat(logits1, dim=1), masks[0], model.refine, dropout)
@@ -1247,12 +1420,13 @@ def video_transformer(x, mask, vid_net, drop=None):
     return tuple(fpn), tuple(fpn_masks)
 
 
-def text_transformer(tokens, mask, text_net):
+def text_transformer(tokens, mask, text_net, drop=None):
     """TextTransformer.forward (text_net.py:158-188, the training branch) on token-major ``tokens`` (B, L, in_dim), with ``text_net`` a
     modeling.TextTransformer -> ((B, L [+ 1], TE), mask (B, L [+ 1])).  To the letter: the background token is prepended to every
     sequence and the mask is extended by its own first column (:179-182); the gradient of ``bkgd_token`` is the sum over the batch.
     The blocks are global self-attention: with L [+ 1] <= 64 positions heads of 16, 32, 64 or 128 channels, or of 8 (``xattn_mha``); longer
-    texts need heads of 32 or 64 channels (``global_attention``)."""
+    texts need heads of 32 or 64 channels (``global_attention``).  ``drop``: block i is layer i of group DROP_G_TEXT, with the sites of a
+    video-encoder block."""
     if not hasattr(text_net, 'bkgd_token') or not hasattr(text_net, 'transformer') or hasattr(text_net, 'attn_pool'):
         raise ValueError(f'text_transformer: {type(text_net).__name__} is not differentiable yet (TextIdentity\'s attention pool has no '
                          f'backward); a modeling.TextTransformer is required')
@@ -1265,6 +1439,7 @@ def text_transformer(tokens, mask, text_net):
     if text_net.bkgd_token is not None:
         x = torch.cat((text_net.bkgd_token.t()[None].expand(B, -1, -1).to(x.dtype), x), dim=1)
         mask = torch.cat((mask[:, :1], mask), dim=1)
-    for block in text_net.transformer:
-        x, _ = transformer_encoder(x, mask, block, narrow_heads=True)
+    drop = _active(drop, 'text_transformer')
+    for i, block in enumerate(text_net.transformer):
+        x, _ = transformer_encoder(x, mask, block, narrow_heads=True, **_drop_kw(None if drop is None else drop.at(DROP_G_TEXT, i)))
     return x, mask

@@ -15,6 +15,7 @@ from __future__ import annotations
 import copy
 import ctypes
 import math
+from collections import namedtuple
 from typing import List, Sequence, Tuple
 
 import torch
@@ -22,6 +23,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+
+# enable_dropout(sites=...) and what _train_dropout_rates() returns
+DROPOUT_SITES = ('engine', 'all')
+PartDropRates = namedtuple('PartDropRates', 'proj path attn')
+TrainDropRates = namedtuple('TrainDropRates', 'vid_net fusion text_net cdrop refine')
 
 __all__ = ['PtTransformerEarlyFusionIterative', 'PtTransformer', 'PtGenerator', 'create_model', 'sinusoid_encoding']
 
@@ -460,6 +466,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
 
     MODEL_KIND = 0
     _dropout = None                                 # enable_dropout: (refine_pdrop, private generator or None)
+    _dropout_sites = 'engine'                       # enable_dropout(sites=...): 'engine' or 'all'
     # float16 clip features (vid and shallow_vid both torch.float16) go to the engine as they are stored in ``forward(..., eval=True)``
     # and ``forward_videos`` (include/decafnet_hip_half.h); False: they are upcast to fp32 first, as every other dtype is
     half_features = True
@@ -518,23 +525,33 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         self.graph_mode = 'auto'
 
     # -- training-forward dropout ----------------------------------------------------------
-    def enable_dropout(self, seed=None, refine_pdrop=0.5):
+    def enable_dropout(self, seed=None, refine_pdrop=0.5, sites='engine'):
         """Turn on dropout and drop-path in the training forward (``forward(..., eval=False)``): opt's vid_net / fusion
         ``proj_pdrop`` and ``path_pdrop`` and ``refine_pdrop`` for the Dropout the reference hard-codes into every refinement TCN
         layer (tcn.py:5,13: 0.5).  The masks come from a counter-based stream (Philox4x32-10, include/decafnet_hip.h
         dcf_model_set_dropout), not from torch's: their distribution is the reference's, their bits are not torch's draws.
         seed=None: every training forward draws its 64-bit key from torch's default CPU generator (``torch.manual_seed``
         reproduces a run); an int seeds a private ``torch.Generator`` that supplies the keys.  ``last_dropout_seed`` holds the
-        key of the last training forward."""
+        key of the last training forward.
+        ``sites``: 'engine' (the default) is the set of sites above, for ``forward(..., eval=False)`` and for
+        ``train.training_forward`` alike, and every other rate is refused.  'all' is an opt-in of the autograd path
+        (``train.training_forward`` / ``TrainStep`` / ``DataParallelTrainStep``) alone, which then applies every rate the reference's
+        model constructors take: ``attn_pdrop`` on the attention maps of the video encoder, the fusion and the text encoder, the text
+        encoder's ``proj_pdrop`` / ``path_pdrop``, ``vid_net.cdrop`` on the clip features, and the fusion's dropouts again per pyramid
+        level with ``second_fusion=True`` (``_train_dropout_rates``); ``forward(..., eval=False)`` keeps refusing those rates."""
         refine_pdrop = float(refine_pdrop)
         if not 0.0 <= refine_pdrop < 1.0:
             raise ValueError(f'refine_pdrop = {refine_pdrop} must lie in [0, 1)')
+        if sites not in DROPOUT_SITES:
+            raise ValueError(f'enable_dropout: sites = {sites!r} (one of {DROPOUT_SITES})')
         gen = None if seed is None else torch.Generator().manual_seed(int(seed))
         self._dropout = (refine_pdrop, gen)
+        self._dropout_sites = sites
 
     def disable_dropout(self):
         """Back to the deterministic training forward (every dropout probability must then be 0, as before)."""
         self._dropout = None
+        self._dropout_sites = 'engine'
 
     def _dropout_rates(self):
         """(vid proj, vid path, fusion proj, fusion path, refine) for dcf_model_set_dropout -- or None without enable_dropout,
@@ -566,6 +583,36 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         for name, p in zip(('vid_net.proj_pdrop', 'vid_net.path_pdrop', 'fusion.proj_pdrop', 'fusion.path_pdrop', 'refine_pdrop'), rates):
             if not 0.0 <= p < 1.0:
                 raise ValueError(f'enable_dropout: {name} = {p} must lie in [0, 1)')
+        return rates
+
+    def _train_dropout_rates(self):
+        """What ``train.training_forward`` applies: None without ``enable_dropout()`` (after the refusals of ``_dropout_rates()``), else a
+        ``TrainDropRates``: proj / path / attn per part (``vid_net``, ``fusion``, ``text_net``), ``cdrop`` and ``refine``.  With
+        ``sites='engine'`` it holds the rates of ``_dropout_rates()`` and zeros elsewhere, after the same refusals.  With ``sites='all'``
+        every rate the reference's constructors take is admitted -- ``attn_pdrop`` of all three parts, the text encoder's rates,
+        ``vid_net.cdrop``, and ``second_fusion=True`` -- and checked to lie in [0, 1); the classes with one classification head stay
+        refused.  Raises before anything touches the GPU."""
+        if self._dropout is None or self._dropout_sites == 'engine':
+            r = self._dropout_rates()
+            if r is None:
+                return None
+            return TrainDropRates(PartDropRates(r[0], r[1], 0.0), PartDropRates(r[2], r[3], 0.0), PartDropRates(0.0, 0.0, 0.0), 0.0, r[4])
+        mo = self.opt['model'] if isinstance(self.opt, dict) else self.opt.model
+        prob = lambda part, key: float(dict(mo[part]).get(key, 0.0) or 0.0)
+        if self.MODEL_KIND != 0:
+            raise NotImplementedError(f'enable_dropout: {type(self).__name__} (one classification head) has no dropout forward; '
+                                      f'PtTransformerEarlyFusionIterative only')
+        parts = {part: PartDropRates(prob(part, 'proj_pdrop'), prob(part, 'path_pdrop'), prob(part, 'attn_pdrop'))
+                 for part in ('vid_net', 'fusion', 'text_net')}
+        rates = TrainDropRates(parts['vid_net'], parts['fusion'], parts['text_net'], prob('vid_net', 'cdrop'), self._dropout[0])
+        for part in ('vid_net', 'fusion', 'text_net'):
+            for key, p in zip(('proj_pdrop', 'path_pdrop', 'attn_pdrop'), parts[part]):
+                if not 0.0 <= p < 1.0:
+                    raise ValueError(f'enable_dropout: {part}.{key} = {p} must lie in [0, 1)')
+        if not 0.0 <= rates.cdrop < 1.0:
+            raise ValueError(f'enable_dropout: vid_net.cdrop = {rates.cdrop} must lie in [0, 1)')
+        if not 0.0 <= rates.refine < 1.0:
+            raise ValueError(f'enable_dropout: refine_pdrop = {rates.refine} must lie in [0, 1)')
         return rates
 
     def _next_dropout_seed(self):

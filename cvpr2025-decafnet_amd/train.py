@@ -7,8 +7,12 @@ coefficient, the fused Adam / AdamW update with the EMA copy (``optim``), schedu
 
 Dropout: after ``model.enable_dropout()`` the forward applies opt's vid_net / fusion ``proj_pdrop`` and ``path_pdrop`` and the
 refinement TCN's rate on the counter-based stream of the library (csrc/dropout.h), one 64-bit key per forward, drawn on the CPU; the
-backward recomputes the keep bits from the key (``autograd.DropSpec``).  Not implemented, and refused as before: attention-map dropout
-(``attn_pdrop``), channel dropout (``cdrop``), dropout in the text encoder, ``second_fusion=True`` with dropout.
+backward recomputes the keep bits from the key (``autograd.DropSpec``).  ``model.enable_dropout(sites='all')`` is the opt-in for the
+sites this path alone has (``model._train_dropout_rates()``): ``attn_pdrop`` on the attention maps of the video encoder (local window
+or ``mha_win_size = 0``), the fusion's cross attention and the text encoder, drawn inside the attention kernels, forward and backward
+(include/decafnet_hip_attn_drop.h); the text encoder's ``proj_pdrop`` / ``path_pdrop`` (group DROP_G_TEXT); the fusion's dropouts again
+per pyramid level with ``second_fusion=True`` (group DROP_G_FUSION2, layer ``l * n_layers + i``); and ``vid_net.cdrop`` on the clip
+features before ``vid_map``.  The one refusal that remains is ``cdrop`` with the shared front end or a ``scat`` model.
 
 ``DataParallelTrainStep``: the same step on every rank of a process group, what the reference gets from wrapping its model in
 DistributedDataParallel (worker_v2.py:278-280): parameters broadcast from rank 0, the gradients packed into buckets by a HIP kernel
@@ -66,7 +70,8 @@ include/decafnet_hip_front.h): what the inference engine does -- ``W[:, :D] . vi
 nothing of size B' T Cin exists in either direction.  'dense' stays the default (it is what tests/test_gpu_train_step.py pins bit
 for bit against ``run_step``).  ``opt.model.scat`` (the raw sidekick score as input channel 2 D + 1) trains through the shared
 path alone, whatever ``front_end`` says: the score channel is a rank-1 term there.  ``sfonly`` stays refused (the reference's
-training branch, model.py:606-612, never reads it), and so does ``cdrop``: a per-sample channel mask cannot share products.
+training branch, model.py:606-612, never reads it).  ``cdrop`` (with ``enable_dropout(sites='all')``) needs the dense front end and
+a model without ``scat``: a per-sample channel mask cannot share products, so the shared path raises ValueError.
 """
 import copy
 import os
@@ -89,8 +94,8 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     differentiated: the gate is a 0 / 1 weight), the product and the concatenation with the shallow features, vid_map, the text
     encoder, the first fusion, the video encoder, then the heads with the refinement stage (``autograd.fuse_and_predict``).
     ``dropout``: the (seed, p, b0) of ``autograd.fuse_and_predict`` for the refinement stage's dropout alone, None for none; only
-    for a model without ``enable_dropout()``.  With ``model.enable_dropout()`` the forward applies all five rates of
-    ``model._dropout_rates()`` with b0 = 0 under one 64-bit key: ``dropout_seed`` if given, else ``model._next_dropout_seed()``
+    for a model without ``enable_dropout()``.  With ``model.enable_dropout()`` the forward applies the rates of
+    ``model._train_dropout_rates()`` (the five of ``model._dropout_rates()``; with ``sites='all'`` every rate of opt) with b0 = 0 under one 64-bit key: ``dropout_seed`` if given, else ``model._next_dropout_seed()``
     (the CPU generator ``enable_dropout`` set up); the key is left in ``model.last_dropout_seed``.
     ``vid`` / ``shallow`` may be float16, both or neither.  With ``front_end='shared'`` (or a ``scat`` model) and
     ``model.half_features`` (default True) a float16 pair is read as it is stored -- dcf_op_sidekick_h for the scores,
@@ -111,7 +116,10 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
         raise NotImplementedError('training_forward: opt.model.sfonly is not implemented: the training branch of the reference '
                                   '(model.py:606-612) never reads it')
     shared = front_end == 'shared' or bool(model.scat)
-    rates = model._dropout_rates()                                  # None without enable_dropout(); refuses what the forward refuses
+    rates = model._train_dropout_rates()                            # None without enable_dropout(); refuses what has no kernel
+    if rates is not None and rates.cdrop > 0.0 and shared:
+        raise ValueError("training_forward: opt.model.vid_net.cdrop > 0 needs front_end='dense' on a model without scat: a per-sample "
+                         "channel mask cannot share the products of vid_map between the queries of a video")
     if rates is None and dropout_seed is not None:
         raise ValueError('training_forward: dropout_seed without model.enable_dropout()')
     if rates is not None and dropout is not None:
@@ -148,6 +156,15 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
         q += k
     gate, mask = torch.cat(gates), torch.cat(masks)
     kv_size = torch.tensor(sizes, device=vid.device)
+    vid_drop = fus_drop = text_drop = None
+    if rates is not None:                                           # one key per forward
+        seed = (model._next_dropout_seed() if dropout_seed is None else int(dropout_seed)) & ((1 << 64) - 1)
+        model.last_dropout_seed = seed
+        vid_drop = A.DropSpec(seed, 0, rates.vid_net.proj, rates.vid_net.path, attn_p=rates.vid_net.attn)
+        fus_drop = A.DropSpec(seed, 0, rates.fusion.proj, rates.fusion.path, attn_p=rates.fusion.attn)
+        text_drop = A.DropSpec(seed, 0, rates.text_net.proj, rates.text_net.path, attn_p=rates.text_net.attn)
+        if rates.refine > 0.0:
+            dropout = (seed, rates.refine, 0)
     if shared:                                                      # the products once per video: nothing is repeated or transposed
         vid_map = A.gated_vid_map(vid, shallow if model.msf else None, gate, mask, torch.cat(correls) if model.scat else None, sizes,
                                   model.vid_map.conv.weight, model.vid_map.conv.bias)
@@ -156,18 +173,16 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
         x = rep(vid) * gate[..., None]
         if model.msf:
             x = torch.cat([x, rep(shallow)], dim=2)
+        if rates is not None and rates.cdrop > 0.0:                 # model.py:614: nn.Dropout1d on the (B', Cin, T) tensor
+            x = A.channel_dropout(x, A.DropSpec(seed, 0, proj_p=rates.cdrop, group=A.DROP_G_INPUT))
         vid_map = A.masked_conv1d(x, mask, model.vid_map.conv.weight, model.vid_map.conv.bias)
-    text, text_mask = A.text_transformer(tokens.transpose(1, 2).contiguous(), token_masks.reshape(nq, -1), model.text_net)
-    vid_drop = fus_drop = None
-    if rates is not None:
-        seed = (model._next_dropout_seed() if dropout_seed is None else int(dropout_seed)) & ((1 << 64) - 1)
-        model.last_dropout_seed = seed
-        vid_drop, fus_drop = A.DropSpec(seed, 0, rates[0], rates[1]), A.DropSpec(seed, 0, rates[2], rates[3])
-        if rates[4] > 0.0:
-            dropout = (seed, rates[4], 0)
+    text, text_mask = A.text_transformer(tokens.transpose(1, 2).contiguous(), token_masks.reshape(nq, -1), model.text_net,
+                                         **({} if text_drop is None or not text_drop.active else {'drop': text_drop}))
     fused, fmask = A.xattn_fusion(vid_map, mask, text, text_mask, model.fusion, kv_size, **({} if fus_drop is None else {'drop': fus_drop}))
     fpn, fpn_masks = A.video_transformer(fused, fmask, model.vid_net, **({} if vid_drop is None else {'drop': vid_drop}))
     extra = dict(text=text, text_mask=text_mask, kv_size=kv_size) if model.second_fusion else {}
+    if model.second_fusion and fus_drop is not None and fus_drop.active:
+        extra['fusion_drop'] = fus_drop
     if dropout is not None:
         extra['dropout'] = dropout
     return A.fuse_and_predict(fpn, fpn_masks, model, **extra)
