@@ -89,6 +89,14 @@ def _mask_rows(mask, B, T):
     return (m if m.dtype == torch.bool else m != 0).contiguous()
 
 
+def _byte_mask(mask, B, T, name):
+    """(B, T) bool on the GPU or None, from (B, T) / (B, 1, T) of any integer type"""
+    m = _mask_rows(mask, B, T)
+    if m is not None and not m.is_cuda:
+        raise RuntimeError(f'{name}: the mask must be on the GPU (there is no CPU path)')
+    return m
+
+
 def _conv_forward(x, m, w, B, T):
     """Y (B, T, N) = conv(x * m) without the bias, through the forward's split-operand kernels"""
     N, Cin, k = w.shape
@@ -214,70 +222,64 @@ class _ChannelLayerNormFn(torch.autograd.Function):
                 gb.reshape(ctx.shapes[1]) if gb is not None else None, None)
 
 
+def _attn_operands(name, q, k, v, mask, cross=False):
+    """What every attention core starts from: q (B, T, C) and k / v (B, Lk, C) as fp32 rows whose shapes agree (self attention:
+    Lk = T), the key mask as (B, Lk) bool on the GPU -- ones for None: the forward cores read their mask unconditionally -- and an
+    empty output."""
+    qd, kd, vd = (_rows(z, name) for z in (q, k, v))
+    B, T, C = qd.shape
+    if cross:
+        if kd.shape != (B, kd.size(1), C) or vd.shape != kd.shape:
+            raise ValueError(f'{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree ((B, T, C) and (B, Lk, C))')
+    elif kd.shape != qd.shape or vd.shape != qd.shape:
+        raise ValueError(f'{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
+    m = _byte_mask(mask, B, kd.size(1), name)
+    if m is None:
+        m = torch.ones(B, kd.size(1), dtype=torch.bool, device=qd.device)
+    return qd, kd, vd, m, torch.empty_like(qd)
+
+
+def _map_drop(drop):
+    """the ``drop`` argument of an attention Function -- None, or (key, site, p, b0) of the dropout on its map -- as the exports take it"""
+    if drop is None:
+        return None
+    key, site, p, b0 = drop
+    return int(b0), int(key), int(site), float(p)
+
+
+def _attn_launch(plain, dropped, tensors, geom, drop):
+    """the export ``plain``; with dropout on the map ``dropped``, which takes the same arguments and then ``drop``"""
+    name, tail = (plain, ()) if drop is None else (dropped, drop)
+    _lib.check(getattr(_lib.lib(), name)(*(_lib.ptr(t) for t in tensors), *geom, *tail, _lib.current_stream()), name)
+
+
+def _attn_backward(ctx, go, plain, dropped, geom):
+    """dQ, dK, dV of an attention Function that saved (q, k, v, mask) and ``ctx.drop``.  With dropout nothing else was saved: the
+    backward draws the keep bits again from (key, site, b0)."""
+    q, k, v, m = ctx.saved_tensors
+    go = go.float().contiguous()
+    gq, gk, gv = (torch.empty_like(z) if need else None for z, need in zip((q, k, v), ctx.needs_input_grad[:3]))
+    if gq is not None or gk is not None or gv is not None:
+        _attn_launch(plain, dropped, (q, k, v, m, go, gq, gk, gv), geom, ctx.drop)
+    return gq, gk, gv
+
+
 class _WindowAttentionFn(torch.autograd.Function):
+    """``drop``: None, or (key, site, p, b0) of the dropout on the map (dcf_op_local_attn_drop / dcf_op_local_attn_drop_bwd)"""
+
     @staticmethod
-    def forward(ctx, q, k, v, mask, n_heads, window):
-        qd, kd, vd = (_rows(z, 'window_attention') for z in (q, k, v))
-        B, T, C = qd.shape
-        if kd.shape != qd.shape or vd.shape != qd.shape:
-            raise ValueError(f'window_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
+    def forward(ctx, q, k, v, mask, n_heads, window, drop):
         if window <= 0 or window % 2 == 0:
             raise ValueError(f'window_attention: window = {window} must be odd and positive (global attention is global_attention)')
-        m = _mask_rows(mask, B, T)
-        if m is None:
-            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)       # the forward core reads its mask unconditionally
-        o = torch.empty_like(qd)
-        _lib.check(_lib.lib().dcf_op_local_attn(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, C, int(n_heads), int(window),
-                                                _lib.current_stream()), 'dcf_op_local_attn')
-        ctx.save_for_backward(qd, kd, vd, m)
-        ctx.n_heads, ctx.window = int(n_heads), int(window)
-        return o
-
-    @staticmethod
-    def backward(ctx, go):
-        q, k, v, m = ctx.saved_tensors
-        B, T, C = q.shape
-        go = go.float().contiguous()
-        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
-        if gq is not None or gk is not None or gv is not None:
-            _lib.check(_lib.lib().dcf_op_local_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
-                                                        _lib.ptr(gv), B, T, C, ctx.n_heads, ctx.window, _lib.current_stream()),
-                       'dcf_op_local_attn_bwd')
-        return gq, gk, gv, None, None, None
-
-
-class _WindowAttentionDropFn(torch.autograd.Function):
-    """_WindowAttentionFn over dcf_op_local_attn_drop / dcf_op_local_attn_drop_bwd: it saves what that one saves and no mask of the
-    map; the backward draws the keep bits again from (key, site, b0)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, mask, n_heads, window, key, site, p, b0):
-        qd, kd, vd = (_rows(z, 'window_attention') for z in (q, k, v))
-        B, T, C = qd.shape
-        if kd.shape != qd.shape or vd.shape != qd.shape:
-            raise ValueError(f'window_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
-        if window <= 0 or window % 2 == 0:
-            raise ValueError(f'window_attention: window = {window} must be odd and positive (global attention is global_attention)')
-        m = _mask_rows(mask, B, T)
-        if m is None:
-            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)       # the forward core reads its mask unconditionally
-        o = torch.empty_like(qd)
-        ctx.geom = (B, T, C, int(n_heads), int(window), int(b0), int(key), int(site), float(p))
-        _lib.check(_lib.lib().dcf_op_local_attn_drop(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), *ctx.geom,
-                                                     _lib.current_stream()), 'dcf_op_local_attn_drop')
+        qd, kd, vd, m, o = _attn_operands('window_attention', q, k, v, mask)
+        ctx.geom, ctx.drop = (*qd.shape, int(n_heads), int(window)), _map_drop(drop)
+        _attn_launch('dcf_op_local_attn', 'dcf_op_local_attn_drop', (qd, kd, vd, m, o), ctx.geom, ctx.drop)
         ctx.save_for_backward(qd, kd, vd, m)
         return o
 
     @staticmethod
     def backward(ctx, go):
-        q, k, v, m = ctx.saved_tensors
-        go = go.float().contiguous()
-        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
-        if gq is not None or gk is not None or gv is not None:
-            _lib.check(_lib.lib().dcf_op_local_attn_drop_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq),
-                                                             _lib.ptr(gk), _lib.ptr(gv), *ctx.geom, _lib.current_stream()),
-                       'dcf_op_local_attn_drop_bwd')
-        return (gq, gk, gv) + (None,) * 7
+        return _attn_backward(ctx, go, 'dcf_op_local_attn_bwd', 'dcf_op_local_attn_drop_bwd', ctx.geom) + (None,) * 4
 
 
 _GLOBAL_HEAD_DIMS = (32, 64)     # the head dimensions of k_global_attn and of its backward
@@ -291,75 +293,25 @@ def _global_head_limit(C, n_heads):
 
 
 class _GlobalAttentionFn(torch.autograd.Function):
+    """``drop``: None, or (key, site, p, b0) of the dropout on the map (dcf_op_local_attn_drop with window = 0 /
+    dcf_op_global_attn_drop_bwd)"""
+
     @staticmethod
-    def forward(ctx, q, k, v, mask, n_heads):
+    def forward(ctx, q, k, v, mask, n_heads, drop):
         limit = _global_head_limit(q.size(-1), int(n_heads))
         if limit:
             raise ValueError(f'global_attention: {limit}')
-        qd, kd, vd = (_rows(z, 'global_attention') for z in (q, k, v))
-        B, T, C = qd.shape
-        if kd.shape != qd.shape or vd.shape != qd.shape:
-            raise ValueError(f'global_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
-        if C > 1024:
-            raise ValueError(f'global_attention: C = {C} (at most 1024)')
-        m = _byte_mask(mask, B, T, 'global_attention')
-        if m is None:
-            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)       # the forward core reads its mask unconditionally
-        o = torch.empty_like(qd)
-        _lib.check(_lib.lib().dcf_op_local_attn(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, C, int(n_heads), 0,
-                                                _lib.current_stream()), 'dcf_op_local_attn')
+        if q.size(-1) > 1024:
+            raise ValueError(f'global_attention: C = {q.size(-1)} (at most 1024)')
+        qd, kd, vd, m, o = _attn_operands('global_attention', q, k, v, mask)
+        ctx.geom, ctx.drop = (*qd.shape, int(n_heads)), _map_drop(drop)
+        _attn_launch('dcf_op_local_attn', 'dcf_op_local_attn_drop', (qd, kd, vd, m, o), ctx.geom + (0,), ctx.drop)
         ctx.save_for_backward(qd, kd, vd, m)
-        ctx.n_heads = int(n_heads)
         return o
 
     @staticmethod
     def backward(ctx, go):
-        q, k, v, m = ctx.saved_tensors
-        B, T, C = q.shape
-        go = go.float().contiguous()
-        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
-        if gq is not None or gk is not None or gv is not None:
-            _lib.check(_lib.lib().dcf_op_global_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
-                                                         _lib.ptr(gv), B, T, C, ctx.n_heads, _lib.current_stream()), 'dcf_op_global_attn_bwd')
-        return gq, gk, gv, None, None
-
-
-class _GlobalAttentionDropFn(torch.autograd.Function):
-    """_GlobalAttentionFn over dcf_op_local_attn_drop(window = 0) / dcf_op_global_attn_drop_bwd; no mask of the map is saved"""
-
-    @staticmethod
-    def forward(ctx, q, k, v, mask, n_heads, key, site, p, b0):
-        limit = _global_head_limit(q.size(-1), int(n_heads))
-        if limit:
-            raise ValueError(f'global_attention: {limit}')
-        qd, kd, vd = (_rows(z, 'global_attention') for z in (q, k, v))
-        B, T, C = qd.shape
-        if kd.shape != qd.shape or vd.shape != qd.shape:
-            raise ValueError(f'global_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree (self attention)')
-        if C > 1024:
-            raise ValueError(f'global_attention: C = {C} (at most 1024)')
-        m = _byte_mask(mask, B, T, 'global_attention')
-        if m is None:
-            m = torch.ones(B, T, dtype=torch.bool, device=qd.device)
-        o = torch.empty_like(qd)
-        ctx.tail = (int(b0), int(key), int(site), float(p))
-        _lib.check(_lib.lib().dcf_op_local_attn_drop(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, C, int(n_heads), 0,
-                                                     *ctx.tail, _lib.current_stream()), 'dcf_op_local_attn_drop')
-        ctx.save_for_backward(qd, kd, vd, m)
-        ctx.n_heads = int(n_heads)
-        return o
-
-    @staticmethod
-    def backward(ctx, go):
-        q, k, v, m = ctx.saved_tensors
-        B, T, C = q.shape
-        go = go.float().contiguous()
-        gq, gk, gv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
-        if gq is not None or gk is not None or gv is not None:
-            _lib.check(_lib.lib().dcf_op_global_attn_drop_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq),
-                                                              _lib.ptr(gk), _lib.ptr(gv), B, T, C, ctx.n_heads, *ctx.tail, _lib.current_stream()),
-                       'dcf_op_global_attn_drop_bwd')
-        return (gq, gk, gv) + (None,) * 6
+        return _attn_backward(ctx, go, 'dcf_op_global_attn_bwd', 'dcf_op_global_attn_drop_bwd', ctx.geom) + (None,) * 3
 
 
 def masked_conv1d(x, mask, weight, bias=None, stride=1):
@@ -496,10 +448,7 @@ def window_attention(q, k, v, mask, n_heads, window, drop=None, sub=None):
     ``drop`` with ``attn_p > 0``: nn.Dropout(attn_p) on the (B, H, T, window) softmax map (blocks.py:368) at site ``sub`` (DROP_ATTN) of
     the block ``drop`` names, drawn inside the kernels, forward and backward; with ``attn_p = 0`` the launches are those without it."""
     drop = _active(drop, 'window_attention')
-    if drop is None or drop.attn_p == 0.0:
-        return _WindowAttentionFn.apply(q, k, v, mask, n_heads, window)
-    return _WindowAttentionDropFn.apply(q, k, v, mask, n_heads, window, drop.key, drop.site(DROP_ATTN if sub is None else sub), drop.attn_p,
-                                        drop.b0)
+    return _WindowAttentionFn.apply(q, k, v, mask, n_heads, window, _map_site(drop, sub))
 
 
 def global_attention(q, k, v, mask, n_heads, drop=None, sub=None):
@@ -510,9 +459,7 @@ def global_attention(q, k, v, mask, n_heads, drop=None, sub=None):
     gradients.  Any T, head dimension 32 or 64, C <= 1024 (dcf_op_local_attn with window = 0, dcf_op_global_attn_bwd).  ``drop`` with
     ``attn_p > 0``: nn.Dropout(attn_p) on the (B, H, T, T) map (blocks.py:388) at site ``sub`` (DROP_ATTN), drawn inside the kernels."""
     drop = _active(drop, 'global_attention')
-    if drop is None or drop.attn_p == 0.0:
-        return _GlobalAttentionFn.apply(q, k, v, mask, n_heads)
-    return _GlobalAttentionDropFn.apply(q, k, v, mask, n_heads, drop.key, drop.site(DROP_ATTN if sub is None else sub), drop.attn_p, drop.b0)
+    return _GlobalAttentionFn.apply(q, k, v, mask, n_heads, _map_site(drop, sub))
 
 
 def masked_mha(q_in, k_in, v_in, mask, mha, drop=None):
@@ -535,14 +482,6 @@ def masked_mha(q_in, k_in, v_in, mask, mha, drop=None):
     else:
         ctx = window_attention(q, k, v, mask, mha.n_heads, mha.window_size, **_drop_kw(drop))
     return masked_conv1d(ctx, None, mha.proj.weight, mha.proj.bias)
-
-
-def _byte_mask(mask, B, T, name):
-    """(B, T) bool on the GPU or None, from (B, T) / (B, 1, T) of any integer type"""
-    m = _mask_rows(mask, B, T)
-    if m is not None and not m.is_cuda:
-        raise RuntimeError(f'{name}: the mask must be on the GPU (there is no CPU path)')
-    return m
 
 
 class _DepthwiseConv1dFn(torch.autograd.Function):
@@ -711,6 +650,14 @@ class DropSpec(namedtuple('DropSpec', 'seed b0 proj_p path_p group layer attn_p'
 def _drop_kw(drop):
     """the ``drop`` keyword of an inner call, passed on only where there is one: without dropout the calls are what they were"""
     return {} if drop is None else {'drop': drop}
+
+
+def _map_site(drop, sub):
+    """the ``drop`` argument of an attention Function: (key, site, p, b0) of the dropout on its map at site ``sub`` (DROP_ATTN) of the
+    block ``drop`` names, or None where there is none (``attn_p = 0`` included: the launches are then those without it)"""
+    if drop is None or drop.attn_p == 0.0:
+        return None
+    return drop.key, drop.site(DROP_ATTN if sub is None else sub), drop.attn_p, drop.b0
 
 
 def _active(drop, name):
@@ -999,70 +946,23 @@ def _narrow_head_attention(q, k, v, kv_mask, n_heads, drop=None):
 
 
 class _CrossAttentionFn(torch.autograd.Function):
+    """``drop``: None, or (key, site, p, b0) of the dropout on the map (dcf_op_xattn_drop / dcf_op_xattn_drop_bwd)"""
+
     @staticmethod
-    def forward(ctx, q, k, v, kv_mask, n_heads):
-        qd, kd, vd = (_rows(z, 'cross_attention') for z in (q, k, v))
+    def forward(ctx, q, k, v, kv_mask, n_heads, drop):
+        qd, kd, vd, m, o = _attn_operands('cross_attention', q, k, v, kv_mask, cross=True)
         B, T, C = qd.shape
-        Lk = kd.size(1)
-        if kd.shape != (B, Lk, C) or vd.shape != kd.shape:
-            raise ValueError(f'cross_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree ((B, T, C) and (B, Lk, C))')
-        limit = _cross_attention_limit(Lk, C, n_heads)
+        limit = _cross_attention_limit(kd.size(1), C, n_heads)
         if limit:
             raise ValueError(limit)
-        m = _byte_mask(kv_mask, B, Lk, 'cross_attention')
-        if m is None:
-            m = torch.ones(B, Lk, dtype=torch.bool, device=qd.device)      # the forward core reads its mask unconditionally
-        o = torch.empty_like(qd)
-        _lib.check(_lib.lib().dcf_op_xattn(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), B, T, Lk, C, int(n_heads),
-                                           _lib.current_stream()), 'dcf_op_xattn')
-        ctx.save_for_backward(qd, kd, vd, m)
-        ctx.n_heads = int(n_heads)
-        return o
-
-    @staticmethod
-    def backward(ctx, go):
-        q, k, v, m = ctx.saved_tensors
-        B, T, C = q.shape
-        go = go.float().contiguous()
-        gq, gk, gv = (torch.empty_like(z) if need else None for z, need in zip((q, k, v), ctx.needs_input_grad[:3]))
-        if gq is not None or gk is not None or gv is not None:
-            _lib.check(_lib.lib().dcf_op_xattn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
-                                                   _lib.ptr(gv), B, T, k.size(1), C, ctx.n_heads, _lib.current_stream()), 'dcf_op_xattn_bwd')
-        return gq, gk, gv, None, None
-
-
-class _CrossAttentionDropFn(torch.autograd.Function):
-    """_CrossAttentionFn over dcf_op_xattn_drop / dcf_op_xattn_drop_bwd; no mask of the map is saved"""
-
-    @staticmethod
-    def forward(ctx, q, k, v, kv_mask, n_heads, key, site, p, b0):
-        qd, kd, vd = (_rows(z, 'cross_attention') for z in (q, k, v))
-        B, T, C = qd.shape
-        Lk = kd.size(1)
-        if kd.shape != (B, Lk, C) or vd.shape != kd.shape:
-            raise ValueError(f'cross_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree ((B, T, C) and (B, Lk, C))')
-        limit = _cross_attention_limit(Lk, C, n_heads)
-        if limit:
-            raise ValueError(limit)
-        m = _byte_mask(kv_mask, B, Lk, 'cross_attention')
-        if m is None:
-            m = torch.ones(B, Lk, dtype=torch.bool, device=qd.device)
-        o = torch.empty_like(qd)
-        ctx.geom = (B, T, Lk, C, int(n_heads), int(b0), int(key), int(site), float(p))
-        _lib.check(_lib.lib().dcf_op_xattn_drop(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(m), _lib.ptr(o), *ctx.geom,
-                                                _lib.current_stream()), 'dcf_op_xattn_drop')
+        ctx.geom, ctx.drop = (B, T, kd.size(1), C, int(n_heads)), _map_drop(drop)
+        _attn_launch('dcf_op_xattn', 'dcf_op_xattn_drop', (qd, kd, vd, m, o), ctx.geom, ctx.drop)
         ctx.save_for_backward(qd, kd, vd, m)
         return o
 
     @staticmethod
     def backward(ctx, go):
-        q, k, v, m = ctx.saved_tensors
-        go = go.float().contiguous()
-        gq, gk, gv = (torch.empty_like(z) if need else None for z, need in zip((q, k, v), ctx.needs_input_grad[:3]))
-        if gq is not None or gk is not None or gv is not None:
-            _lib.check(_lib.lib().dcf_op_xattn_drop_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(m), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
-                                                        _lib.ptr(gv), *ctx.geom, _lib.current_stream()), 'dcf_op_xattn_drop_bwd')
-        return (gq, gk, gv) + (None,) * 6
+        return _attn_backward(ctx, go, 'dcf_op_xattn_bwd', 'dcf_op_xattn_drop_bwd', ctx.geom) + (None,) * 3
 
 
 class _AdaLnFn(torch.autograd.Function):
@@ -1100,9 +1000,7 @@ def cross_attention(q, k, v, kv_mask, n_heads, drop=None, sub=None):
     head dimension 16, 32, 64 or 128.  ``drop`` with ``attn_p > 0``: nn.Dropout(attn_p) on the (B, H, T, Lk) map (blocks.py:388) at site
     ``sub`` (DROP_ATTN), drawn inside the kernels, forward and backward."""
     drop = _active(drop, 'cross_attention')
-    if drop is None or drop.attn_p == 0.0:
-        return _CrossAttentionFn.apply(q, k, v, kv_mask, n_heads)
-    return _CrossAttentionDropFn.apply(q, k, v, kv_mask, n_heads, drop.key, drop.site(DROP_ATTN if sub is None else sub), drop.attn_p, drop.b0)
+    return _CrossAttentionFn.apply(q, k, v, kv_mask, n_heads, _map_site(drop, sub))
 
 
 def adaln_modulate(x, mask, h, norm=True):

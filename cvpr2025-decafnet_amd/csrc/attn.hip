@@ -9,7 +9,7 @@
 //            and one write of the context -- 8 B/channel/clip, the algorithmic minimum.
 //            A VALU variant (lane owns 4 channels, online softmax) serves the shapes the MFMA tiling
 //            does not cover.
-//  * local:  sliding-window self attention |i-j| <= w/2 (MaskedMHA local branch, blocks.py:204-325,
+//  * local:  sliding-window self attention |i-j| <= w/2 (k_local_attn of local_attn_kernels.h; MaskedMHA local branch, blocks.py:204-325,
 //            357-373, restated as a band).  A wavefront owns one clip row; its <= w neighbour K/V
 //            rows come from L1/L2; a lane owns 4 consecutive channels, a head is a group of d/4 adjacent
 //            lanes, the q.k dot product is a 4-FMA partial + log2(d/4) cross-lane adds, and the softmax
@@ -18,22 +18,9 @@
 
 #include <cstdlib>
 #include "common.h"
+#include "local_attn_kernels.h"        // k_local_attn, head_sum, fast_exp, dot4, the table of row shapes
 
 namespace dcf {
-
-template <int LPH>
-__device__ __forceinline__ float head_sum(float v) {
-  if constexpr (LPH == 1) return v;
-  else return group_sum<LPH>(v);
-}
-
-// exp(x) for x <= 0 (softmax after max subtraction) as one v_exp_f32: exp2(x * log2(e)).  Relative error
-// ~ (1 + |x|) * 2^-23; arguments below -126/log2(e) flush to 0 exactly like the tail of expf would round.
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-
-__device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) {
-  return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
-}
 
 // ------------------------------------------------------------------------------------------
 // cross attention
@@ -380,110 +367,6 @@ __global__ __launch_bounds__(256) void k_xattn_mfma(XAttnArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------
-// sliding-window self attention.  One wave per query row, 8 waves per SIMD.  Measured alternatives (level 0, 26 us):
-// all K/V rows of the window requested up front (4 waves/SIMD) 0.107 -> 0.120 ms per step; K/V of a 16-row strip staged
-// once through LDS (3 workgroups per CU) 0.157; a strip of queries per wave with the window in a register ring 0.275 ->
-// 0.314 ms per five-video forward (profiles/r02_gemm_operand_stream.md).
-// ------------------------------------------------------------------------------------------
-constexpr int LA_QPW = 2;      // (four rows per wave at 6 waves per SIMD: 0.251 ms per five-video forward against 0.231; one row: 0.256)
-// WMAX > 0: windows of at most WMAX keys.  A wave takes LA_QPW = two consecutive query rows: their windows overlap in all but one key,
-// so the 2 * (WMAX + 1) K / V row loads serve both (10 KiB instead of 18 KiB per query through the vector-memory path at
-// w = 9, which is what bounds this kernel).  The key loop is fully unrolled (no loop-carried registers: the rows of the
-// next keys stay in flight across the score -> exp -> accumulate chain of the current one with counted waits) and capped at
-// 64 registers = 8 waves per SIMD so that the scheduler cannot hoist the whole window's loads.
-// WMAX = 0: any window, one query per wave, one round trip per key.
-// EAGER (WMAX > 0; small grids: the upper pyramid levels of one video): every K / V row of the wave's window requested at once.  With a
-// few hundred waves on the chip nothing hides a round trip (1 - 2 us from the Infinity Cache, where the projections' output lies), and the
-// two-row ring above makes a wave pay five of them in a row: 6.5 -> 3.6 us per launch at <= 4 096 rows.  Same operations, same bits.
-template <int NCH, int LPH, bool FULL, int WMAX, bool EAGER = false>
-__global__ __launch_bounds__(256, EAGER ? 2 : (WMAX > 0 && NCH == 1 ? 8 : 4)) void k_local_attn(LocalAttnArgs p) {
-  constexpr int QPW = WMAX > 0 ? LA_QPW : 1;           // query rows per wave
-  const int lane = threadIdx.x & 63;
-  const int wps = (p.T + QPW - 1) / QPW;               // waves per sequence
-  const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: the key loop is uniform
-  if (w >= (int64_t)p.B * wps) return;
-  const int C = FULL ? 256 * NCH : p.C;                 // FULL: every lane chunk exists, no per-lane channel predicate
-  const int t = (int)(w % wps) * QPW;
-  const int64_t base = (w / wps) * p.T, r = base + t;
-  const int half = p.window / 2;
-  const float scale = 1.0f / sqrtf(sqrtf((float)(C / p.heads)));
-  // query z of the wave is row t + z (T may be odd: the second one may not exist); out-of-range keys are -inf (blocks.py:260-261)
-  const int nq = min(QPW, p.T - t);
-  const int lo = max(t - half, 0), hi = min(t + (nq - 1) + half, p.T - 1);
-  // validity of the window's keys: one mask byte per lane (lane l <-> key lo + l), one ballot
-  unsigned long long km = 0ull;
-  if constexpr (WMAX > 0) km = __ballot(lane <= hi - lo && p.mask[base + lo + lane] != 0);
-  bool live[QPW];
-#pragma unroll
-  for (int z = 0; z < QPW; ++z) live[z] = z < nq && p.mask[r + (z < nq ? z : 0)] != 0;   // padded query rows are forced to 0 (blocks.py:293)
-  auto fetch = [&](int u, Row<NCH>& k, Row<NCH>& v) __attribute__((always_inline)) {
-    k.load(p.K + (base + u) * C, C, lane);
-    v.load(p.V + (base + u) * C, C, lane);
-  };
-  constexpr int NKB = EAGER ? WMAX + QPW - 1 : 2;
-  static_assert(!EAGER || WMAX > 0, "EAGER needs a bounded window");
-  Row<NCH> kb[NKB], vb[NKB];
-  if constexpr (EAGER) {
-#pragma unroll
-    for (int i = 0; i < NKB; ++i) fetch(lo + i <= hi ? lo + i : hi, kb[i], vb[i]);
-  } else if constexpr (WMAX > 0) {
-    fetch(lo, kb[0], vb[0]);
-    fetch(lo + 1 <= hi ? lo + 1 : hi, kb[1], vb[1]);
-  }
-  Row<NCH> q[QPW];
-  f32x4 acc[QPW][NCH];
-  float m[QPW][NCH], l[QPW][NCH];
-#pragma unroll
-  for (int z = 0; z < QPW; ++z) {
-    q[z].load(p.Q + (r + (z < nq ? z : 0)) * C, C, lane);
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) { q[z].v[j] *= scale; acc[z][j] = f32x4{0.f, 0.f, 0.f, 0.f}; m[z][j] = -INFINITY; l[z][j] = 0.f; }
-  }
-  auto key = [&](int z, bool valid, const Row<NCH>& k, const Row<NCH>& v) __attribute__((always_inline)) {
-    const float pen = valid ? 0.f : -1e4f;             // padded keys get a finite -1e4 (blocks.py:279)
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      float s = head_sum<LPH>(dot4(q[z].v[j], k.v[j] * scale)) + pen;
-      float mn = fmaxf(m[z][j], s);
-      float corr = fast_exp(m[z][j] - mn);             // exp(-inf) = 0 on the first key; v_exp_f32 instead of ~12-instruction expf
-      float e = fast_exp(s - mn);
-      acc[z][j] = acc[z][j] * corr + e * v.v[j];
-      l[z][j] = l[z][j] * corr + e;
-      m[z][j] = mn;
-    }
-  };
-  if constexpr (WMAX > 0) {
-#pragma unroll
-    for (int i = 0; i < WMAX + QPW - 1; ++i) {
-      const int u = lo + i;
-      if (u > hi) break;
-      const bool valid = ((km >> i) & 1ull) != 0;
-#pragma unroll
-      for (int z = 0; z < QPW; ++z)
-        if (live[z] && u >= t + z - half && u <= t + z + half) key(z, valid, kb[EAGER ? i : (i & 1)], vb[EAGER ? i : (i & 1)]);
-      if constexpr (!EAGER) {
-        if (i + 2 < WMAX + QPW - 1 && u + 2 <= hi) fetch(u + 2, kb[i & 1], vb[i & 1]);   // this register set is free again
-      }
-    }
-  } else {
-    if (live[0]) {
-      for (int u = lo; u <= hi; ++u) {
-        fetch(u, kb[0], vb[0]);
-        key(0, p.mask[base + u] != 0, kb[0], vb[0]);
-      }
-    }
-  }
-#pragma unroll
-  for (int z = 0; z < QPW; ++z) {
-    if (z >= nq) break;
-    Row<NCH> o;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) o.v[j] = live[z] ? acc[z][j] / l[z][j] : f32x4{0.f, 0.f, 0.f, 0.f};
-    o.store(p.O + (r + z) * C, C, lane);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 #define DISPATCH_ATTN(KERNEL, C, heads, ...)                                                         \
@@ -495,26 +378,7 @@ __global__ __launch_bounds__(256, EAGER ? 2 : (WMAX > 0 && NCH == 1 ? 8 : 4)) vo
               "attention: unsupported C=%d / head dim=%d (need power-of-two head dim in [4,256], C<=1024)", (int)(C), _d); \
     const int _lph = _d / 4;                                                                         \
     bool _ok = true;                                                                                 \
-    switch (_n * 100 + _lph) {                                                                       \
-      case 101: KERNEL(1, 1, __VA_ARGS__); break;                                                    \
-      case 102: KERNEL(1, 2, __VA_ARGS__); break;                                                    \
-      case 104: KERNEL(1, 4, __VA_ARGS__); break;                                                    \
-      case 108: KERNEL(1, 8, __VA_ARGS__); break;                                                    \
-      case 116: KERNEL(1, 16, __VA_ARGS__); break;                                                   \
-      case 132: KERNEL(1, 32, __VA_ARGS__); break;                                                   \
-      case 164: KERNEL(1, 64, __VA_ARGS__); break;                                                   \
-      case 208: KERNEL(2, 8, __VA_ARGS__); break;                                                    \
-      case 216: KERNEL(2, 16, __VA_ARGS__); break;                                                   \
-      case 232: KERNEL(2, 32, __VA_ARGS__); break;                                                   \
-      case 264: KERNEL(2, 64, __VA_ARGS__); break;                                                   \
-      case 316: KERNEL(3, 16, __VA_ARGS__); break;                                                   \
-      case 332: KERNEL(3, 32, __VA_ARGS__); break;                                                   \
-      case 364: KERNEL(3, 64, __VA_ARGS__); break;                                                   \
-      case 416: KERNEL(4, 16, __VA_ARGS__); break;                                                   \
-      case 432: KERNEL(4, 32, __VA_ARGS__); break;                                                   \
-      case 464: KERNEL(4, 64, __VA_ARGS__); break;                                                   \
-      default: _ok = false;                                                                          \
-    }                                                                                                \
+    DCF_ATTN_ROW_SHAPES(_n, _lph, _ok, KERNEL, __VA_ARGS__);                                         \
     DCF_CHECK(_ok, "attention: no kernel for C=%d heads=%d", (int)(C), (int)(heads));               \
     DCF_HIP(hipGetLastError());                                                                      \
   } while (0)

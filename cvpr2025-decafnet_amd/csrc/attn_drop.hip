@@ -1,29 +1,16 @@
 // Attention-map dropout inside the attention cores, forward and backward -- the sliding-window core first, global self attention and
 // cross attention in the section "dense attention" further down -- and channel dropout (include/decafnet_hip_attn_drop.h).  The map
-// never exists in memory: k_local_attn (attn.hip) and its backward (attn_grad.hip) hold it in registers, so the keep bits are drawn
-// where the map element is formed.
+// never exists in memory: the attention kernels hold it in registers, so the keep bits are drawn where the map element is formed.
 //
-// The kernels are those two files' kernels with one more factor, written again here so that the released exports keep their compiled
-// code: the same data layout (a wave owns a query row -- two in the unrolled forward --, a lane owns 4 consecutive channels of each
-// 256-channel chunk, a head is a group of LPH = d / 4 adjacent lanes), the same expressions in the same order.  With P the softmax
-// map, k the keep factor (scale = 1 / (1 - p) or 0) and Pd = k o P:
-//   O_t = sum_j Pd_tj v_j            dV_j = sum_t Pd_tj dO_t          dPd_tj = dO_t . v_j        dP = k o dPd
-//   delta_t = sum_j Pd_tj dPd_tj     dS = P o (dP - delta)            dQ, dK from dS as in attn_grad.hip
-// The forward carries the softmax online, so the factor multiplies the un-normalised weight e = exp(s - m) on its way into the
-// accumulator, not on its way into the running sum: O = (sum_j k e_j v_j) / (sum_j e_j).
+// The sliding-window kernels are k_local_attn, k_attn_bwd_q and k_attn_bwd_kv of local_attn_kernels.h, instantiated here on
+// LocalAttnDropArgs: one source with the dropout-free kernels of attn.hip and attn_grad.hip, the keep factor switched in at compile
+// time.  That header has the arithmetic and the layout of the keep bits.
 //
-// p = 0 runs the dropout-free kernels themselves (launch_local_attn, launch_local_attn_bwd; the dense forms call their exports):
-// the bits of the dropout-free exports by construction.  A factor of 1.0f changes no bit either, but a second copy of an expression like D * corr + e * dP is contracted into
-// an FMA per instantiation, and the compiler took the other product in one variant here (the loop form of the query side: dQ off by
-// an ulp at p = 0); equal bits must not rest on that.  The kernels below therefore run with p > 0 only.
-//
-// Keep bits.  Element (b, h, t, slot) of the reference's (bs, H, T, W) map has index e = (((b0 + b) H + h) T + t) W + slot; slot is
-// key t - W / 2 + slot.  The W elements of a (row, head) are consecutive, so they lie in at most (W + 6) / 4 counter blocks of the
-// Philox stream.  For W <= 32 the lanes of a head's group draw different blocks of the row and OR their words together with lane
-// permutes: one 32-bit word per (row, head) and chunk, bit `slot` = kept, one Philox block per lane and row at W = 9 / 19 with d >= 24
-// instead of one per lane and key.  The backward's query-side kernel leaves that word in the fourth slot of the row statistics, where
-// the key-side gather -- which meets every (query, key) pair from the key's side, a different row per pair -- picks it up with the
-// statistics it loads anyway.  Wider windows draw per element, on both sides.
+// p = 0 runs the dropout-free instantiations themselves (launch_local_attn, launch_local_attn_bwd; the dense forms call their
+// exports): the bits of the dropout-free exports by construction.  A factor of 1.0f changes no bit either, but a second copy of an
+// expression like D * corr + e * dP is contracted into an FMA per instantiation, and the compiler took the other product in one
+// variant (the loop form of the query side: dQ off by an ulp at p = 0); equal bits must not rest on that.  The instantiations below
+// therefore run with p > 0 only.
 #include "attn_drop.h"
 
 #include "attn.h"
@@ -33,383 +20,9 @@
 #include "../../include/decafnet_hip_attn_drop.h"
 #include "dropout.h"
 #include "grad_common.h"
+#include "local_attn_kernels.h"
 
 namespace dcf {
-
-constexpr int AD_PACK_MAX = 32;        // widest window whose keep bits are packed into one word per (row, head)
-
-template <int LPH>
-__device__ __forceinline__ float ad_head_sum(float v) {
-  if constexpr (LPH == 1) return v;
-  else return group_sum<LPH>(v);
-}
-
-// the forward's exp and 4-channel partial (attn.hip)
-__device__ __forceinline__ float ad_fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float ad_dot4(const f32x4& a, const f32x4& b) {
-  return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
-}
-
-template <int NCH>
-__device__ __forceinline__ void ad_scale_row(Row<NCH>& r, float s) {
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) r.v[j] *= s;
-}
-
-// keep bits of the W (<= 32) elements e0 .. e0 + W - 1 of one (row, head): bit slot <-> element e0 + slot.  The LPH lanes of the head
-// take the row's counter blocks in turn (the row starts at word e0 & 3 of its first block) and OR their parts over the group; every
-// lane of the wave must call it (the exchange is a lane permute).
-template <int LPH>
-__device__ __forceinline__ uint32_t row_keep_bits(uint64_t seed, uint32_t site, float p, uint64_t e0, int W, int lane) {
-  const uint64_t blk0 = e0 >> 2;
-  const int off = (int)(e0 & 3), nblk = (off + W + 3) >> 2, nmax = (W + 6) >> 2;   // nmax: the wave-uniform bound of nblk
-  uint32_t bits = 0;
-  for (int i0 = 0; i0 < nmax; i0 += LPH) {
-    const int i = i0 + (lane & (LPH - 1));
-    if (i < nblk) {
-      const Philox4 v = drop_block(seed, site, blk0 + (uint64_t)i);
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const int slot = 4 * i + w - off;
-        if (slot >= 0 && slot < W) bits |= (uint32_t)drop_keep_word(philox_word(v, w), p) << slot;
-      }
-    }
-  }
-#pragma unroll
-  for (int s = 1; s < LPH; s <<= 1) bits |= (uint32_t)__shfl_xor((int)bits, s);
-  return bits;
-}
-
-// the keep decisions of one query row as a lane sees them: per 256-channel chunk the lane's head, hence its own word / first element
-template <int NCH, int LPH>
-struct RowKeep {
-  uint32_t bits[NCH];
-  uint64_t e0[NCH];
-  // row t of sequence bg = b0 + b of the reference's batch
-  __device__ __forceinline__ void init(const LocalAttnDropArgs& p, int64_t bg, int t, int lane, bool packed) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      const int hd = (64 * j + lane) / LPH;
-      e0[j] = (uint64_t)(((bg * p.heads + hd) * (int64_t)p.T + t) * (int64_t)p.window);
-      bits[j] = packed ? row_keep_bits<LPH>(p.seed, p.site, p.p, e0[j], p.window, lane) : 0u;
-    }
-  }
-  __device__ __forceinline__ bool kept(const LocalAttnDropArgs& p, int j, int slot, bool packed) const {
-    if (packed) return ((bits[j] >> slot) & 1u) != 0;
-    return drop_keep(p.seed, p.site, e0[j] + (uint64_t)slot, p.p);
-  }
-};
-
-// ------------------------------------------------------------------------------------------
-// forward: k_local_attn (attn.hip) with the keep factor on the weight that enters the accumulator
-// ------------------------------------------------------------------------------------------
-constexpr int AD_QPW = 2;              // query rows per wave of the unrolled variants (LA_QPW, attn.hip)
-
-template <int NCH, int LPH, int WMAX>
-__global__ __launch_bounds__(256) void k_local_attn_drop(LocalAttnDropArgs p) {
-  constexpr int QPW = WMAX > 0 ? AD_QPW : 1;
-  const int lane = threadIdx.x & 63;
-  const int wps = (p.T + QPW - 1) / QPW;               // waves per sequence
-  const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (w >= (int64_t)p.B * wps) return;
-  const int C = p.C;
-  const int t = (int)(w % wps) * QPW;
-  const int64_t base = (w / wps) * p.T, r = base + t;
-  const int half = p.window / 2;
-  const float scale = 1.0f / sqrtf(sqrtf((float)(C / p.heads)));
-  const bool packed = WMAX > 0 || p.window <= AD_PACK_MAX;
-  const int nq = min(QPW, p.T - t);
-  const int lo = max(t - half, 0), hi = min(t + (nq - 1) + half, p.T - 1);
-  unsigned long long km = 0ull;
-  if constexpr (WMAX > 0) km = __ballot(lane <= hi - lo && p.mask[base + lo + lane] != 0);
-  bool live[QPW];
-  RowKeep<NCH, LPH> keep[QPW];
-#pragma unroll
-  for (int z = 0; z < QPW; ++z) {
-    live[z] = z < nq && p.mask[r + (z < nq ? z : 0)] != 0;       // padded query rows are forced to 0 (blocks.py:293)
-    keep[z].init(p, p.b0 + w / wps, t + z, lane, packed);
-  }
-  auto fetch = [&](int u, Row<NCH>& k, Row<NCH>& v) __attribute__((always_inline)) {
-    k.load(p.K + (base + u) * C, C, lane);
-    v.load(p.V + (base + u) * C, C, lane);
-  };
-  Row<NCH> kb[2], vb[2];
-  if constexpr (WMAX > 0) {
-    fetch(lo, kb[0], vb[0]);
-    fetch(lo + 1 <= hi ? lo + 1 : hi, kb[1], vb[1]);
-  }
-  Row<NCH> q[QPW];
-  f32x4 acc[QPW][NCH];
-  float m[QPW][NCH], l[QPW][NCH];
-#pragma unroll
-  for (int z = 0; z < QPW; ++z) {
-    q[z].load(p.Q + (r + (z < nq ? z : 0)) * C, C, lane);
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) { q[z].v[j] *= scale; acc[z][j] = f32x4{0.f, 0.f, 0.f, 0.f}; m[z][j] = -INFINITY; l[z][j] = 0.f; }
-  }
-  // key u of query z is slot u - (t + z - half) of that row of the map
-  auto key = [&](int z, bool valid, int u, const Row<NCH>& k, const Row<NCH>& v) __attribute__((always_inline)) {
-    const float pen = valid ? 0.f : -1e4f;             // padded keys get a finite -1e4 (blocks.py:279)
-    const int slot = u - (t + z - half);
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      float s = ad_head_sum<LPH>(ad_dot4(q[z].v[j], k.v[j] * scale)) + pen;
-      float mn = fmaxf(m[z][j], s);
-      float corr = ad_fast_exp(m[z][j] - mn);          // exp(-inf) = 0 on the first key
-      float e = ad_fast_exp(s - mn);
-      const float ek = keep[z].kept(p, j, slot, packed) ? e * p.scale : 0.f;   // a dropped element is +0
-      acc[z][j] = acc[z][j] * corr + ek * v.v[j];
-      l[z][j] = l[z][j] * corr + e;                    // the softmax is the dropout-free one
-      m[z][j] = mn;
-    }
-  };
-  if constexpr (WMAX > 0) {
-#pragma unroll
-    for (int i = 0; i < WMAX + QPW - 1; ++i) {
-      const int u = lo + i;
-      if (u > hi) break;
-      const bool valid = ((km >> i) & 1ull) != 0;
-#pragma unroll
-      for (int z = 0; z < QPW; ++z)
-        if (live[z] && u >= t + z - half && u <= t + z + half) key(z, valid, u, kb[i & 1], vb[i & 1]);
-      if (i + 2 < WMAX + QPW - 1 && u + 2 <= hi) fetch(u + 2, kb[i & 1], vb[i & 1]);   // this register set is free again
-    }
-  } else {
-    if (live[0]) {
-      for (int u = lo; u <= hi; ++u) {
-        fetch(u, kb[0], vb[0]);
-        key(0, p.mask[base + u] != 0, u, kb[0], vb[0]);
-      }
-    }
-  }
-#pragma unroll
-  for (int z = 0; z < QPW; ++z) {
-    if (z >= nq) break;
-    Row<NCH> o;
-#pragma unroll
-    // (+ 0.0f: a zero leaves as +0.  A window that opens with kept padded keys carries their values until the first valid key rescales
-    // them by exp(-1e4) = 0, which leaves the sign of what was there: -0 where every valid key is dropped afterwards.)
-    for (int j = 0; j < NCH; ++j) o.v[j] = live[z] ? acc[z][j] / l[z][j] + 0.0f : f32x4{0.f, 0.f, 0.f, 0.f};
-    o.store(p.O + (r + z) * C, C, lane);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// backward, query side (k_attn_bwd_q, attn_grad.hip): statistics, the row's keep bits, dQ
-// ------------------------------------------------------------------------------------------
-template <int NCH, int LPH, int WMAX>
-__global__ __launch_bounds__(256) void k_attn_drop_bwd_q(LocalAttnDropArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (r >= (int64_t)p.B * p.T) return;
-  const int C = p.C;
-  const int t = (int)(r % p.T);
-  const int64_t base = r - t;
-  if (p.mask && p.mask[r] == 0) {                        // a padded query: P_t. = 0, so dQ_t = 0 and it feeds no key
-    if (p.dQ) { Row<NCH> z; z.zero(); z.store(p.dQ + r * C, C, lane); }
-    return;
-  }
-  const int half = p.window / 2;
-  const int lo = max(t - half, 0), hi = min(t + half, p.T - 1), n = hi - lo + 1;
-  const int slot0 = lo - (t - half);                     // slot of key lo
-  const float scale = 1.0f / sqrtf(sqrtf((float)(C / p.heads)));
-  const bool packed = WMAX > 0 || p.window <= AD_PACK_MAX;
-  unsigned long long km = ~0ull;
-  if constexpr (WMAX > 0) {
-    if (p.mask) km = __ballot(lane < n && p.mask[base + lo + lane] != 0);
-  }
-  RowKeep<NCH, LPH> keep;
-  keep.init(p, p.b0 + base / p.T, t, lane, packed);
-  Row<NCH> q, g, dq;
-  q.load(p.Q + r * C, C, lane);
-  g.load(p.dO + r * C, C, lane);
-  ad_scale_row(q, scale);
-  dq.zero();
-  float m[NCH], l[NCH], D[NCH];
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) { m[j] = -INFINITY; l[j] = 0.f; D[j] = 0.f; }
-
-  auto score = [&](const Row<NCH>& k, const Row<NCH>& v, bool valid, float* s, float* dp) __attribute__((always_inline)) {
-    const float pen = valid ? 0.f : -1e4f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      s[j] = ad_head_sum<LPH>(dotp(q.v[j], k.v[j] * scale)) + pen;
-      dp[j] = ad_head_sum<LPH>(dotp(g.v[j], v.v[j]));    // dPd: the gradient at the dropped map
-    }
-  };
-  auto online = [&](const float* s, const float* dp, int slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      const float mn = fmaxf(m[j], s[j]);
-      const float corr = m[j] == -INFINITY ? 0.f : exp_res(m[j] - mn);
-      const float e = exp_res(s[j] - mn);
-      const float ek = keep.kept(p, j, slot, packed) ? e * p.scale : 0.f;
-      l[j] = l[j] * corr + e;
-      D[j] = D[j] * corr + ek * dp[j];                   // delta = sum_j Pd dPd
-      m[j] = mn;
-    }
-  };
-  float il[NCH], delta[NCH];
-  auto finish = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      il[j] = 1.0f / l[j];                               // the query sees itself: l >= 1
-      delta[j] = D[j] * il[j];
-      if (p.stats && lane % LPH == 0 && 256 * j + 4 * lane < C)
-        *reinterpret_cast<f32x4*>(p.stats + (r * p.heads + (64 * j + lane) / LPH) * 4) =
-            f32x4{m[j], il[j], delta[j], __uint_as_float(keep.bits[j])};     // (the word is moved, never computed with)
-    }
-  };
-  auto accum = [&](const float* s, const float* dp, int slot, const Row<NCH>& k) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      const float pj = exp_res(s[j] - m[j]) * il[j];
-      const float dpk = keep.kept(p, j, slot, packed) ? dp[j] * p.scale : 0.f;   // dP = k o dPd
-      const float ds = pj * (dpk - delta[j]);
-      dq.v[j] += ds * (k.v[j] * scale);
-    }
-  };
-
-  if constexpr (WMAX > 0) {
-    float s[WMAX][NCH], dp[WMAX][NCH];
-    Row<NCH> kb[2], vb[2];
-    kb[0].load(p.K + (base + lo) * C, C, lane);
-    vb[0].load(p.V + (base + lo) * C, C, lane);
-    kb[1].load(p.K + (base + min(lo + 1, hi)) * C, C, lane);
-    vb[1].load(p.V + (base + min(lo + 1, hi)) * C, C, lane);
-#pragma unroll
-    for (int i = 0; i < WMAX; ++i) {
-      if (i < n) {
-        score(kb[i & 1], vb[i & 1], ((km >> i) & 1ull) != 0, s[i], dp[i]);
-        online(s[i], dp[i], slot0 + i);
-      }
-      if (i + 2 < WMAX && i + 2 < n) {
-        kb[i & 1].load(p.K + (base + lo + i + 2) * C, C, lane);
-        vb[i & 1].load(p.V + (base + lo + i + 2) * C, C, lane);
-      }
-    }
-    finish();
-    if (p.dQ) {
-      kb[0].load(p.K + (base + lo) * C, C, lane);
-      kb[1].load(p.K + (base + min(lo + 1, hi)) * C, C, lane);
-#pragma unroll
-      for (int i = 0; i < WMAX; ++i) {
-        if (i < n) accum(s[i], dp[i], slot0 + i, kb[i & 1]);
-        if (i + 2 < WMAX && i + 2 < n) kb[i & 1].load(p.K + (base + lo + i + 2) * C, C, lane);
-      }
-    }
-  } else {
-    float s[NCH], dp[NCH];
-    Row<NCH> k, v;
-    for (int u = lo; u <= hi; ++u) {
-      k.load(p.K + (base + u) * C, C, lane);
-      v.load(p.V + (base + u) * C, C, lane);
-      score(k, v, !p.mask || p.mask[base + u] != 0, s, dp);
-      online(s, dp, slot0 + u - lo);
-    }
-    finish();
-    if (p.dQ) {
-      for (int u = lo; u <= hi; ++u) {                   // the same expressions on the same operands: the same s and dPd
-        k.load(p.K + (base + u) * C, C, lane);
-        v.load(p.V + (base + u) * C, C, lane);
-        score(k, v, !p.mask || p.mask[base + u] != 0, s, dp);
-        accum(s, dp, slot0 + u - lo, k);
-      }
-    }
-  }
-  if (p.dQ) {
-    ad_scale_row(dq, scale);
-    dq.store(p.dQ + r * C, C, lane);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// backward, key side (k_attn_bwd_kv, attn_grad.hip): dK and dV as a gather over the queries whose band holds the key
-// ------------------------------------------------------------------------------------------
-template <int NCH, int LPH, int WMAX>
-__global__ __launch_bounds__(256) void k_attn_drop_bwd_kv(LocalAttnDropArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (r >= (int64_t)p.B * p.T) return;
-  const int C = p.C;
-  const int t = (int)(r % p.T);
-  const int64_t base = r - t;
-  const int half = p.window / 2;
-  const int lo = max(t - half, 0), hi = min(t + half, p.T - 1), n = hi - lo + 1;
-  const float scale = 1.0f / sqrtf(sqrtf((float)(C / p.heads)));
-  const float pen = (p.mask && p.mask[r] == 0) ? -1e4f : 0.f;
-  const bool packed = WMAX > 0 || p.window <= AD_PACK_MAX;
-  const int64_t bg = p.b0 + base / p.T;
-  unsigned long long qm = ~0ull;
-  if constexpr (WMAX > 0) {
-    if (p.mask) qm = __ballot(lane < n && p.mask[base + lo + lane] != 0);
-  }
-  Row<NCH> k, v, dk, dv;
-  k.load(p.K + r * C, C, lane);
-  v.load(p.V + r * C, C, lane);
-  ad_scale_row(k, scale);
-  dk.zero();
-  dv.zero();
-  const bool want_dk = p.dK != nullptr;
-
-  auto fetch = [&](int u, Row<NCH>& q, Row<NCH>& g, f32x4* st) __attribute__((always_inline)) {
-    q.load(p.Q + (base + u) * C, C, lane);
-    g.load(p.dO + (base + u) * C, C, lane);
-#pragma unroll
-    for (int j = 0; j < NCH; ++j)
-      st[j] = 256 * j + 4 * lane < C ? *reinterpret_cast<const f32x4*>(p.stats + ((base + u) * p.heads + (64 * j + lane) / LPH) * 4)
-                                     : f32x4{0.f, 0.f, 0.f, 0.f};
-  };
-  // key t is slot t - (u - half) of query u's row of the map
-  auto query = [&](int u, const Row<NCH>& q, const Row<NCH>& g, const f32x4* st) __attribute__((always_inline)) {
-    const int slot = t - u + half;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      bool kept;
-      if (packed) kept = ((__float_as_uint(st[j].w) >> slot) & 1u) != 0;
-      else {
-        const int hd = (64 * j + lane) / LPH;
-        kept = drop_keep(p.seed, p.site, (uint64_t)(((bg * p.heads + hd) * (int64_t)p.T + u) * (int64_t)p.window + slot), p.p);
-      }
-      const f32x4 qs = q.v[j] * scale;
-      const float s = ad_head_sum<LPH>(dotp(qs, k.v[j])) + pen;
-      const float pj = exp_res(s - st[j].x) * st[j].y;
-      const float pk = kept ? pj * p.scale : 0.f;
-      dv.v[j] += pk * g.v[j];
-      if (want_dk) {
-        const float dp = ad_head_sum<LPH>(dotp(g.v[j], v.v[j]));
-        const float dpk = kept ? dp * p.scale : 0.f;
-        const float ds = pj * (dpk - st[j].z);
-        dk.v[j] += ds * qs;
-      }
-    }
-  };
-
-  if constexpr (WMAX > 0) {
-    Row<NCH> qb[2], gb[2];
-    f32x4 sb[2][NCH];
-    fetch(lo, qb[0], gb[0], sb[0]);
-    fetch(min(lo + 1, hi), qb[1], gb[1], sb[1]);
-#pragma unroll
-    for (int i = 0; i < WMAX; ++i) {
-      if (i < n && ((qm >> i) & 1ull)) query(lo + i, qb[i & 1], gb[i & 1], sb[i & 1]);   // a padded query attends to nothing
-      if (i + 2 < WMAX && i + 2 < n) fetch(lo + i + 2, qb[i & 1], gb[i & 1], sb[i & 1]);
-    }
-  } else {
-    Row<NCH> q, g;
-    f32x4 st[NCH];
-    for (int u = lo; u <= hi; ++u) {
-      if (p.mask && p.mask[base + u] == 0) continue;
-      fetch(u, q, g, st);
-      query(u, q, g, st);
-    }
-  }
-  if (p.dK) {
-    ad_scale_row(dk, scale);
-    dk.store(p.dK + r * C, C, lane);
-  }
-  if (p.dV) dv.store(p.dV + r * C, C, lane);
-}
 
 // ------------------------------------------------------------------------------------------
 // dense attention with dropout on its map: global self attention (keys = the T rows of the query's sequence) and cross attention
@@ -450,7 +63,7 @@ __global__ __launch_bounds__(256) void k_dense_attn_drop_q(DenseAttnDropArgs p) 
   dense_row_e0<NCH, LPH>(p, r, lane, e0);
   Row<NCH> q, g, k, v;
   q.load(p.Q + r * C, C, lane);
-  ad_scale_row(q, scale);
+  scale_row(q, scale);
   if constexpr (BWD) g.load(p.dO + r * C, C, lane);
   f32x4 acc[NCH];
   float m[NCH], l[NCH], D[NCH];
@@ -465,7 +78,7 @@ __global__ __launch_bounds__(256) void k_dense_attn_drop_q(DenseAttnDropArgs p) 
       if (p.kmask && p.kmask[kbase + jk] == 0) continue;
       k.load(p.K + (kbase + jk) * C, C, lane);
 #pragma unroll
-      for (int j = 0; j < NCH; ++j) m[j] = fmaxf(m[j], ad_head_sum<LPH>(dotp(q.v[j], k.v[j] * scale)));
+      for (int j = 0; j < NCH; ++j) m[j] = fmaxf(m[j], head_sum<LPH>(dotp(q.v[j], k.v[j] * scale)));
     }
   }
   for (int j0 = 0; j0 < p.Lk; j0 += 32) {
@@ -482,12 +95,12 @@ __global__ __launch_bounds__(256) void k_dense_attn_drop_q(DenseAttnDropArgs p) 
       v.load(p.V + (kbase + j0 + jj) * C, C, lane);
 #pragma unroll
       for (int j = 0; j < NCH; ++j) {
-        const float s = ad_head_sum<LPH>(dotp(q.v[j], k.v[j] * scale));
+        const float s = head_sum<LPH>(dotp(q.v[j], k.v[j] * scale));
         if constexpr (BWD) {
           const float e = exp_res(s - m[j]);
           const float ek = ((bits[j] >> jj) & 1u) ? e * p.scale : 0.f;
           l[j] += e;
-          D[j] += ek * ad_head_sum<LPH>(dotp(g.v[j], v.v[j]));
+          D[j] += ek * head_sum<LPH>(dotp(g.v[j], v.v[j]));
         } else {
           const float mn = fmaxf(m[j], s);
           const float corr = m[j] == -INFINITY ? 0.f : exp_res(m[j] - mn);
@@ -529,15 +142,15 @@ __global__ __launch_bounds__(256) void k_dense_attn_drop_q(DenseAttnDropArgs p) 
       v.load(p.V + (kbase + j0 + jj) * C, C, lane);
 #pragma unroll
       for (int j = 0; j < NCH; ++j) {
-        const float s = ad_head_sum<LPH>(dotp(q.v[j], k.v[j] * scale));
-        const float dp = ad_head_sum<LPH>(dotp(g.v[j], v.v[j]));
+        const float s = head_sum<LPH>(dotp(q.v[j], k.v[j] * scale));
+        const float dp = head_sum<LPH>(dotp(g.v[j], v.v[j]));
         const float pj = exp_res(s - m[j]) * il[j];
         const float dpk = ((bits[j] >> jj) & 1u) ? dp * p.scale : 0.f;
         dq.v[j] += (pj * (dpk - delta[j])) * (k.v[j] * scale);
       }
     }
   }
-  ad_scale_row(dq, scale);
+  scale_row(dq, scale);
   dq.store(p.dQ + r * C, C, lane);
 }
 
@@ -557,7 +170,7 @@ __global__ __launch_bounds__(256) void k_dense_attn_drop_kv(DenseAttnDropArgs p)
   if (!p.kmask || p.kmask[r] != 0) {                     // a masked key: exactly 0, whatever dO holds
     k.load(p.K + r * C, C, lane);
     v.load(p.V + r * C, C, lane);
-    ad_scale_row(k, scale);
+    scale_row(k, scale);
     const bool want_dk = p.dK != nullptr;
     for (int t = 0; t < p.T; ++t) {
       q.load(p.Q + (qbase + t) * C, C, lane);
@@ -569,12 +182,12 @@ __global__ __launch_bounds__(256) void k_dense_attn_drop_kv(DenseAttnDropArgs p)
         const f32x4 st = act ? *reinterpret_cast<const f32x4*>(p.stats + rh * 4) : zero4();
         const bool kept = act && ((p.bits[rh * p.nw + (jk >> 5)] >> (jk & 31)) & 1u) != 0;
         const f32x4 qs = q.v[j] * scale;
-        const float s = ad_head_sum<LPH>(dotp(qs, k.v[j]));
+        const float s = head_sum<LPH>(dotp(qs, k.v[j]));
         const float pj = exp_res(s - st.x) * st.y;
         const float pk = kept ? pj * p.scale : 0.f;
         dv.v[j] += pk * g.v[j];
         if (want_dk) {
-          const float dp = ad_head_sum<LPH>(dotp(g.v[j], v.v[j]));
+          const float dp = head_sum<LPH>(dotp(g.v[j], v.v[j]));
           const float dpk = kept ? dp * p.scale : 0.f;
           dk.v[j] += (pj * (dpk - st.z)) * qs;
         }
@@ -582,7 +195,7 @@ __global__ __launch_bounds__(256) void k_dense_attn_drop_kv(DenseAttnDropArgs p)
     }
   }
   if (p.dK) {
-    ad_scale_row(dk, scale);
+    scale_row(dk, scale);
     dk.store(p.dK + r * C, C, lane);
   }
   if (p.dV) dv.store(p.dV + r * C, C, lane);
@@ -619,14 +232,7 @@ __global__ __launch_bounds__(256) void k_channel_dropout(const float* __restrict
 // launchers
 // ------------------------------------------------------------------------------------------
 static int ad_check(const char* who, const LocalAttnDropArgs& a) {
-  DCF_CHECK(a.B > 0 && a.T > 0 && a.heads > 0, "%s: empty batch (B=%d T=%d heads=%d)", who, a.B, a.T, a.heads);
-  DCF_CHECK(a.window != 0, "%s: window = 0 (global attention) has its backward in dcf_op_global_attn_drop_bwd", who);
-  DCF_CHECK(a.window >= 1 && a.window % 2 == 1, "%s: window = %d must be odd and >= 1", who, a.window);
-  DCF_CHECK(a.C > 0 && a.C % a.heads == 0, "%s: C=%d not divisible by heads=%d", who, a.C, a.heads);
-  const int d = a.C / a.heads, nch = (a.C + 255) / 256;
-  DCF_CHECK(a.C % 4 == 0 && nch <= 4 && d >= 4 && d <= 256 && (d & (d - 1)) == 0,
-            "%s: unsupported C=%d / head dim=%d (need power-of-two head dim in [4,256], C<=1024)", who, a.C, d);
-  DCF_CHECK((int64_t)a.B * a.T < (1ll << 31) - 64, "%s: %lld rows (< 2^31)", who, (long long)a.B * a.T);
+  if (local_attn_geometry_check(who, a.B, a.T, a.C, a.heads, a.window, "has its backward in dcf_op_global_attn_drop_bwd")) return -1;
   DCF_CHECK(a.b0 >= 0, "%s: b0 = %d must not be negative", who, a.b0);
   DCF_CHECK(a.p >= 0.f && a.p < 1.f, "%s: p = %g outside [0, 1)", who, (double)a.p);
   return 0;
@@ -634,12 +240,12 @@ static int ad_check(const char* who, const LocalAttnDropArgs& a) {
 
 template <int NCH, int LPH, int WMAX>
 static void ad_launch_fwd(const LocalAttnDropArgs& a, dim3 grid, hipStream_t st) {
-  hipLaunchKernelGGL((k_local_attn_drop<NCH, LPH, WMAX>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_local_attn<NCH, LPH, false, WMAX, false, LocalAttnDropArgs>), grid, dim3(256), 0, st, a);
 }
 template <int NCH, int LPH, int WMAX>
 static void ad_launch_bwd(const LocalAttnDropArgs& a, dim3 grid, bool kv, hipStream_t st) {
-  hipLaunchKernelGGL((k_attn_drop_bwd_q<NCH, LPH, WMAX>), grid, dim3(256), 0, st, a);
-  if (kv) hipLaunchKernelGGL((k_attn_drop_bwd_kv<NCH, LPH, WMAX>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_attn_bwd_q<NCH, LPH, WMAX, LocalAttnDropArgs>), grid, dim3(256), 0, st, a);
+  if (kv) hipLaunchKernelGGL((k_attn_bwd_kv<NCH, LPH, WMAX, LocalAttnDropArgs>), grid, dim3(256), 0, st, a);
 }
 // the variants of the dropout-free launchers: the forward unrolls windows of at most 9 / 19 keys at every width, the backward at
 // rows of one chunk
@@ -651,16 +257,6 @@ static void ad_launch_bwd(const LocalAttnDropArgs& a, dim3 grid, bool kv, hipStr
     if (NCH_ == 1 && a.window <= 9) ad_launch_bwd<1, LPH_, 9>(a, grid, kv, st);           \
     else if (NCH_ == 1 && a.window <= 19) ad_launch_bwd<1, LPH_, 19>(a, grid, kv, st);    \
     else ad_launch_bwd<NCH_, LPH_, 0>(a, grid, kv, st); } while (0)
-#define AD_DISPATCH(WHAT) do {                                                            \
-    switch (nch * 100 + lph) {                           /* the forward's table (DISPATCH_ATTN, attn.hip) */ \
-      case 101: WHAT(1, 1); break;   case 102: WHAT(1, 2); break;   case 104: WHAT(1, 4); break;   case 108: WHAT(1, 8); break; \
-      case 116: WHAT(1, 16); break;  case 132: WHAT(1, 32); break;  case 164: WHAT(1, 64); break;  \
-      case 208: WHAT(2, 8); break;   case 216: WHAT(2, 16); break;  case 232: WHAT(2, 32); break;  case 264: WHAT(2, 64); break; \
-      case 316: WHAT(3, 16); break;  case 332: WHAT(3, 32); break;  case 364: WHAT(3, 64); break;  \
-      case 416: WHAT(4, 16); break;  case 432: WHAT(4, 32); break;  case 464: WHAT(4, 64); break;  \
-      default: ok = false;                                                                \
-    } } while (0)
-
 static DenseAttnDropArgs dense_args(const float* Q, const float* K, const float* V, const uint8_t* kmask, float* O, const float* dO, float* dQ,
                                     float* dK, float* dV, int B, int T, int Lk, int C, int heads, int b0, int64_t seed, int32_t site, float p) {
   DenseAttnDropArgs a{};
@@ -701,8 +297,8 @@ static int dense_check(const char* who, const DenseAttnDropArgs& a, int dmin, in
 static int launch_dense_attn_drop(const char* who, const DenseAttnDropArgs& a, bool bwd, hipStream_t st) {
   const int nch = (a.C + 255) / 256, lph = a.C / a.heads / 4;
   bool ok = true;
-  if (bwd) AD_DISPATCH(AD_DENSE_BWD);
-  else AD_DISPATCH(AD_DENSE_FWD);
+  if (bwd) DCF_ATTN_ROW_SHAPES(nch, lph, ok, AD_DENSE_BWD);
+  else DCF_ATTN_ROW_SHAPES(nch, lph, ok, AD_DENSE_FWD);
   DCF_CHECK(ok, "%s: no kernel for C=%d heads=%d", who, a.C, a.heads);
   DCF_HIP(hipGetLastError());
   return 0;
@@ -725,10 +321,10 @@ int launch_local_attn_drop(const LocalAttnDropArgs& a, hipStream_t st) {
   if (ad_check(who, a)) return -1;
   if (a.p == 0.f) return launch_local_attn(LocalAttnArgs{a.Q, a.K, a.V, a.mask, a.O, a.B, a.T, a.C, a.heads, a.window}, st);
   const int nch = (a.C + 255) / 256, lph = a.C / a.heads / 4;
-  const int qpw = a.window <= 19 ? AD_QPW : 1;
+  const int qpw = a.window <= 19 ? LA_QPW : 1;
   const dim3 grid((unsigned)(((int64_t)a.B * ((a.T + qpw - 1) / qpw) + 3) / 4));
   bool ok = true;
-  AD_DISPATCH(AD_FWD);
+  DCF_ATTN_ROW_SHAPES(nch, lph, ok, AD_FWD);
   DCF_CHECK(ok, "%s: no kernel for C=%d heads=%d", who, a.C, a.heads);
   DCF_HIP(hipGetLastError());
   return 0;
@@ -746,7 +342,7 @@ int launch_local_attn_drop_bwd(const LocalAttnDropArgs& a, hipStream_t st) {
   if (!a.dQ && !kv) return 0;
   const dim3 grid((unsigned)(((int64_t)a.B * a.T + 3) / 4));       // four waves per workgroup, a wave per row
   bool ok = true;
-  AD_DISPATCH(AD_BWD);
+  DCF_ATTN_ROW_SHAPES(nch, lph, ok, AD_BWD);
   DCF_CHECK(ok, "%s: no kernel for C=%d heads=%d", who, a.C, a.heads);
   DCF_HIP(hipGetLastError());
   return 0;

@@ -21,4 +21,8 @@ inline size_t local_attn_grad_stats_floats(int64_t rows, int heads) { return (si
 
 int launch_local_attn_bwd(const LocalAttnGradArgs& a, hipStream_t st);
 
+// the geometry check of the sliding-window gradient kernels, which the launchers with dropout on the map share (attn_drop.hip);
+// `window0`: what the message says of window = 0.  0, or -1 with the error set.
+int local_attn_geometry_check(const char* who, int B, int T, int C, int heads, int window, const char* window0);
+
 }  // namespace dcf

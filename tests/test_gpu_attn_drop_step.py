@@ -94,22 +94,24 @@ def test_sites_keys_and_rates_the_forward_draws_from(pkg, name, second, monkeypa
     A = pkg.autograd
     model = rated_model(pkg, f, second_fusion=second, **RATES)
     seen = {'map': [], 'cross': [], 'chan': []}
-    inner = {k: getattr(A, k).apply for k in ('_WindowAttentionDropFn', '_CrossAttentionDropFn', '_ChannelDropoutFn')}
+    inner = {k: getattr(A, k).apply for k in ('_WindowAttentionFn', '_CrossAttentionFn', '_ChannelDropoutFn')}
 
-    def map_apply(q, k, v, mask, n_heads, window, key, site, p, b0):
-        seen['map'].append((key, site, p, b0))
-        return inner['_WindowAttentionDropFn'](q, k, v, mask, n_heads, window, key, site, p, b0)
+    def map_apply(q, k, v, mask, n_heads, window, drop):       # drop: None, or (key, site, p, b0)
+        if drop is not None:
+            seen['map'].append(tuple(drop))
+        return inner['_WindowAttentionFn'](q, k, v, mask, n_heads, window, drop)
 
-    def cross_apply(q, k, v, mask, n_heads, key, site, p, b0):
-        seen['cross'].append((key, site, p, b0))
-        return inner['_CrossAttentionDropFn'](q, k, v, mask, n_heads, key, site, p, b0)
+    def cross_apply(q, k, v, mask, n_heads, drop):
+        if drop is not None:
+            seen['cross'].append(tuple(drop))
+        return inner['_CrossAttentionFn'](q, k, v, mask, n_heads, drop)
 
     def chan_apply(x, key, site, p, b0):
         seen['chan'].append((key, site, p, b0, tuple(x.shape)))
         return inner['_ChannelDropoutFn'](x, key, site, p, b0)
 
-    monkeypatch.setattr(A._WindowAttentionDropFn, 'apply', staticmethod(map_apply))
-    monkeypatch.setattr(A._CrossAttentionDropFn, 'apply', staticmethod(cross_apply))
+    monkeypatch.setattr(A._WindowAttentionFn, 'apply', staticmethod(map_apply))
+    monkeypatch.setattr(A._CrossAttentionFn, 'apply', staticmethod(cross_apply))
     monkeypatch.setattr(A._ChannelDropoutFn, 'apply', staticmethod(chan_apply))
     batch, _ = batch_of(f)
     with torch.no_grad():
