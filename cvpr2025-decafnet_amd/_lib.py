@@ -351,6 +351,27 @@ ATTN_DROP = (
 )
 
 
+# the selected-clip extension (include/decafnet_hip_select.h, csrc/select.hip; the two forwards in csrc/engine.hip): which clips the
+# gates need, the gather that makes clip-major rows of dense features, and the externally gated forward on those rows.  ``clips`` /
+# ``pos`` / ``count`` are int32 in device memory; ``text`` / ``text_mask`` / ``text_len`` are HOST arrays as in SIGNATURES.
+_FWD_SEL = [i32, c_i32p, vp, c_u8p, i64, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i32), c_f32p, c_f32p, c_f32p, c_u8p, vp]
+SELECT_TABLE = {
+    'dcf_select_ext_version': (i32, []),
+    'dcf_op_select_clips': (i32, [c_f32p, c_u8p, i32, i32, c_i32p, c_i32p, c_i32p, vp]),
+    'dcf_op_gather_clip_rows': (i32, [c_f32p, i64, c_i32p, i32, i32, c_f32p, vp]),
+    'dcf_op_gather_clip_rows_h': (i32, [c_f16p, i64, c_i32p, i32, i32, c_f16p, vp]),
+    'dcf_forward_eval_selected': (i32, [vp, c_f32p] + _FWD_SEL),
+    'dcf_forward_eval_selected_h': (i32, [vp, c_f16p] + _FWD_SEL),
+}
+
+
+# Bound by lib() after ATTN_DROP and waiting for the same follow-up: registration at the end of EXTENSIONS together with a
+# ``borders.TABLE`` row (the cases are tests/select_abi_cases.py, run through the same driver by tests/test_gpu_select_borders.py).
+SELECT = (
+    Extension('select', 'decafnet_hip_select.h', 'dcf_select_ext_version', 1, 'DCF_SELECT_EXT_VERSION', ('decafnet_hip.h',), SELECT_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -362,11 +383,11 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG + ATTN_DROP:
+        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG + ATTN_DROP + SELECT:
             for name, (res, args) in ext.table.items():
                 if name in bound:
                     raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED / _lib.FIT / '
-                                       f'_lib.STEPLOG / _lib.ATTN_DROP')
+                                       f'_lib.STEPLOG / _lib.ATTN_DROP / _lib.SELECT')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

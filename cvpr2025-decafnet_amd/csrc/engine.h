@@ -224,6 +224,9 @@ struct ForwardCall {
   const float* const* text; const uint8_t* const* text_mask; const int32_t* text_len;
   const float* gate;                          // nullptr, or the externally selected gate (nq, T) of dcf_forward_eval_gated / dcf_hybrid_phase1
   float *logits, *offsets; uint8_t* masks;
+  // dcf_forward_eval_selected (with `gate`): the expert features of the selected clips only, clip-major fp32 rows (sel_n, D), and
+  // sel_pos (T) int32, the row of clip t among them or -1 (dcf_op_select_clips); the video's vid pointer is null
+  const float* sel_rows = nullptr; const int32_t* sel_pos = nullptr; int sel_n = 0;
 };
 
 // the level-cut state of dcf_hybrid_phase1 / 2 / 3 (engine_hybrid.hip)

@@ -16,6 +16,7 @@
 
 #include "engine.h"
 #include "../../include/decafnet_hip_half.h"
+#include "../../include/decafnet_hip_select.h"
 
 namespace dcf {
 
@@ -72,6 +73,19 @@ __global__ void k_gather_masks(MaskPtrs mp, uint8_t* __restrict__ dst, int T0) {
   if (t < T0) dst[(size_t)blockIdx.y * T0 + t] = mp.p[blockIdx.y][t];
 }
 
+// m->half_ws holds at least `need` bytes afterwards
+static int grow_half_ws(dcf_model* m, size_t need, hipStream_t st) {
+  if (need <= m->half_ws_bytes) return 0;
+  DCF_CHECK(!m->capturing, "internal: workspace growth during graph capture");
+  drop_graph(m, true);                          // (a captured graph bakes the copies' addresses in)
+  DCF_HIP(hipStreamSynchronize(st));
+  if (m->half_ws) DCF_HIP(hipFree(m->half_ws));
+  m->half_ws = nullptr; m->half_ws_bytes = 0;
+  DCF_HIP(hipMalloc(&m->half_ws, need));
+  m->half_ws_bytes = need;
+  return 0;
+}
+
 // Half features (VideoSet::half): read as they are where the kernels in front can -- the split-operand vid_map GEMMs (with the scores on
 // their side or the scoring kernels beside them) --, otherwise upcast once into m->half_ws and handed on as an fp32 video set.
 // *use = the set the forward goes on with.  dcf_debug_set_option("half_native", 0 / 1 / 2): never / where possible / or fail.
@@ -88,16 +102,7 @@ static int half_features(dcf_model* m, const VideoSet& in, int T0, const Forward
                                  "pointer that is not 8-byte aligned) and the option half_native = 2 forbids the upcast");
   if (native) { *use = &in; return 0; }
   const size_t per = ((size_t)c.D * T0 * sizeof(float) + 255) & ~(size_t)255;
-  const size_t need = per * 2 * in.nvid;
-  if (need > m->half_ws_bytes) {
-    DCF_CHECK(!m->capturing, "internal: workspace growth during graph capture");
-    drop_graph(m, true);                          // (a captured graph bakes the copies' addresses in)
-    DCF_HIP(hipStreamSynchronize(st));
-    if (m->half_ws) DCF_HIP(hipFree(m->half_ws));
-    m->half_ws = nullptr; m->half_ws_bytes = 0;
-    DCF_HIP(hipMalloc(&m->half_ws, need));
-    m->half_ws_bytes = need;
-  }
+  TRY(grow_half_ws(m, per * 2 * in.nvid, st));
   f32 = in;
   f32.half = false;
   for (int v = 0; v < in.nvid; ++v) {
@@ -172,6 +177,13 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
   carve_at(m->arena, c, T0, Bmax, nq, S, Lk, nvid, b, m->hyb_extra, &m->hyb_extra_ptr);
   // ---- per video: sidekick scores and the query-independent halves of vid_map
   DCF_CHECK(!(fc.gate && c.scat), "opt.model.scat needs the sidekick scores: the externally gated (T-sharded) forward does not take them");
+  const bool sel = fc.sel_rows != nullptr;        // dcf_forward_eval_selected: the expert product on the rows of the selected clips
+  if (sel) {
+    DCF_CHECK(fc.gate && fc.sel_pos && nvid == 1, "internal: the selected-clip forward is an externally gated forward of one video");
+    DCF_CHECK(m->vid_w1, "dcf_forward_eval_selected: opt.model.sfonly reads no expert features: there is nothing to select");
+    DCF_CHECK(fc.sel_n >= 1 && fc.sel_n <= T0, "dcf_forward_eval_selected: n_rows=%d must lie in [1, T=%d]", fc.sel_n, T0);
+    DCF_CHECK(D % 4 == 0 && aligned16(fc.sel_rows), "dcf_forward_eval_selected: vid_rows needs D %% 4 == 0 and a 16-byte aligned base");
+  }
   // The sidekick scores ride on the shallow half of vid_map where they can: that GEMM streams exactly the (D, T) matrix the scores
   // are a reduction of, so the scoring pass's read of it (4 KB per clip) disappears; otherwise three launches of their own.
   // (dcf_debug_set_option("fuse_scores", 0) = the scoring kernels)
@@ -271,11 +283,18 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
       }
     } else {
       for (int v = 0; v < nvid; ++v) {
-        if (m->vid_w1) TRY(expert_half(v, false));
+        if (m->vid_w1 && !sel) TRY(expert_half(v, false));
         if (m->vid_w2) TRY(shallow_half(v));
       }
       TRY(flush());
       TRY(gather_masks());
+      if (sel) {
+        // P1c (n_rows, E) = vid_rows . W1^T into the first n_rows rows of P1: a row-major GEMM on the same weight image; every row is
+        // needed by construction, so no tile is skipped
+        GemmArgs ge = gemm(fc.sel_rows, D, m->vid_w1, nullptr, b.P1, E, fc.sel_n, E, D);
+        ge.ldw = m->vid_ldw; ge.a_scale = 1.f;
+        TRY(run_gemm(m, &ge, 1, A_ROWS, st));
+      }
     }
   }
   if (nvid > 1) vid_mask = b.maskv;
@@ -313,6 +332,8 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
     const uint8_t* maskP = b.mask_all;            // pyramid level 0
 
     // ---- vid_map (model.py:543-555)
+    if (sel) TRY(launch_vidmap_combine_sel(b.P1, fc.sel_pos, m->vid_w2 ? b.P2 : nullptr, m->vid_map_b, b.gate, mask0, b.X, T0, rows0, E, st));
+    else
     TRY(launch_vidmap_combine(m->vid_w1 ? b.P1 : nullptr, m->vid_w2 ? b.P2 : nullptr, m->vid_map_b, b.gate, mask0,
                               m->vid_w3, m->vid_w3 ? b.correl + (int64_t)q0 * T0 : nullptr, b.X, T0, rows0, E, vmap, st));
     if (m->keep_debug) DCF_CHECK((int64_t)rows0 * E <= m->dbg_cap, "dcf_debug_copy: armed destination holds %lld floats, the tap needs %lld", (long long)m->dbg_cap, (long long)rows0 * E);
@@ -646,7 +667,8 @@ static int forward_maybe_graph(dcf_model* m, const VideoSet& vs, int T0, int nq,
   // costs ~0.9 us more than an in-order launch, and the host needs ~0.5 ms to issue the forward the GPU takes 1.75 ms for).
   const bool want = m->graph_mode == 1 || (m->graph_mode == 0 && (long long)nq * T0 >= 65536);
   // (dropout: eager, the seed is a kernel argument that a captured graph would bake in)
-  const bool eligible = want && !no_graph.get() && !profiling_on() && !m->keep_debug && nq > 0 && !m->drop;
+  // (the selected-clip forward: eager, its row count and row pointers are no part of a graph's key)
+  const bool eligible = want && !no_graph.get() && !profiling_on() && !m->keep_debug && nq > 0 && !m->drop && !fc.sel_rows;
   if (!eligible) {
     m->last_launch = 0;
     return forward(m, vs, T0, nq, fc, st);
@@ -784,6 +806,66 @@ int dcf_forward_eval_gated(dcf_model* m, const float* vid, const float* shallow_
   vs.nvid = 1; vs.vid[0] = vid; vs.shallow[0] = shallow_vid; vs.mask[0] = vid_mask; vs.text_cls[0] = nullptr; vs.nq[0] = nq;
   return dcf::forward_maybe_graph(m, vs, (int)T, nq, {text, text_mask, text_len, gate, logits_out, offsets_out, masks_out},
                                   (hipStream_t)stream);
+}
+
+namespace dcf {
+static int forward_selected(dcf_model* m, const char* who, const float* rows, int32_t n_rows, const int32_t* pos, const float* shallow,
+                            const uint8_t* vid_mask, int64_t T, int32_t nq, const float* const* text, const uint8_t* const* text_mask,
+                            const int32_t* text_len, const float* gate, float* logits_out, float* offsets_out, uint8_t* masks_out,
+                            hipStream_t st) {
+  VideoSet vs;
+  vs.nvid = 1; vs.vid[0] = nullptr; vs.shallow[0] = shallow; vs.mask[0] = vid_mask; vs.text_cls[0] = nullptr; vs.nq[0] = nq;
+  ForwardCall fc{text, text_mask, text_len, gate, logits_out, offsets_out, masks_out};
+  fc.sel_rows = rows; fc.sel_pos = pos; fc.sel_n = n_rows;
+  return forward_maybe_graph(m, vs, (int)T, nq, fc, st);
+}
+// the refusals of the selected-clip forward that need no workspace: before any launch, and before the half form's upcast
+static int selected_checks(const dcf_model* m, const char* who, int32_t n_rows, int64_t T) {
+  DCF_CHECK(T >= 1 && T < (1ll << 24), "%s: T out of range", who);
+  DCF_CHECK(m->finalized, "%s: model not finalized", who);
+  DCF_CHECK(!m->cfg.scat, "%s: opt.model.scat needs the sidekick scores, which this forward is not handed (as dcf_forward_eval_gated)", who);
+  DCF_CHECK(m->vid_w1, "%s: opt.model.sfonly reads no expert features: there is nothing to select", who);
+  DCF_CHECK(vid_stride_of(m->cfg) == 1, "%s: vid_net.stride = %d: the externally gated forward takes vid_net.stride = 1", who, vid_stride_of(m->cfg));
+  DCF_CHECK(n_rows >= 1 && n_rows <= T, "%s: n_rows=%d must lie in [1, T=%lld]", who, (int)n_rows, (long long)T);
+  return 0;
+}
+}  // namespace dcf
+
+int dcf_select_ext_version(void) { return DCF_SELECT_EXT_VERSION; }
+
+int dcf_forward_eval_selected(dcf_model* m, const float* vid_rows, int32_t n_rows, const int32_t* pos, const float* shallow_vid,
+                              const uint8_t* vid_mask, int64_t T, int32_t nq, const float* const* text, const uint8_t* const* text_mask,
+                              const int32_t* text_len, const float* gate, float* logits_out, float* offsets_out, uint8_t* masks_out,
+                              void* stream) {
+  const char* who = "dcf_forward_eval_selected";
+  DCF_CHECK(m && vid_rows && pos && shallow_vid && vid_mask && text && text_len && gate && logits_out && offsets_out && masks_out,
+            "%s: null argument", who);
+  if (dcf::selected_checks(m, who, n_rows, T)) return -1;
+  return dcf::forward_selected(m, who, vid_rows, n_rows, pos, shallow_vid, vid_mask, T, nq, text, text_mask, text_len, gate, logits_out,
+                               offsets_out, masks_out, (hipStream_t)stream);
+}
+
+int dcf_forward_eval_selected_h(dcf_model* m, const uint16_t* vid_rows, int32_t n_rows, const int32_t* pos, const uint16_t* shallow_vid,
+                                const uint8_t* vid_mask, int64_t T, int32_t nq, const float* const* text, const uint8_t* const* text_mask,
+                                const int32_t* text_len, const float* gate, float* logits_out, float* offsets_out, uint8_t* masks_out,
+                                void* stream) {
+  const char* who = "dcf_forward_eval_selected_h";
+  DCF_CHECK(m && vid_rows && pos && shallow_vid && vid_mask && text && text_len && gate && logits_out && offsets_out && masks_out,
+            "%s: null argument", who);
+  if (dcf::selected_checks(m, who, n_rows, T)) return -1;
+  // the compact rows and the shallow features upcast once into the engine's half workspace (exact: every binary16 value is an fp32
+  // value), then the fp32 form: the same numbers as fp32 operands of the same values give
+  hipStream_t st = (hipStream_t)stream;
+  const int D = m->cfg.D;
+  const size_t rows_b = ((size_t)n_rows * D * sizeof(float) + 255) & ~(size_t)255;
+  const size_t sh_b = ((size_t)D * T * sizeof(float) + 255) & ~(size_t)255;
+  if (dcf::grow_half_ws(m, rows_b + sh_b, st)) return -1;
+  float* rows32 = reinterpret_cast<float*>(m->half_ws);
+  float* sh32 = reinterpret_cast<float*>(m->half_ws + rows_b);
+  if (dcf::launch_half_to_f32(vid_rows, rows32, (int64_t)n_rows * D, st)) return -1;
+  if (dcf::launch_half_to_f32(shallow_vid, sh32, (int64_t)D * T, st)) return -1;
+  return dcf::forward_selected(m, who, rows32, n_rows, pos, sh32, vid_mask, T, nq, text, text_mask, text_len, gate, logits_out, offsets_out,
+                               masks_out, st);
 }
 
 int dcf_graph_active(const dcf_model* m) { return m ? m->last_launch : 0; }

@@ -314,8 +314,14 @@ class GroundingEvaluator:
     """``opt`` needs ``opt.model.{max_vid_len, num_fpn_levels, mha_win_size, vid_stride}``, ``opt.eval.{pre_nms_topk,
     pre_nms_thresh, seg_len_thresh}`` and ``opt.nms`` (libs/core/opt.py:174-194)."""
 
-    def __init__(self, opt, model, feature_dtype=None):
-        """``feature_dtype``: None -- ``vid`` / ``shallow_vid`` go to the GPU in the dtype they come in --, or 'float16': ``prepare``
+    def __init__(self, opt, model, feature_dtype=None, expert='dense', expert_fn=None):
+        """``expert``: 'dense' (the default: the reference's interface, ``vid`` holds the expert features of every clip) or 'selected':
+        per forward window ``model.select_clips`` says which clips the gates need, the expert features of those clips alone are
+        obtained -- from ``expert_fn(sample, clips_host)`` -> (count, D) fp32 or float16 rows, clips_host the ascending int64 clip
+        indices (all below the video's length), or, with ``expert_fn=None``, by ``model.gather_clip_rows`` from the sample's dense
+        ``vid`` -- and ``model.forward_selected`` runs on them (include/decafnet_hip_select.h).  The proposal stage is the same.
+        Not here: several videos per forward (``run(batch_videos > 1)``) and the items of a ``data.EvalBank``.
+        ``feature_dtype``: None -- ``vid`` / ``shallow_vid`` go to the GPU in the dtype they come in --, or 'float16': ``prepare``
         rounds them to float16 on the host, before padding, and uploads half the bytes; the forward reads them as they are
         (``model.half_features``).  The proposals then are those of features rounded to float16."""
         self.opt, self.model = opt, model
@@ -323,6 +329,11 @@ class GroundingEvaluator:
                                                  for x in ('float16', 'half', torch.float16, np.float16)):
             raise ValueError(f"feature_dtype {feature_dtype!r}: None (as the features come) or 'float16'")
         self.feature_dtype = None if feature_dtype is None else torch.float16
+        if expert not in ('dense', 'selected'):
+            raise ValueError(f"expert {expert!r}: 'dense' or 'selected'")
+        if expert_fn is not None and expert != 'selected':
+            raise ValueError("expert_fn is the source of the selected clips' features: it needs expert='selected'")
+        self.expert, self.expert_fn = expert, expert_fn
         mo = opt['model']
         self.max_vid_len = mo['max_vid_len']
         self.vid_stride = mo.get('vid_stride', 1)
@@ -393,13 +404,15 @@ class GroundingEvaluator:
             window, shallow_window, mask = bank.windows(data['clip_id'], T)
             self.time_dict['prepare'].append(time.perf_counter() - t0)
             return (window, shallow_window, mask, tuple(texts), data['text_cls'], tuple(tmasks)), T, None
-        vid, shallow = data['vid'], data['shallow_vid']
+        shallow = data['shallow_vid']
+        # expert='selected' with an expert_fn: the sample needs no dense expert features, and none are uploaded
+        vid = None if self.expert == 'selected' and self.expert_fn is not None else data['vid']
         if self.feature_dtype is not None:
             name = data.get('clip_id', '?') if isinstance(data, dict) else '?'
-            vid, shallow = self._to_half(vid, 'vid', name), self._to_half(shallow, 'shallow_vid', name)
-        vid_len = vid.size(-1)
+            vid, shallow = None if vid is None else self._to_half(vid, 'vid', name), self._to_half(shallow, 'shallow_vid', name)
+        vid_len = shallow.size(-1)
         T = padded_length(vid_len, self.max_vid_len, self.num_fpn_levels, self.mha_win_size, self.vid_stride)
-        window = F.pad(vid, (0, T - vid_len))[None].to(dev, non_blocking=True)
+        window = None if vid is None else F.pad(vid, (0, T - vid_len))[None].to(dev, non_blocking=True)
         shallow_window = F.pad(shallow, (0, T - vid_len))[None].to(dev, non_blocking=True)
         mask = (torch.arange(T, device=dev).view(1, -1) < vid_len)
         text_cls = data['text_cls'].to(dev, non_blocking=True)
@@ -417,10 +430,31 @@ class GroundingEvaluator:
         model_ = model or self.model
         args, T, self._window_ext = self.prepare(data, model_)
         t0 = time.perf_counter()
-        out = model_(*args, eval=True)
+        out = self._forward_selected(data, model_, args) if self.expert == 'selected' else model_(*args, eval=True)
         self.time_dict['forward'].append(time.perf_counter() - t0)
         self.outputs = out
         return model_._last_flat, T
+
+    def _forward_selected(self, data, model_, args):
+        """the two-call pattern on one forward window: select_clips -> the rows of the selected clips -> forward_selected"""
+        if isinstance(data, dict) and data.get('bank') is not None:
+            raise NotImplementedError("expert='selected' does not take the items of a data.EvalBank (they hold dense features on the device)")
+        window, shallow_window, mask, texts, text_cls, tmasks = args
+        sel = model_.select_clips(shallow_window, mask, text_cls)
+        if self.expert_fn is None:
+            rows = model_.gather_clip_rows(window, sel)
+        else:
+            rows = self.expert_fn(data, sel.clips_host())
+            if not torch.is_tensor(rows) or rows.dim() != 2 or rows.size(0) != sel.count:
+                raise ValueError(f'expert_fn returned {tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__} for {sel.count} clips: '
+                                 f'one row of D features per clip is expected')
+            if self.feature_dtype is not None:
+                rows = self._to_half(rows, 'the expert rows', data.get('clip_id', '?') if isinstance(data, dict) else '?')
+            elif shallow_window.dtype != torch.float16:
+                rows = rows.float()
+            rows = rows.to(shallow_window.device, non_blocking=True)
+        self.last_selection = sel
+        return model_.forward_selected(rows, sel, shallow_window, mask, texts, tmasks)
 
     @torch.no_grad()
     def launch_proposals(self, flat, T, data=None, window_ext=None):
@@ -516,6 +550,8 @@ class GroundingEvaluator:
         ``loss_meter``: a ``DeviceLossMeter`` of the bank the videos come from; on the device route, in each of the three modes, every
         video's forward is followed by ``loss_meter.update_device`` beside the counting.  The host route refuses it (ValueError:
         ``calc_loss`` per video is the host's validation loss)."""
+        if self.expert == 'selected' and batch_videos > 1:
+            raise NotImplementedError("expert='selected' runs one video per forward: run(batch_videos=1)")
         if loss_meter is not None and not isinstance(counter, DeviceRecallCounter):
             raise ValueError('run(loss_meter=...): the meter fills its table on the device route, run(counter=DeviceRecallCounter(...)); '
                              'calc_loss per video is the host route')

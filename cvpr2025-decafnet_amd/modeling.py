@@ -457,6 +457,33 @@ def _check_feature_dtypes(vid, shallow):
                          f'(cast one of them, or set model.half_features = False and pass both as fp32)')
 
 
+class Selection:
+    """What ``model.select_clips`` returns: the clips of one video that the gates of its queries need.
+
+    ``gate`` (nq, T) fp32 0 / 1 and ``pos`` (T) int32 (row of clip t in the list, -1 where it is not needed) stay on the device and
+    go to ``forward_selected`` as they are; ``count`` is a host int -- the one host read of the pattern, the caller must know what
+    to encode --, ``clips`` the device int32 view of the ``count`` needed clips in ascending order."""
+
+    def __init__(self, gate, pos, clips_buf, count):
+        self.gate, self.pos, self.count = gate, pos, int(count)
+        self.clips = clips_buf[:self.count]
+        self._host = None
+
+    @property
+    def T(self):
+        return self.gate.size(1)
+
+    @property
+    def nq(self):
+        return self.gate.size(0)
+
+    def clips_host(self):
+        """the needed clips as a CPU int64 tensor, ascending (copied once)"""
+        if self._host is None:
+            self._host = self.clips.cpu().long()
+        return self._host
+
+
 class PtTransformerEarlyFusionIterative(nn.Module):
     """Drop-in for libs/modeling/model.py:397-565 (created by libs/worker_v2.py:182-211).
 
@@ -860,6 +887,141 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         video's position encoding.  Same return structure as ``forward(..., eval=True)``."""
         return self._drop_forward_eval(vid, shallow_vid, vid_masks, text, None, text_masks, eval=True, gate=gate,
                                        pe_tokens=pe_tokens)
+
+    # -- selected-clip inference (include/decafnet_hip_select.h): expert features for the gated clips only ---------------------------
+    def _selected_refusals(self, what):
+        if self.scat:
+            raise NotImplementedError(f'{what}: opt.model.scat needs the sidekick scores, which the externally gated forward is not handed')
+        if self.sfonly and self.MODEL_KIND == 0:
+            raise NotImplementedError(f'{what}: opt.model.sfonly reads no expert features: there is nothing to select')
+        if self.vid_net.stride != 1:
+            raise NotImplementedError(f'{what}: vid_net.stride = {self.vid_net.stride}: the externally gated forward takes vid_net.stride = 1')
+
+    def select_clips(self, shallow_vid, vid_masks, text_cls):
+        """First call of the two-call pattern: which clips of this video does the model need expert features for?
+
+        shallow_vid (1, D, T) fp32 or float16, vid_masks (1, T), text_cls (nq, D) as ``forward`` takes them.  Runs the sidekick scores,
+        the block top-k gate and the compaction of the gates' union (dcf_op_sidekick(_h), dcf_op_gate, dcf_op_select_clips) on the
+        current stream and reads ONE int back, the number of needed clips.  Returns a ``Selection``.
+
+        The gate comes from the scoring kernels, not from the by-product of the shallow vid_map GEMM that ``forward(..., eval=True)``
+        uses where it can: the two scoring paths differ by ~2e-6 in a score and can therefore choose differently at an exact tie of
+        two pooled block scores."""
+        self._selected_refusals('select_clips')
+        if not shallow_vid.is_cuda:
+            raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
+        assert shallow_vid.dim() == 3 and shallow_vid.size(0) == 1, shallow_vid.size()
+        lib = _lib.lib()
+        dev = shallow_vid.device
+        T = shallow_vid.size(-1)
+        half = self.half_features and shallow_vid.dtype == torch.float16
+        sh = shallow_vid[0].contiguous() if half else shallow_vid[0].contiguous().float()
+        cls = text_cls.contiguous().float()
+        vm = vid_masks.reshape(-1).to(torch.bool).contiguous()
+        nq = cls.size(0)
+        assert sh.shape == (self.D, T) and vm.numel() == T and cls.shape == (nq, self.D), (sh.shape, vm.shape, cls.shape)
+        st = _lib.current_stream()
+        correl = torch.empty(nq, T, device=dev, dtype=torch.float32)
+        gate = torch.empty(nq, T, device=dev, dtype=torch.float32)
+        mo = torch.empty(nq, T, device=dev, dtype=torch.bool)
+        fn, what = (lib.dcf_op_sidekick_h, 'dcf_op_sidekick_h') if half else (lib.dcf_op_sidekick, 'dcf_op_sidekick')
+        _lib.check(fn(_lib.ptr(sh), _lib.ptr(cls), _lib.ptr(correl), self.D, T, nq, int(self.norm), st), what)
+        _lib.check(lib.dcf_op_gate(_lib.ptr(correl), _lib.ptr(vm), _lib.ptr(gate), _lib.ptr(mo), T, nq, self.sn, float(self.sratio),
+                                   int(self.msf), st), 'dcf_op_gate')
+        clips = torch.empty(T, device=dev, dtype=torch.int32)
+        pos = torch.empty(T, device=dev, dtype=torch.int32)
+        count = torch.empty(1, device=dev, dtype=torch.int32)
+        _lib.check(lib.dcf_op_select_clips(_lib.ptr(gate), _lib.ptr(vm), T, nq, _lib.ptr(clips), _lib.ptr(pos), _lib.ptr(count), st),
+                   'dcf_op_select_clips')
+        return Selection(gate, pos, clips, int(count.item()))
+
+    def gather_clip_rows(self, vid, selection):
+        """The rows ``forward_selected`` takes, made from dense features: vid (1, D, T) fp32 or float16 -> (count, D) of the same type,
+        row i = the features of clip ``selection.clips[i]`` (dcf_op_gather_clip_rows(_h)).  The emulation path of callers that hold
+        dense features."""
+        if not vid.is_cuda:
+            raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
+        assert vid.dim() == 3 and vid.size(0) == 1 and vid.size(1) == self.D and vid.size(2) == selection.T, (vid.size(), selection.T)
+        if selection.count < 1:
+            raise ValueError('gather_clip_rows: the selection is empty (no valid clip)')
+        lib = _lib.lib()
+        half = vid.dtype == torch.float16
+        x = vid[0].contiguous() if half else vid[0].contiguous().float()
+        rows = torch.empty(selection.count, self.D, device=vid.device, dtype=x.dtype)
+        fn, what = (lib.dcf_op_gather_clip_rows_h, 'dcf_op_gather_clip_rows_h') if half else (lib.dcf_op_gather_clip_rows, 'dcf_op_gather_clip_rows')
+        _lib.check(fn(_lib.ptr(x), selection.T, _lib.ptr(selection.clips), selection.count, self.D, _lib.ptr(rows), _lib.current_stream()), what)
+        return rows
+
+    def forward_selected(self, vid_rows, selection, shallow_vid, vid_masks, text, text_masks, pe_tokens=None):
+        """Second call of the two-call pattern: the eval forward with the expert features of the selected clips only.
+
+        vid_rows: (count, D) fp32 or float16 on the GPU, row i = the expert features of clip ``selection.clips[i]`` (more rows than
+        ``count`` are allowed: a capacity buffer; the rest is never read).  selection: what ``select_clips`` returned for this video
+        and these queries.  shallow_vid (1, D, T), vid_masks (1, T), text / text_masks as ``forward`` takes them; the dtype rule of the
+        dense pair holds for (vid_rows, shallow_vid).  Same return structure as ``forward(..., eval=True)``; the values are those of
+        ``forward_window(dense vid, ..., gate=selection.gate)`` up to the summation order of the expert product.  Always launched
+        eagerly (no HIP graph)."""
+        self._selected_refusals('forward_selected')
+        _check_feature_dtypes(vid_rows, shallow_vid)
+        if not (vid_rows.is_cuda and shallow_vid.is_cuda):
+            raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
+        assert shallow_vid.dim() == 3 and shallow_vid.size(0) == 1, shallow_vid.size()
+        T = shallow_vid.size(-1)
+        n = selection.count
+        if n < 1:
+            raise ValueError('forward_selected: the selection is empty (no valid clip)')
+        if vid_rows.dim() != 2 or vid_rows.size(1) != self.D or vid_rows.size(0) < n:
+            raise ValueError(f'forward_selected: vid_rows is {tuple(vid_rows.shape)}, the selection needs ({n}, {self.D}): one row of '
+                             f'D expert features per selected clip')
+        if not isinstance(text, (tuple, list)):
+            text, text_masks = (text,), (text_masks,)
+        nq = len(text)
+        if selection.T != T or selection.nq != nq or selection.pos.numel() != T:
+            raise ValueError(f'forward_selected: the selection is for {selection.nq} queries on {selection.T} clips, the call has {nq} '
+                             f'on {T}')
+        dev = shallow_vid.device
+        if self._engine is None:
+            self._engine = _Engine(self._config())
+        self._raise_if_flagged()
+        eng = self._engine
+        eng.bind(self)
+        lib = eng.lib
+        half = self.half_features and vid_rows.dtype == torch.float16
+        rows_c = vid_rows.contiguous() if half else vid_rows.contiguous().float()
+        sh_c = shallow_vid[0].contiguous() if half else shallow_vid[0].contiguous().float()
+        mask_c = vid_masks.reshape(-1).to(torch.bool).contiguous()
+        gate_c, pos_c = selection.gate.contiguous().float(), selection.pos.contiguous()
+        assert mask_c.numel() == T and sh_c.shape == (self.D, T) and pos_c.dtype == torch.int32
+        keep = []
+        tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
+        for q in range(nq):
+            t = text[q][0].contiguous().float()                              # (TE, Lk)
+            m = text_masks[q].reshape(-1).to(torch.bool).contiguous()
+            assert t.dim() == 2 and m.numel() == t.size(1)
+            keep += [t, m]
+            tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
+        pe = None
+        if self.vid_net.use_abs_pe:
+            pe = self._position_encoding(T, dev) if pe_tokens is None else pe_tokens.contiguous().float()
+            assert pe.shape == (T, self.E)
+            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), T), 'dcf_model_set_pe')
+        S = lib.dcf_points_per_query(eng.handle, T)
+        logits = torch.empty(nq, S, device=dev, dtype=torch.float32)
+        offsets = torch.empty(nq, S, 2, device=dev, dtype=torch.float32)
+        masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
+        fn, what = (lib.dcf_forward_eval_selected_h, 'dcf_forward_eval_selected_h') if half else \
+                   (lib.dcf_forward_eval_selected, 'dcf_forward_eval_selected')
+        _lib.check(fn(eng.handle, _lib.ptr(rows_c), n, _lib.ptr(pos_c), _lib.ptr(sh_c), _lib.ptr(mask_c), T, nq, tptr, mptr, tlen,
+                      _lib.ptr(gate_c), _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()), what)
+        self.last_feature_dtype = torch.float16 if half else torch.float32
+        self._last_inputs = (rows_c, sh_c, mask_c, gate_c, pos_c, keep, pe)
+        self._last_flat = (logits, offsets, masks)
+        self._probe_numerics()
+        sizes = [T >> l for l in range(self.vid_net.arch[2])]
+        lg = [tuple(x.unsqueeze(0) for x in logits[q].split(sizes)) for q in range(nq)]
+        of = [tuple(x.unsqueeze(0) for x in offsets[q].split(sizes)) for q in range(nq)]
+        mk = [tuple(x.unsqueeze(0) for x in masks[q].split(sizes)) for q in range(nq)]
+        return lg, of, mk
 
     # -- one long video cut at pyramid level k (dist.hybrid_forward; dcf_hybrid_phase1 / 2 / 3) --------------------------------
     def hybrid_phase1(self, vid_w, shallow_w, mask_w, text, text_masks, gate_w, k, Tc, pe_tokens=None):
