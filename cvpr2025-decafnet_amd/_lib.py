@@ -372,6 +372,32 @@ SELECT = (
 )
 
 
+# selected-clip inference on several videos per forward (include/decafnet_hip_select_videos.h, csrc/select_videos.hip; the two
+# forwards in csrc/engine.hip).  ``nq_per_video`` / ``row_first`` and every array of pointers are HOST arrays; ``clips`` / ``pos`` /
+# ``counts`` are int32 in device memory.
+_PP, _IP = ctypes.POINTER(vp), ctypes.POINTER(i32)
+_SELV = [i32, _PP, _PP, i64, _IP, _PP, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, vp]
+_FWD_SELV = [_IP, c_i32p, _PP, _PP, i64, _IP, _PP, _PP, _IP, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, vp]
+SELECT_VIDEOS_TABLE = {
+    'dcf_select_videos_ext_version': (i32, []),
+    'dcf_op_select_clips_videos': (i32, [c_f32p, c_u8p, i32, i32, _IP, c_i32p, c_i32p, c_i32p, vp]),
+    'dcf_op_gather_clip_rows_videos': (i32, [_PP, i64, c_i32p, i32, i32, _IP, i32, c_f32p, vp]),
+    'dcf_op_gather_clip_rows_videos_h': (i32, [_PP, i64, c_i32p, i32, i32, _IP, i32, c_f16p, vp]),
+    'dcf_select_videos': (i32, [vp] + _SELV),
+    'dcf_select_videos_h': (i32, [vp] + _SELV),
+    'dcf_forward_eval_videos_selected': (i32, [vp, i32, c_f32p] + _FWD_SELV),
+    'dcf_forward_eval_videos_selected_h': (i32, [vp, i32, c_f16p] + _FWD_SELV),
+}
+
+
+# Bound by lib() after SELECT, and waiting for the same follow-up (the cases are tests/select_videos_abi_cases.py, run through the
+# border driver by tests/test_gpu_select_videos_borders.py).
+SELECT_VIDEOS = (
+    Extension('select_videos', 'decafnet_hip_select_videos.h', 'dcf_select_videos_ext_version', 1, 'DCF_SELECT_VIDEOS_EXT_VERSION',
+              ('decafnet_hip.h',), SELECT_VIDEOS_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -383,11 +409,11 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG + ATTN_DROP + SELECT:
+        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG + ATTN_DROP + SELECT + SELECT_VIDEOS:
             for name, (res, args) in ext.table.items():
                 if name in bound:
                     raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED / _lib.FIT / '
-                                       f'_lib.STEPLOG / _lib.ATTN_DROP / _lib.SELECT')
+                                       f'_lib.STEPLOG / _lib.ATTN_DROP / _lib.SELECT / _lib.SELECT_VIDEOS')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

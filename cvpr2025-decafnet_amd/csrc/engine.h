@@ -125,7 +125,8 @@ struct dcf_model {
   int64_t text_pe_L = 0;
   char* text_ws = nullptr;
   size_t text_ws_bytes = 0;
-  // half features (decafnet_hip_half.h) of a forward that cannot read them natively: their fp32 copies, vid then shallow of every video
+  // half features (decafnet_hip_half.h) of a forward that cannot read them natively: their fp32 copies, vid then shallow of every video;
+  // between forwards the scratch of dcf_select_videos (scores' partial sums, the masks side by side): stream order keeps the two apart
   char* half_ws = nullptr;
   size_t half_ws_bytes = 0;
 
@@ -227,6 +228,10 @@ struct ForwardCall {
   // dcf_forward_eval_selected (with `gate`): the expert features of the selected clips only, clip-major fp32 rows (sel_n, D), and
   // sel_pos (T) int32, the row of clip t among them or -1 (dcf_op_select_clips); the video's vid pointer is null
   const float* sel_rows = nullptr; const int32_t* sel_pos = nullptr; int sel_n = 0;
+  // dcf_forward_eval_videos_selected: several videos, vs.nvid of them: sel_rows holds the rows of all of them, video v's from row
+  // sel_first[v] on (sel_first[nvid] = sel_n), sel_pos is (nvid, T) and video-local; sel_first = nullptr is the one-video form.
+  // sel_correl (nq, T): the sidekick scores a scat model needs, handed over by the caller (dcf_select_videos wrote them)
+  const int32_t* sel_first = nullptr; const float* sel_correl = nullptr;
 };
 
 // the level-cut state of dcf_hybrid_phase1 / 2 / 3 (engine_hybrid.hip)
@@ -304,6 +309,8 @@ int run_embd_chain(dcf_model* m, const float* X, int64_t ldx, const uint8_t* nbr
 
 // ---- engine.hip
 int forward(dcf_model* m, const VideoSet& vs, int T0, int nq, const ForwardCall& fc, hipStream_t st);
+int launch_gather_masks(const uint8_t* const* masks, int nvid, uint8_t* dst, int T0, hipStream_t st);   // dst (nvid, T0)
+int grow_half_ws(dcf_model* m, size_t need, hipStream_t st);     // m->half_ws holds at least `need` bytes afterwards
 void launch_masks_out(const uint8_t* mask_all, uint8_t* out, const LevelTable* lt, const unsigned* status, float* logits, int rows,
                       hipStream_t st);
 

@@ -17,6 +17,7 @@
 #include "engine.h"
 #include "../../include/decafnet_hip_half.h"
 #include "../../include/decafnet_hip_select.h"
+#include "../../include/decafnet_hip_select_videos.h"
 
 namespace dcf {
 
@@ -55,12 +56,13 @@ __global__ void k_points_out(const float* __restrict__ rows, float* __restrict__
   out[(int64_t)b * lt->S + lt->off[l] + t] = rows[r];
 }
 
-// gate[b][t] = override[q0 + b][t]; mask = vid_mask (msf) or vid_mask & gate (model.py:544-545)
+// gate[b][t] = override[q0 + b][t]; mask = vid_mask (msf) or vid_mask & gate (model.py:544-545).  vid_mask (nvid, T): batch element b
+// reads the row of its own video, nibble b of vmap (0 for one video)
 __global__ void k_apply_gate(const float* __restrict__ gate_in, const uint8_t* __restrict__ vid_mask, float* __restrict__ gate,
-                             uint8_t* __restrict__ mask_out, int T, int rows, int msf) {
+                             uint8_t* __restrict__ mask_out, int T, int rows, int msf, unsigned long long vmap) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
-  const int t = r % T;
+  const int t = r % T + (int)((vmap >> (4 * ((r / T) & 15))) & 15ull) * T;
   const float g = gate_in[r];
   const bool m = vid_mask[t] != 0;
   gate[r] = g;
@@ -72,9 +74,16 @@ __global__ void k_gather_masks(MaskPtrs mp, uint8_t* __restrict__ dst, int T0) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < T0) dst[(size_t)blockIdx.y * T0 + t] = mp.p[blockIdx.y][t];
 }
+// the videos' masks side by side, dst (nvid, T0): one launch (it was one copy node per video)
+int launch_gather_masks(const uint8_t* const* masks, int nvid, uint8_t* dst, int T0, hipStream_t st) {
+  MaskPtrs mp{};
+  for (int v = 0; v < nvid; ++v) mp.p[v] = masks[v];
+  hipLaunchKernelGGL(k_gather_masks, dim3((unsigned)((T0 + 255) / 256), (unsigned)nvid), dim3(256), 0, st, mp, dst, T0);
+  DCF_HIP(hipGetLastError());
+  return 0;
+}
 
-// m->half_ws holds at least `need` bytes afterwards
-static int grow_half_ws(dcf_model* m, size_t need, hipStream_t st) {
+int grow_half_ws(dcf_model* m, size_t need, hipStream_t st) {
   if (need <= m->half_ws_bytes) return 0;
   DCF_CHECK(!m->capturing, "internal: workspace growth during graph capture");
   drop_graph(m, true);                          // (a captured graph bakes the copies' addresses in)
@@ -129,7 +138,8 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
   const int L = m->hyb_levels > 0 ? m->hyb_levels : c.n_levels;      // dcf_hybrid_phase1: the pyramid up to the split level only
   const int nvid = vs.nvid;
   if (m->hyb) m->hyb->valid = false;              // the phases of a level-cut forward live in this workspace
-  DCF_CHECK(!(fc.gate && nvid != 1), "the externally gated forward takes one video");
+  const bool sel = fc.sel_rows != nullptr;        // dcf_forward_eval_selected: the expert product on the rows of the selected clips
+  DCF_CHECK(!(fc.gate && nvid != 1) || (sel && fc.sel_first), "the externally gated forward takes one video");
   int video_of[DCF_MAX_VIDEOS * 64];           // flat query -> video
   {
     int tot = 0;
@@ -176,12 +186,14 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
   }
   carve_at(m->arena, c, T0, Bmax, nq, S, Lk, nvid, b, m->hyb_extra, &m->hyb_extra_ptr);
   // ---- per video: sidekick scores and the query-independent halves of vid_map
-  DCF_CHECK(!(fc.gate && c.scat), "opt.model.scat needs the sidekick scores: the externally gated (T-sharded) forward does not take them");
-  const bool sel = fc.sel_rows != nullptr;        // dcf_forward_eval_selected: the expert product on the rows of the selected clips
+  DCF_CHECK(!(fc.gate && c.scat) || fc.sel_correl, "opt.model.scat needs the sidekick scores: the externally gated (T-sharded) forward does not take them");
+  SelFirst sel_first{};                           // first row of every video among the selected rows
   if (sel) {
-    DCF_CHECK(fc.gate && fc.sel_pos && nvid == 1, "internal: the selected-clip forward is an externally gated forward of one video");
+    DCF_CHECK(fc.gate && fc.sel_pos && (nvid == 1 || fc.sel_first), "internal: the selected-clip forward is an externally gated forward");
+    DCF_CHECK(!fc.sel_correl || (fc.sel_first && c.scat), "internal: the scores go with dcf_forward_eval_videos_selected on a scat model");
+    for (int v = 0; v <= nvid; ++v) sel_first.r[v] = fc.sel_first ? fc.sel_first[v] : (v == 0 ? 0 : fc.sel_n);
     DCF_CHECK(m->vid_w1, "dcf_forward_eval_selected: opt.model.sfonly reads no expert features: there is nothing to select");
-    DCF_CHECK(fc.sel_n >= 1 && fc.sel_n <= T0, "dcf_forward_eval_selected: n_rows=%d must lie in [1, T=%d]", fc.sel_n, T0);
+    DCF_CHECK(fc.sel_n >= 1 && fc.sel_n <= (int64_t)nvid * T0, "dcf_forward_eval_selected: n_rows=%d must lie in [1, T=%d] a video", fc.sel_n, T0);
     DCF_CHECK(D % 4 == 0 && aligned16(fc.sel_rows), "dcf_forward_eval_selected: vid_rows needs D %% 4 == 0 and a 16-byte aligned base");
   }
   // The sidekick scores ride on the shallow half of vid_map where they can: that GEMM streams exactly the (D, T) matrix the scores
@@ -248,12 +260,7 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
       return 0;
     };
     auto gather_masks = [&]() -> int {
-      if (nvid > 1) {                               // the videos' masks side by side: one launch (it was one copy node per video)
-        MaskPtrs mp{};
-        for (int v = 0; v < nvid; ++v) mp.p[v] = vs.mask[v];
-        hipLaunchKernelGGL(k_gather_masks, dim3((unsigned)((T0 + 255) / 256), (unsigned)nvid), dim3(256), 0, st, mp, b.maskv, T0);
-        DCF_HIP(hipGetLastError());
-      }
+      if (nvid > 1) TRY(launch_gather_masks(vs.mask, nvid, b.maskv, T0, st));
       return 0;
     };
     if (gate_first) {
@@ -293,7 +300,7 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
         // needed by construction, so no tile is skipped
         GemmArgs ge = gemm(fc.sel_rows, D, m->vid_w1, nullptr, b.P1, E, fc.sel_n, E, D);
         ge.ldw = m->vid_ldw; ge.a_scale = 1.f;
-        TRY(run_gemm(m, &ge, 1, A_ROWS, st));
+        TRY(run_gemm(m, &ge, 1, A_ROWS, st));        // (several videos: ONE product over the packed rows of all of them)
       }
     }
   }
@@ -314,7 +321,7 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
     if (fc.gate) {
       // T-sharded videos: the gate was selected globally (all-gathered scores) by the caller
       hipLaunchKernelGGL(k_apply_gate, dim3((rows0 + 255) / 256), dim3(256), 0, st, fc.gate + (int64_t)q0 * T0, vid_mask,
-                         b.gate, mask_in, T0, rows0, c.msf);
+                         b.gate, mask_in, T0, rows0, c.msf, vmap);
       DCF_HIP(hipGetLastError());
     } else if (!gate_first) {                      // (gate_first: selected in front of the expert products, above)
       GateArgs ga{b.correl, vid_mask, b.gate, mask_in, T0, B, q0, c.sn, c.msf, (double)c.sratio, vmap, nullptr, 0};
@@ -332,7 +339,8 @@ int forward(dcf_model* m, const VideoSet& vs_in, int T0, int nq, const ForwardCa
     const uint8_t* maskP = b.mask_all;            // pyramid level 0
 
     // ---- vid_map (model.py:543-555)
-    if (sel) TRY(launch_vidmap_combine_sel(b.P1, fc.sel_pos, m->vid_w2 ? b.P2 : nullptr, m->vid_map_b, b.gate, mask0, b.X, T0, rows0, E, st));
+    if (sel) TRY(launch_vidmap_combine_sel(b.P1, fc.sel_pos, sel_first, m->vid_w2 ? b.P2 : nullptr, m->vid_map_b, b.gate, mask0, m->vid_w3,
+                                           m->vid_w3 ? fc.sel_correl + (int64_t)q0 * T0 : nullptr, b.X, T0, rows0, E, vmap, st));
     else
     TRY(launch_vidmap_combine(m->vid_w1 ? b.P1 : nullptr, m->vid_w2 ? b.P2 : nullptr, m->vid_map_b, b.gate, mask0,
                               m->vid_w3, m->vid_w3 ? b.correl + (int64_t)q0 * T0 : nullptr, b.X, T0, rows0, E, vmap, st));
@@ -866,6 +874,94 @@ int dcf_forward_eval_selected_h(dcf_model* m, const uint16_t* vid_rows, int32_t 
   if (dcf::launch_half_to_f32(shallow_vid, sh32, (int64_t)D * T, st)) return -1;
   return dcf::forward_selected(m, who, rows32, n_rows, pos, sh32, vid_mask, T, nq, text, text_mask, text_len, gate, logits_out, offsets_out,
                                masks_out, st);
+}
+
+namespace dcf {
+// the refusals of the several-video selected forward that need no workspace: before any launch, and before the half form's upcast;
+// *nq_out = the queries of all videos
+static int videos_selected_checks(const dcf_model* m, const char* who, int nvid, const int32_t* row_first, int64_t T,
+                                  const int32_t* nq_per_video, const float* correl, int* nq_out) {
+  DCF_CHECK(T >= 1 && T < (1ll << 24), "%s: T out of range", who);
+  DCF_CHECK(m->finalized, "%s: model not finalized", who);
+  DCF_CHECK(nvid >= 1 && nvid <= DCF_MAX_VIDEOS, "%s: 1 .. %d videos per call (got %d)", who, DCF_MAX_VIDEOS, nvid);
+  DCF_CHECK(m->vid_w1, "%s: opt.model.sfonly reads no expert features: there is nothing to select", who);
+  DCF_CHECK(vid_stride_of(m->cfg) == 1, "%s: vid_net.stride = %d: the externally gated forward takes vid_net.stride = 1", who, vid_stride_of(m->cfg));
+  DCF_CHECK(!m->cfg.scat == !correl, "%s: correl (the sidekick scores of dcf_select_videos) is required with opt.model.scat and must be "
+                                     "null without it", who);
+  int nq = 0;
+  for (int v = 0; v < nvid; ++v) {
+    DCF_CHECK(nq_per_video[v] >= 1 && nq + nq_per_video[v] <= DCF_MAX_VIDEOS * 64, "%s: bad query count of video %d", who, v);
+    nq += nq_per_video[v];
+  }
+  const int Bmax = std::min(nq, m->cfg.max_batch > 0 ? m->cfg.max_batch : 8);
+  DCF_CHECK(nvid == 1 || Bmax <= 16, "%s: several videos per forward need max_batch <= 16 (got %d)", who, Bmax);
+  DCF_CHECK(row_first[0] == 0, "%s: row_first[0] = %d, not 0", who, (int)row_first[0]);
+  for (int v = 0; v < nvid; ++v) {
+    const int64_t n = (int64_t)row_first[v + 1] - row_first[v];
+    DCF_CHECK(n >= 1 && n <= T, "%s: video %d has %lld rows: every video needs 1 .. T = %lld", who, v, (long long)n, (long long)T);
+  }
+  *nq_out = nq;
+  return 0;
+}
+static int forward_videos_selected(dcf_model* m, int nvid, const float* rows, const int32_t* row_first, const int32_t* pos,
+                                   const float* const* shallow, const uint8_t* const* vid_mask, int64_t T, const int32_t* nq_per_video,
+                                   int nq, const float* const* text, const uint8_t* const* text_mask, const int32_t* text_len,
+                                   const float* gate, const float* correl, float* logits_out, float* offsets_out, uint8_t* masks_out,
+                                   hipStream_t st) {
+  VideoSet vs;
+  vs.nvid = nvid;
+  for (int v = 0; v < nvid; ++v) {
+    vs.vid[v] = nullptr; vs.shallow[v] = shallow[v]; vs.mask[v] = vid_mask[v]; vs.text_cls[v] = nullptr; vs.nq[v] = nq_per_video[v];
+  }
+  ForwardCall fc{text, text_mask, text_len, gate, logits_out, offsets_out, masks_out};
+  fc.sel_rows = rows; fc.sel_pos = pos; fc.sel_n = row_first[nvid]; fc.sel_first = row_first; fc.sel_correl = correl;
+  return forward_maybe_graph(m, vs, (int)T, nq, fc, st);
+}
+}  // namespace dcf
+
+int dcf_forward_eval_videos_selected(dcf_model* m, int32_t nvid, const float* vid_rows, const int32_t* row_first, const int32_t* pos,
+                                     const float* const* shallow_vid, const uint8_t* const* vid_mask, int64_t T,
+                                     const int32_t* nq_per_video, const float* const* text, const uint8_t* const* text_mask,
+                                     const int32_t* text_len, const float* gate, const float* correl, float* logits_out,
+                                     float* offsets_out, uint8_t* masks_out, void* stream) {
+  const char* who = "dcf_forward_eval_videos_selected";
+  DCF_CHECK(m && vid_rows && row_first && pos && shallow_vid && vid_mask && nq_per_video && text && text_len && gate && logits_out &&
+                offsets_out && masks_out, "%s: null argument", who);
+  int nq = 0;
+  if (dcf::videos_selected_checks(m, who, nvid, row_first, T, nq_per_video, correl, &nq)) return -1;
+  for (int v = 0; v < nvid; ++v) DCF_CHECK(shallow_vid[v] && vid_mask[v], "%s: video %d is incomplete", who, v);
+  return dcf::forward_videos_selected(m, nvid, vid_rows, row_first, pos, shallow_vid, vid_mask, T, nq_per_video, nq, text, text_mask,
+                                      text_len, gate, correl, logits_out, offsets_out, masks_out, (hipStream_t)stream);
+}
+
+int dcf_forward_eval_videos_selected_h(dcf_model* m, int32_t nvid, const uint16_t* vid_rows, const int32_t* row_first,
+                                       const int32_t* pos, const uint16_t* const* shallow_vid, const uint8_t* const* vid_mask, int64_t T,
+                                       const int32_t* nq_per_video, const float* const* text, const uint8_t* const* text_mask,
+                                       const int32_t* text_len, const float* gate, const float* correl, float* logits_out,
+                                       float* offsets_out, uint8_t* masks_out, void* stream) {
+  const char* who = "dcf_forward_eval_videos_selected_h";
+  DCF_CHECK(m && vid_rows && row_first && pos && shallow_vid && vid_mask && nq_per_video && text && text_len && gate && logits_out &&
+                offsets_out && masks_out, "%s: null argument", who);
+  int nq = 0;
+  if (dcf::videos_selected_checks(m, who, nvid, row_first, T, nq_per_video, correl, &nq)) return -1;
+  for (int v = 0; v < nvid; ++v) DCF_CHECK(shallow_vid[v] && vid_mask[v], "%s: video %d is incomplete", who, v);
+  // the packed rows and every video's shallow features upcast once into the engine's half workspace (exact), then the fp32 form
+  hipStream_t st = (hipStream_t)stream;
+  const int D = m->cfg.D;
+  const int64_t n_rows = row_first[nvid];
+  const size_t rows_b = ((size_t)n_rows * D * sizeof(float) + 255) & ~(size_t)255;
+  const size_t sh_b = ((size_t)D * T * sizeof(float) + 255) & ~(size_t)255;
+  if (dcf::grow_half_ws(m, rows_b + sh_b * nvid, st)) return -1;
+  float* rows32 = reinterpret_cast<float*>(m->half_ws);
+  const float* sh32[dcf::DCF_MAX_VIDEOS];
+  if (dcf::launch_half_to_f32(vid_rows, rows32, n_rows * D, st)) return -1;
+  for (int v = 0; v < nvid; ++v) {
+    float* d = reinterpret_cast<float*>(m->half_ws + rows_b + sh_b * v);
+    if (dcf::launch_half_to_f32(shallow_vid[v], d, (int64_t)D * T, st)) return -1;
+    sh32[v] = d;
+  }
+  return dcf::forward_videos_selected(m, nvid, rows32, row_first, pos, sh32, vid_mask, T, nq_per_video, nq, text, text_mask, text_len, gate,
+                                      correl, logits_out, offsets_out, masks_out, st);
 }
 
 int dcf_graph_active(const dcf_model* m) { return m ? m->last_launch : 0; }

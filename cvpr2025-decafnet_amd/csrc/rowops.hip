@@ -65,28 +65,31 @@ __global__ void k_mask_down(const uint8_t* __restrict__ in, uint8_t* __restrict_
 // P1 = W[:, :D] . vid, P2 = W[:, D:2D] . shallow are query independent and computed once; w3 = W[:, 2D] is the
 // column of the raw-score channel (opt.model.scat).  P1 is null for sfonly, P2 without msf, w3 without scat.
 // ------------------------------------------------------------------------------------------
-// SEL (dcf_forward_eval_selected): P1 holds the expert products of the selected clips only, one row per clip of the selection;
-// pos[t] is clip t's row in it (or -1: not selected -- then the clip contributes no expert half, whatever its gate says)
+// SEL (dcf_forward_eval_selected, dcf_forward_eval_videos_selected): P1 holds the expert products of the selected clips only, one
+// row per clip of the selection, video after video; pos[v * T + t] is clip t's row among those of its video v (or -1: not selected --
+// then the clip contributes no expert half, whatever its gate says), first.r[v] the video's first row
 template <int NCH, bool SEL>
 __device__ __forceinline__ void vidmap_combine_row(const float* __restrict__ P1, const float* __restrict__ P2,
                                                    const float* __restrict__ bias, const float* __restrict__ gate,
                                                    const uint8_t* __restrict__ mask,
                                                    const float* __restrict__ w3, const float* __restrict__ correl,
                                                    float* __restrict__ X, int T, int rows, int E,
-                                                   unsigned long long vmap, const int* __restrict__ vtab, const int* __restrict__ pos) {
+                                                   unsigned long long vmap, const int* __restrict__ vtab, const int* __restrict__ pos,
+                                                   const SelFirst* first) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   // row of the video's products: video (vmap >> 4b) & 15 of batch element b = r / T (0 for one video), or vtab[b] where a
   // table is given (any number of videos: the training front end, front_grad.hip)
-  const int t = r % T + (vtab ? vtab[r / T] : (int)((vmap >> (4 * ((r / T) & 15))) & 15ull)) * T;
+  const int v = vtab ? vtab[r / T] : (int)((vmap >> (4 * ((r / T) & 15))) & 15ull);
+  const int t = r % T + v * T;
   const float m = mask[r] ? 1.f : 0.f;
   const float g = gate[r];
   const float s = w3 ? correl[r] : 0.f;     // scat: the clip's raw sidekick score is one more input channel
   Row<NCH> a, b;
   if constexpr (SEL) {
-    const int pr = g != 0.f ? pos[r % T] : -1;
-    if (pr >= 0) a.load(P1 + (int64_t)pr * E, E, lane); else a.zero();
+    const int pr = g != 0.f ? pos[t] : -1;
+    if (pr >= 0) a.load(P1 + (int64_t)(first->r[v] + pr) * E, E, lane); else a.zero();
   } else {
     if (P1 && g != 0.f) a.load(P1 + (int64_t)t * E, E, lane); else a.zero();     // (rows under a closed gate may not exist: GemmArgs::tile_skip)
   }
@@ -110,14 +113,16 @@ __global__ __launch_bounds__(256) void k_vidmap_combine(const float* __restrict_
                                                          const float* __restrict__ w3, const float* __restrict__ correl,
                                                          float* __restrict__ X, int T, int rows, int E,
                                                          unsigned long long vmap, const int* __restrict__ vtab) {
-  vidmap_combine_row<NCH, false>(P1, P2, bias, gate, mask, w3, correl, X, T, rows, E, vmap, vtab, nullptr);
+  vidmap_combine_row<NCH, false>(P1, P2, bias, gate, mask, w3, correl, X, T, rows, E, vmap, vtab, nullptr, nullptr);
 }
 template <int NCH>
 __global__ __launch_bounds__(256) void k_vidmap_combine_sel(const float* __restrict__ P1c, const float* __restrict__ P2,
                                                              const float* __restrict__ bias, const float* __restrict__ gate,
                                                              const uint8_t* __restrict__ mask, const int* __restrict__ pos,
-                                                             float* __restrict__ X, int T, int rows, int E) {
-  vidmap_combine_row<NCH, true>(P1c, P2, bias, gate, mask, nullptr, nullptr, X, T, rows, E, 0ull, nullptr, pos);
+                                                             const float* __restrict__ w3, const float* __restrict__ correl,
+                                                             float* __restrict__ X, int T, int rows, int E,
+                                                             unsigned long long vmap, SelFirst first) {
+  vidmap_combine_row<NCH, true>(P1c, P2, bias, gate, mask, w3, correl, X, T, rows, E, vmap, nullptr, pos, &first);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -599,13 +604,14 @@ int launch_vidmap_combine(const float* P1, const float* P2, const float* bias, c
   return 0;
 }
 
-int launch_vidmap_combine_sel(const float* P1c, const int* pos, const float* P2, const float* bias, const float* gate, const uint8_t* mask,
-                              float* X, int T, int rows, int E, hipStream_t st) {
+int launch_vidmap_combine_sel(const float* P1c, const int* pos, const SelFirst& first, const float* P2, const float* bias, const float* gate,
+                              const uint8_t* mask, const float* w3, const float* correl, float* X, int T, int rows, int E,
+                              unsigned long long vmap, hipStream_t st) {
   if (rows <= 0) return 0;
-  DCF_CHECK(P1c && pos, "launch_vidmap_combine_sel: null operand");
+  DCF_CHECK(P1c && pos && (!w3 || correl), "launch_vidmap_combine_sel: null operand");
   ProfScope prof("vidmap_combine_sel", st, 3.0 * rows * E, 4.0 * 3.0 * rows * E);
   DISPATCH_NCH(E, hipLaunchKernelGGL((k_vidmap_combine_sel<NCH>), dim3((rows + 3) / 4), dim3(256), 0, st, P1c, P2, bias, gate, mask, pos,
-                                     X, T, rows, E));
+                                     w3, correl, X, T, rows, E, vmap, first));
   return 0;
 }
 

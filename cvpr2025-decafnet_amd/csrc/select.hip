@@ -2,103 +2,21 @@
 // (dcf_op_select_clips) and the transposing gather that makes clip-major rows of dense channel-major features
 // (dcf_op_gather_clip_rows, _h).  The two forwards of the extension live in engine.hip beside the forwards they are a form of.
 //
-// k_select_clips is a stream compaction by ONE workgroup of 16 waves.  A strip is 4 sub-strips of 1024 clips, thread i takes clip
-// i of each: its gate loads are coalesced, and a sub-strip's order is the lane order, so a wave's ballot and a popcount below the
-// lane give the rank inside the wave.  The 4 x 16 wave counts go through LDS (double buffered: one barrier per strip), every thread
-// adds up the ones in front of its own, and the count of all strips before rides in a register.  The flags of the next strip are
-// loaded before the scan of the current one.  No atomics: the list is ascending by construction.
+// The device code of both kernels is in select.h, which the several-video forms (select_videos.hip) call too.
 #include "../../include/decafnet_hip_select.h"
-#include "common.h"
+#include "select.h"
 
 namespace dcf {
 
-constexpr int SEL_NT = 1024, SEL_WAVES = SEL_NT / DCF_WAVE, SEL_SUB = 4;
-constexpr int SEL_STRIP = SEL_NT * SEL_SUB;
-
 __global__ __launch_bounds__(SEL_NT) void k_select_clips(const float* __restrict__ gate, const uint8_t* __restrict__ mask, int T, int nq,
                                                          int* __restrict__ clips, int* __restrict__ pos, int* __restrict__ count) {
-  __shared__ int tot[2][SEL_SUB * SEL_WAVES];
-  const int tid = threadIdx.x, lane = tid & (DCF_WAVE - 1), wave = tid / DCF_WAVE;
-  // bit j: clip t0 + j * SEL_NT + tid is needed
-  auto flags = [&](long long t0) -> unsigned {
-    unsigned f = 0;
-#pragma unroll
-    for (int j = 0; j < SEL_SUB; ++j) {
-      const long long t = t0 + j * SEL_NT + tid;
-      if (t < T) {
-        // the mask byte and every query's gate are loaded side by side: no load waits for the value of another
-        unsigned any = 0;
-        for (int q = 0; q < nq; ++q) any |= gate[(long long)q * T + t] != 0.f ? 1u : 0u;
-        f |= (mask[t] ? any : 0u) << j;
-      }
-    }
-    return f;
-  };
-  int carry = 0;
-  unsigned cur = flags(0);
-  int s = 0;
-  for (long long t0 = 0; t0 < T; t0 += SEL_STRIP, ++s) {
-    const unsigned nxt = t0 + SEL_STRIP < T ? flags(t0 + SEL_STRIP) : 0u;
-    int* tt = tot[s & 1];
-    unsigned long long bal[SEL_SUB];
-#pragma unroll
-    for (int j = 0; j < SEL_SUB; ++j) {
-      bal[j] = __ballot((cur >> j) & 1u);
-      if (lane == 0) tt[j * SEL_WAVES + wave] = __popcll(bal[j]);
-    }
-    __syncthreads();
-    int run = carry, base[SEL_SUB] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < SEL_SUB * SEL_WAVES; ++i) {
-      if ((i % SEL_WAVES) == wave) base[i / SEL_WAVES] = run;
-      run += tt[i];
-    }
-    carry = run;
-#pragma unroll
-    for (int j = 0; j < SEL_SUB; ++j) {
-      const long long t = t0 + j * SEL_NT + tid;
-      if (t < T) {
-        const bool need = (cur >> j) & 1u;
-        const int k = base[j] + __popcll(bal[j] & ((1ull << lane) - 1ull));
-        pos[t] = need ? k : -1;
-        if (need) clips[k] = (int)t;
-      }
-    }
-    cur = nxt;
-  }
-  if (tid == 0) *count = carry;
+  select_clips_body(gate, mask, T, nq, clips, pos, count);
 }
 
-// rows[i][d] = X[d * ldx + clips[i]]: a 64 x 64 tile through LDS.  Load phase: lane = clip of the tile, the waves walk the channels
-// (a wave reads 64 entries of one channel row: contiguous wherever the clip list is); the image is [channel][clip] at a pitch of 65
-// elements.  Store phase: lane = channel, the waves walk the clips (a wave writes 64 contiguous elements of one output row and reads
-// LDS at a stride of 65: conflict free for fp32).
-constexpr int GAT_NT = 256, GAT_WAVES = GAT_NT / DCF_WAVE, GAT_SIDE = DCF_WAVE;
 template <typename E>
 __global__ __launch_bounds__(GAT_NT) void k_gather_clip_rows(const E* __restrict__ X, long long ldx, const int* __restrict__ clips, int n,
                                                              int D, E* __restrict__ rows) {
-  __shared__ E tile[GAT_SIDE * (GAT_SIDE + 1)];
-  const int lane = threadIdx.x & (DCF_WAVE - 1), wave = threadIdx.x / DCF_WAVE;
-  const int i0 = blockIdx.x * GAT_SIDE, d0 = blockIdx.y * GAT_SIDE;
-  {
-    const int i = i0 + lane;
-    long long c = i < n ? clips[i] : 0;
-    c = c < 0 ? 0 : (c >= ldx ? ldx - 1 : c);      // no read outside the matrix, whatever the list holds
-#pragma unroll 4
-    for (int r = wave; r < GAT_SIDE; r += GAT_WAVES) {
-      const int d = d0 + r;
-      if (i < n && d < D) tile[r * (GAT_SIDE + 1) + lane] = X[(long long)d * ldx + c];
-    }
-  }
-  __syncthreads();
-  const int d = d0 + lane;
-  if (d >= D) return;
-#pragma unroll 4
-  for (int r = wave; r < GAT_SIDE; r += GAT_WAVES) {
-    const int i = i0 + r;
-    if (i >= n) break;
-    rows[(long long)i * D + d] = tile[lane * (GAT_SIDE + 1) + r];
-  }
+  gather_clip_rows_tile<E>(X, ldx, clips, n, D, rows, blockIdx.x * GAT_SIDE, blockIdx.y * GAT_SIDE);
 }
 
 template <typename E>

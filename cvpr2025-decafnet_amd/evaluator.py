@@ -314,13 +314,17 @@ class GroundingEvaluator:
     """``opt`` needs ``opt.model.{max_vid_len, num_fpn_levels, mha_win_size, vid_stride}``, ``opt.eval.{pre_nms_topk,
     pre_nms_thresh, seg_len_thresh}`` and ``opt.nms`` (libs/core/opt.py:174-194)."""
 
-    def __init__(self, opt, model, feature_dtype=None, expert='dense', expert_fn=None):
+    def __init__(self, opt, model, feature_dtype=None, expert='dense', expert_fn=None, select_videos=False):
         """``expert``: 'dense' (the default: the reference's interface, ``vid`` holds the expert features of every clip) or 'selected':
         per forward window ``model.select_clips`` says which clips the gates need, the expert features of those clips alone are
         obtained -- from ``expert_fn(sample, clips_host)`` -> (count, D) fp32 or float16 rows, clips_host the ascending int64 clip
         indices (all below the video's length), or, with ``expert_fn=None``, by ``model.gather_clip_rows`` from the sample's dense
         ``vid`` -- and ``model.forward_selected`` runs on them (include/decafnet_hip_select.h).  The proposal stage is the same.
-        Not here: several videos per forward (``run(batch_videos > 1)``) and the items of a ``data.EvalBank``.
+        ``select_videos`` (with expert='selected'; default False): ``run(batch_videos=N)`` groups videos of one padded length as the
+        dense route does, on the host route and on the device route; per group ``model.select_clips_videos`` (one host read for all
+        videos), ``expert_fn`` once per video -- its rows are packed video after video -- or ``model.gather_clip_rows_videos``, and
+        ONE ``model.forward_videos_selected`` (include/decafnet_hip_select_videos.h).  A ``scat`` model is accepted with it.  Without
+        it ``run(batch_videos > 1)`` is refused.  Not here in either form: the items of a ``data.EvalBank``.
         ``feature_dtype``: None -- ``vid`` / ``shallow_vid`` go to the GPU in the dtype they come in --, or 'float16': ``prepare``
         rounds them to float16 on the host, before padding, and uploads half the bytes; the forward reads them as they are
         (``model.half_features``).  The proposals then are those of features rounded to float16."""
@@ -333,7 +337,9 @@ class GroundingEvaluator:
             raise ValueError(f"expert {expert!r}: 'dense' or 'selected'")
         if expert_fn is not None and expert != 'selected':
             raise ValueError("expert_fn is the source of the selected clips' features: it needs expert='selected'")
-        self.expert, self.expert_fn = expert, expert_fn
+        if select_videos and expert != 'selected':
+            raise ValueError("select_videos groups the videos of the selected-clip route: it needs expert='selected'")
+        self.expert, self.expert_fn, self.select_videos = expert, expert_fn, bool(select_videos)
         mo = opt['model']
         self.max_vid_len = mo['max_vid_len']
         self.vid_stride = mo.get('vid_stride', 1)
@@ -430,7 +436,10 @@ class GroundingEvaluator:
         model_ = model or self.model
         args, T, self._window_ext = self.prepare(data, model_)
         t0 = time.perf_counter()
-        out = self._forward_selected(data, model_, args) if self.expert == 'selected' else model_(*args, eval=True)
+        if self.select_videos:                        # a group of one video: the same route as run(batch_videos=N), scat included
+            out = self._forward_group([(data, args, T, self._window_ext)], model_)[0]
+        else:
+            out = self._forward_selected(data, model_, args) if self.expert == 'selected' else model_(*args, eval=True)
         self.time_dict['forward'].append(time.perf_counter() - t0)
         self.outputs = out
         return model_._last_flat, T
@@ -455,6 +464,39 @@ class GroundingEvaluator:
             rows = rows.to(shallow_window.device, non_blocking=True)
         self.last_selection = sel
         return model_.forward_selected(rows, sel, shallow_window, mask, texts, tmasks)
+
+    def _forward_group(self, pending, model=None):
+        """one forward for the videos of ``pending`` ((data, args, T, ext) each, one padded length); the outputs are model._last_flat"""
+        videos = [p[1] for p in pending]
+        model_ = model or self.model
+        if not self.select_videos:
+            return model_.forward_videos(videos)
+        for data, _, _, _ in pending:
+            if isinstance(data, dict) and data.get('bank') is not None:
+                raise NotImplementedError("expert='selected' does not take the items of a data.EvalBank (they hold dense features on the device)")
+        batch = model_.select_clips_videos(videos)
+        if self.expert_fn is None:
+            rows = model_.gather_clip_rows_videos([a[0] for a in videos], batch)
+        else:
+            half = videos[0][1].dtype == torch.float16
+            parts = []
+            for v, (data, _, _, _) in enumerate(pending):
+                r = self.expert_fn(data, batch.clips_host(v))
+                if not torch.is_tensor(r) or r.dim() != 2 or r.size(0) != batch.counts[v]:
+                    raise ValueError(f'expert_fn returned {tuple(r.shape) if torch.is_tensor(r) else type(r).__name__} for {batch.counts[v]} '
+                                     f'clips: one row of D features per clip is expected')
+                if self.feature_dtype is not None:
+                    r = self._to_half(r, 'the expert rows', data.get('clip_id', '?') if isinstance(data, dict) else '?')
+                elif not half:
+                    r = r.float()
+                parts.append(r)
+            dev = videos[0][1].device
+            if any(r.is_cuda for r in parts):
+                rows = torch.cat([r.to(dev, non_blocking=True) for r in parts])
+            else:
+                rows = torch.cat(parts).to(dev, non_blocking=True)           # host rows: packed on the host, ONE upload
+        self.last_selection = batch
+        return model_.forward_videos_selected(rows, batch, videos)
 
     @torch.no_grad()
     def launch_proposals(self, flat, T, data=None, window_ext=None):
@@ -550,8 +592,9 @@ class GroundingEvaluator:
         ``loss_meter``: a ``DeviceLossMeter`` of the bank the videos come from; on the device route, in each of the three modes, every
         video's forward is followed by ``loss_meter.update_device`` beside the counting.  The host route refuses it (ValueError:
         ``calc_loss`` per video is the host's validation loss)."""
-        if self.expert == 'selected' and batch_videos > 1:
-            raise NotImplementedError("expert='selected' runs one video per forward: run(batch_videos=1)")
+        if self.expert == 'selected' and batch_videos > 1 and not self.select_videos:
+            raise NotImplementedError("expert='selected' runs one video per forward: run(batch_videos=1), or make the evaluator with "
+                                      "select_videos=True")
         if loss_meter is not None and not isinstance(counter, DeviceRecallCounter):
             raise ValueError('run(loss_meter=...): the meter fills its table on the device route, run(counter=DeviceRecallCounter(...)); '
                              'calc_loss per video is the host route')
@@ -593,7 +636,7 @@ class GroundingEvaluator:
                 if not pending:
                     return
                 T = pending[0][2]
-                self.model.forward_videos([p[1] for p in pending])
+                self._forward_group(pending)
                 logits, offsets, masks = self.model._last_flat
                 q = 0
                 for data, args, _, ext in pending:
@@ -660,7 +703,7 @@ class GroundingEvaluator:
                 t0 = time.perf_counter()
 
                 def compute():
-                    self.model.forward_videos([p[1] for p in pending])
+                    self._forward_group(pending)
                     logits, offsets, masks = self.model._last_flat
                     q, out = 0, []
                     for data, args, _, ext in pending:

@@ -484,6 +484,48 @@ class Selection:
         return self._host
 
 
+class SelectionBatch:
+    """What ``model.select_clips_videos`` returns: the needed clips of every video of one forward.
+
+    On the device, as ``forward_videos_selected`` takes them: ``gate`` (NQ, T) fp32 0 / 1 for the flat query list in video order,
+    ``pos`` (nvid, T) int32 video-local, ``clips`` (nvid, T) int32 (row v: the first ``counts[v]`` entries, ascending), and ``scores``
+    (NQ, T) fp32 for a ``scat`` model, None otherwise.  On the host, from the ONE device-to-host read of the pattern: ``counts`` and
+    ``row_first`` (nvid + 1: where video v's rows start among the packed rows) as lists of ints; ``nqs`` the query counts."""
+
+    def __init__(self, gate, pos, clips, scores, counts, nqs):
+        self.gate, self.pos, self.clips, self.scores = gate, pos, clips, scores
+        self.counts, self.nqs = [int(c) for c in counts], [int(n) for n in nqs]
+        self.row_first = [0]
+        for c in self.counts:
+            self.row_first.append(self.row_first[-1] + c)
+        self.q_first = [0]
+        for n in self.nqs:
+            self.q_first.append(self.q_first[-1] + n)
+        self._host = {}
+
+    @property
+    def T(self):
+        return self.gate.size(1)
+
+    @property
+    def nvid(self):
+        return len(self.counts)
+
+    @property
+    def n_rows(self):
+        return self.row_first[-1]
+
+    def selection(self, v):
+        """video ``v`` as the ``Selection`` that ``forward_selected`` / ``gather_clip_rows`` take (views, no copy)"""
+        return Selection(self.gate[self.q_first[v]:self.q_first[v + 1]], self.pos[v], self.clips[v], self.counts[v])
+
+    def clips_host(self, v):
+        """video ``v``'s needed clips as a CPU int64 tensor, ascending (the lists of all videos come over in one copy, once)"""
+        if 'all' not in self._host:
+            self._host['all'] = self.clips[:, :max(self.counts + [1])].cpu()
+        return self._host['all'][v, :self.counts[v]].long()
+
+
 class PtTransformerEarlyFusionIterative(nn.Module):
     """Drop-in for libs/modeling/model.py:397-565 (created by libs/worker_v2.py:182-211).
 
@@ -1022,6 +1064,176 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         of = [tuple(x.unsqueeze(0) for x in offsets[q].split(sizes)) for q in range(nq)]
         mk = [tuple(x.unsqueeze(0) for x in masks[q].split(sizes)) for q in range(nq)]
         return lg, of, mk
+
+    # -- selected-clip inference on several videos per forward (include/decafnet_hip_select_videos.h) ------------------------------
+    def _selected_videos_refusals(self, what, nvid, lengths):
+        if self.sfonly and self.MODEL_KIND == 0:
+            raise NotImplementedError(f'{what}: opt.model.sfonly reads no expert features: there is nothing to select')
+        if self.vid_net.stride != 1:
+            raise NotImplementedError(f'{what}: vid_net.stride = {self.vid_net.stride}: the externally gated forward takes vid_net.stride = 1')
+        if not 1 <= nvid <= 16:
+            raise ValueError(f'{what}: 1 .. 16 videos per forward (got {nvid})')
+        if len(set(lengths)) != 1:
+            raise ValueError(f'{what}: the videos of one call share the padded length T (got {sorted(set(lengths))})')
+
+    def select_clips_videos(self, videos):
+        """First call of the pattern for all videos of a forward: which clips does the model need expert features for?
+
+        ``videos`` as ``forward_videos`` takes them -- ``(vid, shallow_vid (1, D, T), vid_masks (1, T), text, text_cls (nq, D),
+        text_masks)`` per video; ``vid`` is not read and may be None --, all of one padded length, all fp32 or all float16.  One
+        call (dcf_select_videos(_h): the scoring kernels over all videos, the gate, one compaction launch with a workgroup per video)
+        and ONE device-to-host read, of the videos' counts.  Returns a ``SelectionBatch``; a ``scat`` model's carries the scores."""
+        nv = len(videos)
+        self._selected_videos_refusals('select_clips_videos', nv, [video[1].size(-1) for video in videos])
+        if len({video[1].dtype == torch.float16 for video in videos}) != 1:
+            raise ValueError('select_clips_videos: the videos of one call are all float16 or none of them is')
+        if not videos[0][1].is_cuda:
+            raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
+        dev = videos[0][1].device
+        if self._engine is None:
+            self._engine = _Engine(self._config())
+        eng = self._engine
+        eng.bind(self)
+        lib = eng.lib
+        T = videos[0][1].size(-1)
+        half = self.half_features and videos[0][1].dtype == torch.float16
+        keep = []
+        sptr, mptr, cptr = ((ctypes.c_void_p * nv)() for _ in range(3))
+        nqs = (ctypes.c_int32 * nv)()
+        for v, video in enumerate(videos):
+            shallow, vmask, text_cls = video[1], video[2], video[4]
+            assert shallow.dim() == 3 and shallow.size(0) == 1, shallow.size()
+            sc = shallow[0].contiguous() if half else shallow[0].contiguous().float()
+            mc = vmask.reshape(-1).to(torch.bool).contiguous()
+            cc = text_cls.contiguous().float()
+            assert sc.shape == (self.D, T) and mc.numel() == T and cc.dim() == 2 and cc.size(1) == self.D and cc.size(0) >= 1
+            keep += [sc, mc, cc]
+            sptr[v], mptr[v], cptr[v], nqs[v] = sc.data_ptr(), mc.data_ptr(), cc.data_ptr(), cc.size(0)
+        NQ = sum(nqs)
+        gate = torch.empty(NQ, T, device=dev, dtype=torch.float32)
+        scores = torch.empty(NQ, T, device=dev, dtype=torch.float32) if self.scat else None
+        lists = torch.empty(2 * nv * T + nv, device=dev, dtype=torch.int32)          # clips, pos and counts: one allocation
+        clips, pos, counts = lists[:nv * T].view(nv, T), lists[nv * T:2 * nv * T].view(nv, T), lists[2 * nv * T:]
+        fn, what = (lib.dcf_select_videos_h, 'dcf_select_videos_h') if half else (lib.dcf_select_videos, 'dcf_select_videos')
+        _lib.check(fn(eng.handle, nv, sptr, mptr, T, nqs, cptr, _lib.ptr(gate), _lib.ptr(scores) if scores is not None else None,
+                      _lib.ptr(clips), _lib.ptr(pos), _lib.ptr(counts), _lib.current_stream()), what)
+        return SelectionBatch(gate, pos, clips, scores, counts.cpu().tolist(), list(nqs))
+
+    def gather_clip_rows_videos(self, vids, batch):
+        """The packed rows ``forward_videos_selected`` takes, made from dense features: ``vids`` a sequence of (1, D, T) tensors, all
+        fp32 or all float16 -> (batch.n_rows, D) of that type, video v's rows from ``batch.row_first[v]`` on
+        (dcf_op_gather_clip_rows_videos(_h): one launch).  The emulation path of callers that hold dense features."""
+        nv = len(vids)
+        if nv != batch.nvid:
+            raise ValueError(f'gather_clip_rows_videos: {nv} feature tensors for a selection of {batch.nvid} videos')
+        if len({x.dtype == torch.float16 for x in vids}) != 1:
+            raise ValueError('gather_clip_rows_videos: the videos of one call are all float16 or none of them is')
+        if not vids[0].is_cuda:
+            raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
+        lib = _lib.lib()
+        half = vids[0].dtype == torch.float16
+        keep, xptr = [], (ctypes.c_void_p * nv)()
+        for v, x in enumerate(vids):
+            assert x.dim() == 3 and x.size(0) == 1 and x.size(1) == self.D and x.size(2) == batch.T, (x.size(), batch.T)
+            xc = x[0].contiguous() if half else x[0].contiguous().float()
+            keep.append(xc)
+            xptr[v] = xc.data_ptr()
+        rows = torch.empty(batch.n_rows, self.D, device=vids[0].device, dtype=keep[0].dtype)
+        first = (ctypes.c_int32 * (nv + 1))(*batch.row_first)
+        fn, what = (lib.dcf_op_gather_clip_rows_videos_h, 'dcf_op_gather_clip_rows_videos_h') if half else \
+                   (lib.dcf_op_gather_clip_rows_videos, 'dcf_op_gather_clip_rows_videos')
+        _lib.check(fn(xptr, batch.T, _lib.ptr(batch.clips), batch.T, nv, first, self.D, _lib.ptr(rows), _lib.current_stream()), what)
+        self._last_gather = keep
+        return rows
+
+    def forward_videos_selected(self, vid_rows, batch, videos):
+        """Second call of the pattern: ONE eval forward of all videos on the packed expert features of their selected clips.
+
+        vid_rows: (batch.n_rows, D) fp32 or float16 on the GPU (more rows are allowed: a capacity buffer), video v's rows from
+        ``batch.row_first[v]`` on, row i of them = the expert features of clip ``batch.clips[v, i]``.  batch: what
+        ``select_clips_videos`` returned for these videos and queries.  videos: as there (``vid`` is not read).  Returns what
+        ``forward_videos`` returns.  A ``scat`` model is served: the batch carries the scores.  Always launched eagerly."""
+        nv = len(videos)
+        self._selected_videos_refusals('forward_videos_selected', nv, [video[1].size(-1) for video in videos])
+        if self.scat and getattr(batch, 'scores', None) is None:
+            raise ValueError('forward_videos_selected: opt.model.scat needs the sidekick scores: the selection carries none '
+                             '(batch.scores; select_clips_videos of a scat model fills them)')
+        if nv != batch.nvid or [len(v[3]) if isinstance(v[3], (tuple, list)) else 1 for v in videos] != batch.nqs:
+            raise ValueError(f'forward_videos_selected: the selection is for {batch.nvid} videos with {batch.nqs} queries, the call has '
+                             f'{nv} videos')
+        if vid_rows.dim() != 2 or vid_rows.size(1) != self.D or vid_rows.size(0) < batch.n_rows:
+            raise ValueError(f'forward_videos_selected: vid_rows is {tuple(vid_rows.shape)}, row_first {batch.row_first} needs '
+                             f'({batch.n_rows}, {self.D}): one row of D expert features per selected clip')
+        if min(batch.counts) < 1:
+            raise ValueError(f'forward_videos_selected: a video of the selection is empty (counts {batch.counts})')
+        for video in videos:
+            _check_feature_dtypes(vid_rows, video[1])
+        if not vid_rows.is_cuda:
+            raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
+        dev = vid_rows.device
+        T = videos[0][1].size(-1)
+        if batch.T != T:
+            raise ValueError(f'forward_videos_selected: the selection is on {batch.T} clips, the call has {T}')
+        if self._engine is None:
+            self._engine = _Engine(self._config())
+        self._raise_if_flagged()
+        eng = self._engine
+        eng.bind(self)
+        lib = eng.lib
+        half = self.half_features and vid_rows.dtype == torch.float16
+        rows_c = vid_rows.contiguous() if half else vid_rows.contiguous().float()
+        keep = [rows_c]
+        sptr, mptr_v = (ctypes.c_void_p * nv)(), (ctypes.c_void_p * nv)()
+        nqs = (ctypes.c_int32 * nv)(*batch.nqs)
+        flat_text, flat_masks = [], []
+        for v, video in enumerate(videos):
+            shallow, vmask, text, tmasks = video[1], video[2], video[3], video[5]
+            sc = shallow[0].contiguous() if half else shallow[0].contiguous().float()
+            mc = vmask.reshape(-1).to(torch.bool).contiguous()
+            if not isinstance(text, (tuple, list)):
+                text, tmasks = (text,), (tmasks,)
+            assert sc.shape == (self.D, T) and mc.numel() == T
+            keep += [sc, mc]
+            sptr[v], mptr_v[v] = sc.data_ptr(), mc.data_ptr()
+            flat_text += list(text)
+            flat_masks += list(tmasks)
+        nq = len(flat_text)
+        tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
+        for q in range(nq):
+            t = flat_text[q][0].contiguous().float()
+            m = flat_masks[q].reshape(-1).to(torch.bool).contiguous()
+            assert t.dim() == 2 and m.numel() == t.size(1)
+            keep += [t, m]
+            tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
+        gate_c, pos_c = batch.gate.contiguous().float(), batch.pos.contiguous()
+        scores_c = batch.scores.contiguous().float() if self.scat else None
+        assert gate_c.shape == (nq, T) and pos_c.shape == (nv, T) and pos_c.dtype == torch.int32
+        pe = None
+        if self.vid_net.use_abs_pe:
+            pe = self._position_encoding(T, dev)
+            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), T), 'dcf_model_set_pe')
+        S = lib.dcf_points_per_query(eng.handle, T)
+        logits = torch.empty(nq, S, device=dev, dtype=torch.float32)
+        offsets = torch.empty(nq, S, 2, device=dev, dtype=torch.float32)
+        masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
+        first = (ctypes.c_int32 * (nv + 1))(*batch.row_first)
+        fn, what = (lib.dcf_forward_eval_videos_selected_h, 'dcf_forward_eval_videos_selected_h') if half else \
+                   (lib.dcf_forward_eval_videos_selected, 'dcf_forward_eval_videos_selected')
+        _lib.check(fn(eng.handle, nv, _lib.ptr(rows_c), first, _lib.ptr(pos_c), sptr, mptr_v, T, nqs, tptr, mptr, tlen, _lib.ptr(gate_c),
+                      _lib.ptr(scores_c) if scores_c is not None else None, _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks),
+                      _lib.current_stream()), what)
+        self.last_feature_dtype = torch.float16 if half else torch.float32
+        self._last_inputs = (keep, gate_c, pos_c, scores_c, pe)
+        self._last_flat = (logits, offsets, masks)
+        self._probe_numerics()
+        sizes = [T >> l for l in range(self.vid_net.arch[2])]
+        out, q = [], 0
+        for n in batch.nqs:
+            out.append(([tuple(x.unsqueeze(0) for x in logits[i].split(sizes)) for i in range(q, q + n)],
+                        [tuple(x.unsqueeze(0) for x in offsets[i].split(sizes)) for i in range(q, q + n)],
+                        [tuple(x.unsqueeze(0) for x in masks[i].split(sizes)) for i in range(q, q + n)]))
+            q += n
+        return out
 
     # -- one long video cut at pyramid level k (dist.hybrid_forward; dcf_hybrid_phase1 / 2 / 3) --------------------------------
     def hybrid_phase1(self, vid_w, shallow_w, mask_w, text, text_masks, gate_w, k, Tc, pe_tokens=None):
