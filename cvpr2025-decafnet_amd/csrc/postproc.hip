@@ -19,9 +19,11 @@ namespace dcf {
 constexpr int NT = 1024;          // threads per workgroup
 constexpr int NW = NT / 64;
 
-// order-preserving map float -> uint32 (larger float => larger key), total order incl. negatives
+// order-preserving map float -> uint32 (larger float => larger key), total order incl. negatives; -0 counted as +0, as the reference's
+// comparisons do (equal scores then fall back to index order)
 __device__ __forceinline__ uint32_t fkey(float f) {
   uint32_t u = __float_as_uint(f);
+  u = f == 0.f ? 0u : u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

@@ -10,7 +10,13 @@
   queries of a video at once.
 
 Ties between equal scores are broken by the lower index (the reference leaves them to
-at::sort / argsort, which is unspecified).
+at::sort / argsort, which is unspecified); -0.0 and +0.0 are equal scores.
+
+Scores must not be NaN (``nms``, ``softnms``, ``nms_device``, ``softnms_device``, ``voting_device``,
+``batched_nms``, ``batched_nms_queries``): the kernels order candidates by an integer image of
+the score in which a NaN has no defined place, as it has none in the reference's sort.
+``collect_segments`` never emits one (it keeps ``score > pre_nms_thresh`` only, which a NaN
+fails), so its output can be handed on as it is.
 """
 from __future__ import annotations
 

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import forward_parity
 from conftest import Golden, ROOT, load_pkg
 
 sys.path.insert(0, ROOT)
@@ -1061,7 +1062,7 @@ def test_nms_fuzz_vs_oracle(L):
 def test_softnms_ties_and_pruning_fuzz_vs_oracle(L):
     """Quantised scores and segments: decayed scores tie again and again, and fall below min_score one at a time or several at once --
     the order of the picks then hangs on the positions the reference's swap-with-last pruning (nms_cpu.cpp:157-165) leaves behind, which
-    both pruning paths of k_softnms (one dead segment: the move alone; several: the scans) have to reproduce."""
+    the pruning pass of k_softnms (one pass of scans, for one dead segment or for several) has to reproduce."""
     pkg, lib = L
     nms = pkg.nms
     g = torch.Generator().manual_seed(99)
@@ -1145,6 +1146,47 @@ def test_batched_nms_over_queries_without_host_sync(L):
             assert kk == len(wc), (cfg, q, kk, len(wc))
             torch.testing.assert_close(c[q, :kk].cpu(), wc, rtol=0, atol=0)
             torch.testing.assert_close(s[q, :kk].cpu(), ws, rtol=1e-6, atol=1e-6)
+    # ... and against the CPU oracle's batched_nms query by query (the comparison above runs the same kernels on both sides): scores
+    # exact, voted segments by the parity rule of the voting kernel (tests/test_gpu_postproc_batched.py) against the oracle's voting in
+    # fp64 on the oracle's own picks; mode=None; fewer candidates than max_num_segs (K = 3 < 5); K = 4100 (the global-scratch kernels)
+    cases = [(segs, scores, counts, cfg) for cfg in (
+        dict(iou_thresh=0.1, min_score=0.001, max_num_segs=5, mode='soft_nms', sigma=0.9, voting_thresh=0.95),
+        dict(iou_thresh=0.5, min_score=0.3, max_num_segs=7, mode='nms', sigma=0.5, voting_thresh=0.0),
+        dict(iou_thresh=0.4, min_score=0.0, max_num_segs=4, mode='nms', sigma=0.5, voting_thresh=0.75),
+        dict(iou_thresh=0.3, min_score=0.05, max_num_segs=6, mode='soft_nms', sigma=0.4, voting_thresh=0.0),
+        dict(iou_thresh=0.3, min_score=0.05, max_num_segs=6, mode=None, sigma=0.4, voting_thresh=0.75))]
+    for mode, vt in (('soft_nms', 0.75), ('nms', 0.75), (None, 0.0)):
+        cases.append((segs[:3, :3].contiguous(), scores[:3, :3].contiguous(), torch.tensor([3, 2, 0], dtype=torch.int32),
+                      dict(iou_thresh=0.3, min_score=0.001, max_num_segs=5, mode=mode, sigma=0.5, voting_thresh=vt)))
+    Kb = 4100
+    ctr = torch.rand(2, Kb, generator=gen) * 900
+    ln = torch.rand(2, Kb, generator=gen) * 40 + 0.2
+    big_segs = torch.stack((ctr - ln / 2, ctr + ln / 2), -1).contiguous()
+    big_scores = torch.rand(2, Kb, generator=gen).sort(1, descending=True)[0].contiguous()
+    for mode in ('soft_nms', 'nms'):
+        cases.append((big_segs, big_scores, torch.tensor([Kb, 4097], dtype=torch.int32),
+                      dict(iou_thresh=0.4, min_score=0.001, max_num_segs=9, mode=mode, sigma=0.6, voting_thresh=0.75)))
+    voted = [[], [], []]                                                  # got, fp64, fp32: pooled over every voted case
+    for sg, sc, cn, cfg in cases:
+        s, c, kc = pkg.nms.batched_nms_queries(sg.cuda(), sc.cuda(), cn.cuda(), **cfg)
+        assert s.shape == (len(cn), cfg['max_num_segs'], 2) and c.shape == (len(cn), cfg['max_num_segs'])
+        for q in range(len(cn)):
+            m = int(cn[q])
+            ws, wc = R.batched_nms(sg[q, :m].clone(), sc[q, :m].clone(), **cfg)
+            kk = int(kc[q])
+            assert kk == len(wc), (cfg, q, kk, len(wc))
+            assert torch.equal(c[q, :kk].cpu(), wc), (cfg, q)
+            if cfg['mode'] is None or cfg['voting_thresh'] <= 0:
+                assert torch.equal(s[q, :kk].cpu(), ws), (cfg, q)
+            elif kk:
+                picks, pick_scores = R.batched_nms(sg[q, :m].clone(), sc[q, :m].clone(), **dict(cfg, voting_thresh=0.0))
+                assert torch.equal(pick_scores, wc)
+                y64 = R.segment_voting(picks.double(), sg[q, :m].double(), sc[q, :m].double(), cfg['voting_thresh'])
+                assert y64.dtype == torch.float64 and not torch.isnan(y64).any()
+                voted[0].append(s[q, :kk].cpu()); voted[1].append(y64); voted[2].append(ws)
+    top, e_ref, e_gpu, bound, ratio = forward_parity.rule(torch.cat(voted[0]), torch.cat(voted[1]), torch.cat(voted[2]))
+    print(f'VOTEERR batched_nms_queries: max|y64| {top:.3e} e_ref {e_ref:.3e} e_gpu {e_gpu:.3e} bound {bound:.3e} ratio {ratio:.3f}')
+    assert e_gpu <= bound, (e_gpu, bound)
 
 
 def test_collect_multi_query_vs_oracle(L):
