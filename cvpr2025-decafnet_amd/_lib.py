@@ -398,6 +398,28 @@ SELECT_VIDEOS = (
 )
 
 
+# selected-clip training (include/decafnet_hip_front_select.h, csrc/front_select.hip): vid_map of the training step and its weight
+# gradient on the packed expert rows of the selected clips.  ``row_first`` and ``nq`` are HOST arrays of int32; ``pos`` is int32 in
+# device memory; the ``_h`` forms take ``rows`` / ``shallow`` as the device address of IEEE binary16 values.
+_FS_FWD = [c_i32p, c_i32p, vp, c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_i32p, c_f32p, i32, i32, i32, i32, vp]
+_FS_BWD = [c_i32p, c_i32p, vp, c_f32p, c_u8p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, i32, vp]
+FRONT_SELECT_TABLE = {
+    'dcf_front_select_ext_version': (i32, []),
+    'dcf_op_vidmap_selected': (i32, [c_f32p] + _FS_FWD),
+    'dcf_op_vidmap_selected_bwd': (i32, [c_f32p] + _FS_BWD),
+    'dcf_op_vidmap_selected_h': (i32, [c_f16p] + _FS_FWD),
+    'dcf_op_vidmap_selected_bwd_h': (i32, [c_f16p] + _FS_BWD),
+}
+
+
+# Bound by lib() after SELECT_VIDEOS, and waiting for the same follow-up (the cases are tests/front_select_abi_cases.py, run through
+# the border driver by tests/test_gpu_front_select_borders.py).
+FRONT_SELECT = (
+    Extension('front_select', 'decafnet_hip_front_select.h', 'dcf_front_select_ext_version', 1, 'DCF_FRONT_SELECT_EXT_VERSION',
+              ('decafnet_hip.h',), FRONT_SELECT_TABLE),
+)
+
+
 def lib():
     """Load (once) and return the ctypes handle.  torch is imported first so that the HIP runtime
     already mapped by PyTorch-ROCm (same soname, libamdhip64.so.7) is the one this library binds to."""
@@ -409,11 +431,11 @@ def lib():
                                f'(there is no CPU fallback for the grounding path)')
         h = ctypes.CDLL(SO_PATH, mode=ctypes.RTLD_GLOBAL)
         bound = set()
-        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG + ATTN_DROP + SELECT + SELECT_VIDEOS:
+        for ext in EXTENSIONS + PENDING + STAGED + FIT + STEPLOG + ATTN_DROP + SELECT + SELECT_VIDEOS + FRONT_SELECT:
             for name, (res, args) in ext.table.items():
                 if name in bound:
                     raise RuntimeError(f'{name} is in two signature tables of _lib.EXTENSIONS / _lib.PENDING / _lib.STAGED / _lib.FIT / '
-                                       f'_lib.STEPLOG / _lib.ATTN_DROP / _lib.SELECT / _lib.SELECT_VIDEOS')
+                                       f'_lib.STEPLOG / _lib.ATTN_DROP / _lib.SELECT / _lib.SELECT_VIDEOS / _lib.FRONT_SELECT')
                 bound.add(name)
                 fn = getattr(h, name)
                 fn.restype = res

@@ -60,7 +60,11 @@ dcf_op_vidmap_shared / dcf_op_vidmap_shared_bwd (csrc/front_grad.hip, include/de
 ``W[:, D:2D] . shallow`` once per video, skip the 64-clip tiles that no query's gate keeps, combine them per query row, and form the
 weight gradient from per-video row sums of the upstream gradient against the channel-major features; the raw-score channel of
 ``opt.model.scat`` is a rank-1 term.  It saves only its inputs and meets the same rule against the same reference
-(tests/test_gpu_front_grad.py); ``train.training_forward(front_end='shared')`` composes the step with it.
+(tests/test_gpu_front_grad.py); ``train.training_forward(front_end='shared')`` composes the step with it.  ``selected_vid_map`` is its
+counterpart on the expert features of the selected clips alone: packed (n_rows, D) rows with ``row_first`` and ``pos`` as
+``model.select_clips_videos`` returns them (dcf_op_vidmap_selected / dcf_op_vidmap_selected_bwd, csrc/front_select.hip,
+include/decafnet_hip_front_select.h); its backward saves the rows as stored and no dense expert tensor
+(tests/test_gpu_front_select.py); ``train.training_forward(expert='selected')`` composes the step with it.
 
 Without a backward yet: the gate (it has no parameters: its inputs are features the caller supplies, so it does not stand between these
 functions and a training step), TextIdentity's attention pool (``text_transformer`` refuses a TextIdentity), cross-attention over more
@@ -409,6 +413,92 @@ def gated_vid_map(vid, shallow, gate, mask, correl, text_size, weight, bias, ski
     m = (m if m.dtype == torch.bool else m != 0).contiguous()
     x = (lambda z: None if z is None else z.detach().contiguous()) if vid.dtype == torch.float16 else f      # float16: as stored
     return _GatedVidMapFn.apply(x(vid), x(shallow), f(gate), m, f(correl), sizes, weight, bias, bool(skip))
+
+
+class _SelectedVidMapFn(torch.autograd.Function):
+    """dcf_op_vidmap_selected / dcf_op_vidmap_selected_bwd (csrc/front_select.hip), or their ``_h`` forms on float16 features
+    (include/decafnet_hip_front_select.h).  Saves its inputs -- the packed rows as they are stored -- and no dense expert tensor."""
+
+    @staticmethod
+    def forward(ctx, rows, row_first, pos, shallow, gate, mask, correl, sizes, weight, bias):
+        nvid, T = pos.shape
+        D, E = rows.size(1), weight.size(0)
+        y = torch.empty(sum(sizes), T, E, dtype=torch.float32, device=rows.device)
+        host_first, host_nq = torch.tensor(row_first, dtype=torch.int32), torch.tensor(sizes, dtype=torch.int32)
+        w, b = weight.detach().float().reshape(E, -1).contiguous(), bias.detach().float().contiguous()
+        name = 'dcf_op_vidmap_selected_h' if rows.dtype == torch.float16 else 'dcf_op_vidmap_selected'
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(rows), _lib.ptr(host_first), _lib.ptr(pos), _lib.ptr(shallow), _lib.ptr(w), _lib.ptr(b),
+                                             _lib.ptr(gate), _lib.ptr(mask), _lib.ptr(correl), _lib.ptr(host_nq), _lib.ptr(y), nvid, D, T, E,
+                                             _lib.current_stream()), name)
+        ctx.save_for_backward(rows, pos, gate, mask, *(z for z in (shallow, correl) if z is not None))
+        ctx.msf, ctx.scat, ctx.sizes, ctx.row_first, ctx.wshape = shallow is not None, correl is not None, sizes, row_first, tuple(weight.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        rows, pos, gate, mask, *rest = ctx.saved_tensors
+        shallow = rest.pop(0) if ctx.msf else None
+        correl = rest.pop(0) if ctx.scat else None
+        nvid, T = pos.shape
+        D, E = rows.size(1), ctx.wshape[0]
+        want_w, want_b = ctx.needs_input_grad[8], ctx.needs_input_grad[9]
+        if not (want_w or want_b):
+            return (None,) * 10
+        # a bias whose weight is frozen still takes its sum from the same call: the same bits whether or not the weight asks
+        gy = gy.float().contiguous()
+        gw = torch.empty(ctx.wshape, dtype=torch.float32, device=rows.device)
+        gb = torch.empty(E, dtype=torch.float32, device=rows.device) if want_b else None
+        host_first, host_nq = torch.tensor(ctx.row_first, dtype=torch.int32), torch.tensor(ctx.sizes, dtype=torch.int32)
+        name = 'dcf_op_vidmap_selected_bwd_h' if rows.dtype == torch.float16 else 'dcf_op_vidmap_selected_bwd'
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(rows), _lib.ptr(host_first), _lib.ptr(pos), _lib.ptr(shallow), _lib.ptr(gate),
+                                             _lib.ptr(mask), _lib.ptr(correl), _lib.ptr(host_nq), _lib.ptr(gy), _lib.ptr(gw), _lib.ptr(gb), nvid,
+                                             D, T, E, 0, _lib.current_stream()), name)
+        return None, None, None, None, None, None, None, None, (gw if want_w else None), gb
+
+
+def selected_vid_map(rows, row_first, pos, shallow, gate, mask, correl, text_size, weight, bias):
+    """``gated_vid_map`` on the expert features of the selected clips alone: ``rows`` (>= row_first[-1], D) clip-major and packed, video
+    v's rows from ``row_first[v]`` on (more rows are allowed: a capacity buffer that is never read); ``row_first`` nvid + 1 ints on the
+    host, strictly increasing from 0; ``pos`` (nvid, T) int32 video-local as ``model.select_clips_videos`` returns it (-1: the clip has
+    no expert half, whatever its gate says: documented, not detected).  ``shallow`` (nvid, D, T) channel-major or None, ``gate`` /
+    ``mask`` / ``correl`` (B', T), ``text_size``, ``weight`` (E, Cin, 1) and ``bias`` as ``gated_vid_map`` takes them -> (B', T, E).
+    With ``pos`` a bijection between the clips some query of a video keeps and its rows, the result and the gradients of the weight
+    and the bias are those of ``gated_vid_map`` on the dense features up to the summation order of the expert half
+    (include/decafnet_hip_front_select.h).  The backward saves ``rows`` as stored, plus its other inputs: no dense expert tensor.
+    ``rows`` / ``shallow`` may be ``torch.float16``, both or neither; at most 16 videos per call."""
+    for name, z in (('rows', rows), ('shallow', shallow), ('gate', gate), ('correl', correl)):
+        if z is not None and z.requires_grad:
+            raise ValueError(f'selected_vid_map: `{name}` requires a gradient; the features, the gate and the scores are data (no gradient reaches them)')
+    if torch.is_tensor(rows) and torch.is_tensor(shallow):
+        from .modeling import _check_feature_dtypes
+        _check_feature_dtypes(rows, shallow)
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dim() == 2):
+        raise RuntimeError('selected_vid_map: (n_rows, D) expert rows on the GPU are required (there is no CPU path)')
+    if not (torch.is_tensor(pos) and pos.dim() == 2 and pos.dtype == torch.int32 and pos.is_cuda):
+        raise ValueError('selected_vid_map: pos is a (nvid, T) int32 tensor on the GPU')
+    nvid, T = pos.shape
+    D = rows.size(1)
+    first = tuple(int(k) for k in row_first)
+    sizes = tuple([1] * nvid if text_size is None else [int(k) for k in text_size])
+    nq = sum(sizes)
+    cin = D * (2 if shallow is not None else 1) + (1 if correl is not None else 0)
+    if len(sizes) != nvid or min(sizes) < 1:
+        raise ValueError(f'selected_vid_map: text_size {list(sizes)} does not match {nvid} videos (one entry >= 1 per video)')
+    if len(first) != nvid + 1 or first[0] != 0 or any(not 0 < b - a <= T for a, b in zip(first, first[1:])) or rows.size(0) < first[-1]:
+        raise ValueError(f'selected_vid_map: row_first {list(first)} for {nvid} videos and {rows.size(0)} rows (nvid + 1 entries, strictly '
+                         f'increasing from 0, at most T = {T} rows per video, within rows)')
+    if weight.dim() != 3 or weight.size(1) != cin or weight.size(2) != 1 or bias is None or tuple(bias.shape) != (weight.size(0),):
+        raise ValueError(f'selected_vid_map: weight {tuple(weight.shape)} / bias on {cin} input channels (k = 1, with bias)')
+    if shallow is not None and tuple(shallow.shape) != (nvid, D, T):
+        raise ValueError(f'selected_vid_map: shallow {tuple(shallow.shape)} against {(nvid, D, T)}')
+    for name, z in (('gate', gate), ('mask', mask), ('correl', correl)):
+        if z is not None and tuple(z.shape) != (nq, T):
+            raise ValueError(f'selected_vid_map: {name} {tuple(z.shape)} is not ({nq}, {T})')
+    f = lambda z: None if z is None else z.detach().float().contiguous()
+    m = mask.detach()
+    m = (m if m.dtype == torch.bool else m != 0).contiguous()
+    x = (lambda z: None if z is None else z.detach().contiguous()) if rows.dtype == torch.float16 else f      # float16: as stored
+    return _SelectedVidMapFn.apply(x(rows), first, pos.detach().contiguous(), x(shallow), f(gate), m, f(correl), sizes, weight, bias)
 
 
 def strided_masked_conv1d(x, mask, weight):

@@ -5,7 +5,7 @@
 
 One translation unit per kernel family, compiled in parallel, linked into a single shared
 object that exports the C ABI of include/decafnet_hip.h and of its extensions,
-include/decafnet_hip_train.h, include/decafnet_hip_dist.h, include/decafnet_hip_attn.h, include/decafnet_hip_front.h, include/decafnet_hip_guard.h, include/decafnet_hip_clock.h, include/decafnet_hip_half.h, include/decafnet_hip_front_half.h, include/decafnet_hip_embd.h, include/decafnet_hip_batch.h, include/decafnet_hip_eval.h, include/decafnet_hip_fit.h, include/decafnet_hip_steplog.h, include/decafnet_hip_attn_drop.h, include/decafnet_hip_select.h and include/decafnet_hip_select_videos.h.  The .so stays in the source tree
+include/decafnet_hip_train.h, include/decafnet_hip_dist.h, include/decafnet_hip_attn.h, include/decafnet_hip_front.h, include/decafnet_hip_guard.h, include/decafnet_hip_clock.h, include/decafnet_hip_half.h, include/decafnet_hip_front_half.h, include/decafnet_hip_embd.h, include/decafnet_hip_batch.h, include/decafnet_hip_eval.h, include/decafnet_hip_fit.h, include/decafnet_hip_steplog.h, include/decafnet_hip_attn_drop.h, include/decafnet_hip_select.h, include/decafnet_hip_select_videos.h and include/decafnet_hip_front_select.h.  The .so stays in the source tree
 (git-ignored) so that it travels with the working copy to the GPU machine.
 """
 import os
@@ -17,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libdecafnet_hip.so')
-SOURCES = ['engine.hip', 'engine_model.hip', 'engine_blocks.hip', 'engine_hybrid.hip', 'ops_api.hip', 'half.hip', 'dropout.hip', 'gemm.hip', 'gemm_bf16s.hip', 'ffn_chain.hip', 'head_chain.hip', 'dec_chain.hip', 'enc_chain.hip', 'rowops.hip', 'attn.hip', 'attn_grad.hip', 'global_attn_grad.hip', 'score.hip', 'heads.hip', 'postproc.hip', 'loss.hip', 'objective.hip', 'conv_grad.hip', 'enc_grad.hip', 'xattn_grad.hip', 'refine_grad.hip', 'drop_grad.hip', 'front_grad.hip', 'optim.hip', 'optim_guard.hip', 'optim_clock.hip', 'grad_bucket.hip', 'batch.hip', 'eval_metric.hip', 'fit.hip', 'steplog.hip', 'attn_drop.hip', 'calib.hip', 'select_videos.hip', 'select.hip']
+SOURCES = ['engine.hip', 'engine_model.hip', 'engine_blocks.hip', 'engine_hybrid.hip', 'ops_api.hip', 'half.hip', 'dropout.hip', 'gemm.hip', 'gemm_bf16s.hip', 'ffn_chain.hip', 'head_chain.hip', 'dec_chain.hip', 'enc_chain.hip', 'rowops.hip', 'attn.hip', 'attn_grad.hip', 'global_attn_grad.hip', 'score.hip', 'heads.hip', 'postproc.hip', 'loss.hip', 'objective.hip', 'conv_grad.hip', 'enc_grad.hip', 'xattn_grad.hip', 'refine_grad.hip', 'drop_grad.hip', 'front_grad.hip', 'front_select.hip', 'optim.hip', 'optim_guard.hip', 'optim_clock.hip', 'grad_bucket.hip', 'batch.hip', 'eval_metric.hip', 'fit.hip', 'steplog.hip', 'attn_drop.hip', 'calib.hip', 'select_videos.hip', 'select.hip']
 ARCH = 'gfx950'
 FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
 

@@ -23,4 +23,14 @@ struct FrontWgradArgs {
 // half: X holds binary16 values (any alignment), read as stored: one X plane and two products per k-step instead of two and three
 int launch_front_wgrad(const FrontWgradArgs& a, int pairs, hipStream_t st, bool half = false);
 
+// The pieces the selected-clip form of the operators (front_select.hip) shares with front_grad.hip.
+// qoff[v] = first row of video v (qoff[nvid] = B'), vtab[q] = video of row q; nq is a host array, read before the call returns
+int launch_front_qtables(int nvid, const int32_t* nq, int* qoff, int* vtab, hipStream_t st);
+// the column groups of W (E, Cin) as compact matrices W1c / W2c (E, D) and w3c (E); a null destination is not written
+int launch_front_unpack_w(const float* W, int Cin, int D, int E, float* W1c, float* W2c, float* w3c, hipStream_t st);
+// k_fg_reduce: out[(i / rowlen) pitch + i % rowlen] (+)= extra * inv_scale(absmax) * sum_s part[s stride + i], i < count, the parts in
+// the blocked order of grad_common.h; a non-finite value raises bit 0 of *status
+int launch_front_reduce(const float* part, int nparts, int64_t stride, int count, int rowlen, int pitch, const unsigned* absmax, float extra,
+                        float* out, int accumulate, unsigned* status, hipStream_t st);
+
 }  // namespace dcf

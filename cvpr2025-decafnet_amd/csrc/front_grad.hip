@@ -319,14 +319,34 @@ static int front_check(const char* what, const void* vid, const float* gate, con
 
 // the device tables of the call: qoff (nvid + 1), vtab (B'), tile flags (nvid, ntiles)
 static int front_tables(const FrontShape& s, const int32_t* nq, const float* gate, int noskip, int* qoff, int* vtab, uint8_t* flags, hipStream_t st) {
+  if (launch_front_qtables(s.nvid, nq, qoff, vtab, st)) return -1;
+  hipLaunchKernelGGL(k_fg_tileflags, dim3(s.ntiles, s.nvid), dim3(64), 0, st, gate, qoff, flags, s.T, s.ntiles, noskip);
+  DCF_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_front_qtables(int nvid, const int32_t* nq, int* qoff, int* vtab, hipStream_t st) {
   int q0 = 0;
-  for (int v0 = 0; v0 < s.nvid; v0 += FG_NQ_CHUNK) {
+  for (int v0 = 0; v0 < nvid; v0 += FG_NQ_CHUNK) {
     FrontNq c{};
-    c.v0 = v0; c.q0 = q0; c.n = s.nvid - v0 < FG_NQ_CHUNK ? s.nvid - v0 : FG_NQ_CHUNK;
+    c.v0 = v0; c.q0 = q0; c.n = nvid - v0 < FG_NQ_CHUNK ? nvid - v0 : FG_NQ_CHUNK;
     for (int i = 0; i < c.n; ++i) { c.nq[i] = nq[v0 + i]; q0 += nq[v0 + i]; }
     hipLaunchKernelGGL(k_fg_tables, dim3(1), dim3(64), 0, st, c, qoff, vtab);
   }
-  hipLaunchKernelGGL(k_fg_tileflags, dim3(s.ntiles, s.nvid), dim3(64), 0, st, gate, qoff, flags, s.T, s.ntiles, noskip);
+  DCF_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_front_unpack_w(const float* W, int Cin, int D, int E, float* W1c, float* W2c, float* w3c, hipStream_t st) {
+  hipLaunchKernelGGL(k_fg_unpack_w, dim3((E * D + 255) / 256), dim3(256), 0, st, W, Cin, D, E, W1c, W2c, w3c);
+  DCF_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_front_reduce(const float* part, int nparts, int64_t stride, int count, int rowlen, int pitch, const unsigned* absmax, float extra,
+                        float* out, int accumulate, unsigned* status, hipStream_t st) {
+  hipLaunchKernelGGL(k_fg_reduce, dim3((count + 255) / 256), dim3(256), 0, st, part, nparts, stride, count, rowlen, pitch, absmax, extra, out,
+                     accumulate, status);
   DCF_HIP(hipGetLastError());
   return 0;
 }

@@ -86,11 +86,11 @@ int launch_vidmap_combine(const float* P1, const float* P2, const float* bias, c
                           const float* w3, const float* correl, float* X, int T, int rows, int E, unsigned long long vmap,
                           hipStream_t st, const int* vtab = nullptr);      // vtab: device table, video of batch element r / T (overrides vmap)
 // the same epilogue for videos whose expert products exist for the selected clips only: P1c [n][E], the rows of video v from first.r[v]
-// on, row first.r[v] + pos[v * T + t] where the gate of its clip t is open (pos < 0: no expert half); vmap as above
+// on, row first.r[v] + pos[v * T + t] where the gate of its clip t is open (pos < 0: no expert half); vmap / vtab as above
 struct SelFirst { int r[17]; };
 int launch_vidmap_combine_sel(const float* P1c, const int* pos, const SelFirst& first, const float* P2, const float* bias, const float* gate,
                               const uint8_t* mask, const float* w3, const float* correl, float* X, int T, int rows, int E,
-                              unsigned long long vmap, hipStream_t st);
+                              unsigned long long vmap, hipStream_t st, const int* vtab = nullptr);
 int launch_ln(const LnArgs& a, hipStream_t st);
 int launch_dec_pre(const DecPreArgs& a, hipStream_t st);
 int launch_dec_mid(const float* Xa, const float* H, const float* ln_w, const float* ln_b, float* Q3, float* Xn, int rows,

@@ -121,8 +121,8 @@ __global__ __launch_bounds__(256) void k_vidmap_combine_sel(const float* __restr
                                                              const uint8_t* __restrict__ mask, const int* __restrict__ pos,
                                                              const float* __restrict__ w3, const float* __restrict__ correl,
                                                              float* __restrict__ X, int T, int rows, int E,
-                                                             unsigned long long vmap, SelFirst first) {
-  vidmap_combine_row<NCH, true>(P1c, P2, bias, gate, mask, w3, correl, X, T, rows, E, vmap, nullptr, pos, &first);
+                                                             unsigned long long vmap, SelFirst first, const int* __restrict__ vtab) {
+  vidmap_combine_row<NCH, true>(P1c, P2, bias, gate, mask, w3, correl, X, T, rows, E, vmap, vtab, pos, &first);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -606,12 +606,12 @@ int launch_vidmap_combine(const float* P1, const float* P2, const float* bias, c
 
 int launch_vidmap_combine_sel(const float* P1c, const int* pos, const SelFirst& first, const float* P2, const float* bias, const float* gate,
                               const uint8_t* mask, const float* w3, const float* correl, float* X, int T, int rows, int E,
-                              unsigned long long vmap, hipStream_t st) {
+                              unsigned long long vmap, hipStream_t st, const int* vtab) {
   if (rows <= 0) return 0;
   DCF_CHECK(P1c && pos && (!w3 || correl), "launch_vidmap_combine_sel: null operand");
   ProfScope prof("vidmap_combine_sel", st, 3.0 * rows * E, 4.0 * 3.0 * rows * E);
   DISPATCH_NCH(E, hipLaunchKernelGGL((k_vidmap_combine_sel<NCH>), dim3((rows + 3) / 4), dim3(256), 0, st, P1c, P2, bias, gate, mask, pos,
-                                     w3, correl, X, T, rows, E, vmap, first));
+                                     w3, correl, X, T, rows, E, vmap, first, vtab));
   return 0;
 }
 

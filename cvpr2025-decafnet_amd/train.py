@@ -72,8 +72,17 @@ for bit against ``run_step``).  ``opt.model.scat`` (the raw sidekick score as in
 path alone, whatever ``front_end`` says: the score channel is a rank-1 term there.  ``sfonly`` stays refused (the reference's
 training branch, model.py:606-612, never reads it).  ``cdrop`` (with ``enable_dropout(sites='all')``) needs the dense front end and
 a model without ``scat``: a per-sample channel mask cannot share products, so the shared path raises ValueError.
+
+The expert features.  ``training_forward(..., expert='selected')`` / ``TrainStep(..., expert='selected', expert_fn=None)`` run ``vid_map``
+and its weight gradient on the expert features of the clips the top-k gates keep (``autograd.selected_vid_map``, csrc/front_select.hip,
+include/decafnet_hip_front_select.h): after the scores and the gates one compaction launch and ONE host read -- the videos' clip
+counts, which a caller with an online expert encoder needs anyway --, then ``expert_fn(b, clips)`` per video or a gather from the dense
+batch, then the op on packed (n_rows, D) rows.  No dense expert tensor is read by the op or saved for its backward.  'dense', the
+default, launches exactly what it launched before.  At most 16 videos per forward (more: micro-batches); ``cdrop`` and ``sfonly`` are
+refused.
 """
 import copy
+import ctypes
 import os
 from collections import namedtuple
 
@@ -83,10 +92,58 @@ from . import _lib, autograd as A, dist as D, loss as L, optim as O
 
 
 FRONT_ENDS = ('dense', 'shared')
+EXPERTS = ('dense', 'selected')
+MAX_SELECTED_VIDEOS = 16           # DCF_MAX_VIDEOS of the selected-clip extensions
+
+
+def _selected_front(model, vid, shallow, vid_masks, gate, mask, correl, sizes, half, expert_fn, selection, vid_rows):
+    """The front end of ``training_forward(expert='selected')`` behind the scores and the gates: the selection (one launch and ONE host
+    read, of the videos' counts), the packed expert rows, and ``autograd.selected_vid_map`` -> (vid_map (B', T, E), mask (B', T) bool)"""
+    from . import modeling
+    bs, D, T = shallow.shape
+    dev = shallow.device
+    if selection is None:                                           # dcf_op_select_clips_videos on the gates dcf_op_gate just wrote
+        vm = vid_masks.reshape(bs, T).to(torch.bool).contiguous()
+        lists = torch.empty(2 * bs * T + bs, device=dev, dtype=torch.int32)           # clips, pos and counts: one allocation
+        clips, pos, counts = lists[:bs * T].view(bs, T), lists[bs * T:2 * bs * T].view(bs, T), lists[2 * bs * T:]
+        nqs = torch.tensor(sizes, dtype=torch.int32)
+        _lib.check(_lib.lib().dcf_op_select_clips_videos(_lib.ptr(gate), _lib.ptr(vm), T, bs, ctypes.cast(nqs.data_ptr(), _lib._IP),
+                                                         _lib.ptr(clips), _lib.ptr(pos), _lib.ptr(counts), _lib.current_stream()),
+                   'dcf_op_select_clips_videos')
+        selection = modeling.SelectionBatch(gate, pos, clips, correl if model.scat else None, counts.cpu().tolist(), sizes)
+    else:                                                           # the caller's: its gate decides, the mask follows it as dcf_op_gate defines it
+        if selection.nvid != bs or list(selection.nqs) != list(sizes) or selection.T != T:
+            raise ValueError(f'training_forward: the selection is for {selection.nvid} videos with {selection.nqs} queries on '
+                             f'{selection.T} clips, the batch has {bs} videos with {list(sizes)} on {T}')
+        if model.scat and selection.scores is None:
+            raise ValueError('training_forward: opt.model.scat needs the sidekick scores: the selection carries none')
+        gate = selection.gate.float().contiguous()
+        mask = vid_masks.reshape(bs, T).to(torch.bool).repeat_interleave(torch.tensor(sizes, device=dev), dim=0)
+        if not model.msf:
+            mask = mask & (gate != 0)
+    if min(selection.counts) < 1:
+        raise ValueError(f'training_forward: a video of the selection is empty (counts {selection.counts}): no clip of it is valid')
+    if vid_rows is not None:
+        rows = vid_rows
+    elif expert_fn is not None:                                     # once per video, on the host's ascending clip list, packed
+        rows = torch.cat([expert_fn(b, selection.clips_host(b)) for b in range(bs)])
+    else:
+        rows = model.gather_clip_rows_videos([vid[b:b + 1] for b in range(bs)], selection)
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dim() == 2 and rows.size(1) == D and rows.size(0) >= selection.n_rows):
+        raise ValueError(f'training_forward: the expert rows are {tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__}, the '
+                         f'selection needs ({selection.n_rows}, {D}) on the GPU: one row of D expert features per selected clip')
+    if half and rows.dtype != torch.float16:
+        modeling._check_feature_dtypes(rows, shallow)
+    if not half:
+        rows = rows.float()
+    model.last_train_feature_dtype = torch.float16 if half else torch.float32
+    y = A.selected_vid_map(rows, selection.row_first, selection.pos, shallow if model.msf else None, gate, mask,
+                           selection.scores if model.scat else None, sizes, model.vid_map.conv.weight, model.vid_map.conv.bias)
+    return y, mask
 
 
 def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_masks, text_size=None, dropout=None, dropout_seed=None,
-                     front_end='dense'):
+                     front_end='dense', expert='dense', expert_fn=None, selection=None, vid_rows=None):
     """vid / shallow (bs, D, T) channel-major, vid_masks (bs, T) bool, tokens (B', C_t, Lq) channel-major, text_cls (B', D),
     token_masks (B', 1, Lq) or (B', Lq), text_size: queries per video (None: one each), B' = sum(text_size), all on the GPU.
     -> (fpn_logits1, fpn_logits2, fpn_offsets, fpn_masks) as ``model(..., eval=False)`` returns them, with an autograd graph to every
@@ -106,17 +163,37 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     every video's features once per query, gated, concatenated -- and runs ``masked_conv1d`` on it.  'shared' is
     ``autograd.gated_vid_map``: the products of ``vid_map`` with the features once per video, clips that no query's gate keeps not at
     all, no (B', T, Cin) tensor in the forward or saved for the backward.  A model with ``opt.model.scat`` always takes the shared
-    path (its 2 D + 1 input channels do not fit the dense weight gradient), with the scores dcf_op_sidekick returns."""
+    path (its 2 D + 1 input channels do not fit the dense weight gradient), with the scores dcf_op_sidekick returns.
+    ``expert``: 'dense' reads the expert features ``vid`` of every clip and launches exactly what it launched before the option
+    existed.  'selected' runs vid_map on the expert features of the clips the gates keep (``autograd.selected_vid_map``,
+    include/decafnet_hip_front_select.h), whatever ``front_end`` says, ``scat`` included: first the selection (the scores and the
+    gates as on every path, then dcf_op_select_clips_videos on them -- the compaction ``model.select_clips_videos`` ends with -- and
+    ONE host read, of the videos' counts; the engine is not bound and ``vid_net.stride`` does not matter: vid_map sees the input clips), then the rows --
+    ``vid_rows`` (packed, with the ``selection`` they were made for) if given, else ``expert_fn(b, clips)`` once per video b with its
+    ascending clip list as a CPU int64 tensor, returning (len(clips), D) on the GPU (``vid`` may then be None), else gathered from the
+    dense ``vid`` (``model.gather_clip_rows_videos``: the emulation path) -- then the op.  Nothing of size (bs, D, T) is read or saved
+    on the expert side.  ``shallow`` alone decides the feature type (a float16 ``shallow`` with ``model.half_features`` takes float16
+    rows).  At most 16 videos per forward; ``sfonly`` and ``cdrop`` are refused."""
     from . import modeling
     if front_end not in FRONT_ENDS:
         raise ValueError(f'training_forward: front_end = {front_end!r} (one of {FRONT_ENDS})')
+    if expert not in EXPERTS:
+        raise ValueError(f'training_forward: expert = {expert!r} (one of {EXPERTS})')
+    selected = expert == 'selected'
+    if not selected and (expert_fn is not None or selection is not None or vid_rows is not None):
+        raise ValueError("training_forward: expert_fn / selection / vid_rows belong to expert='selected'")
+    if (vid_rows is None) != (selection is None):
+        raise ValueError('training_forward: vid_rows and selection come together (the packed rows and the selection they were made for)')
     if type(model) is not modeling.PtTransformerEarlyFusionIterative:
         raise NotImplementedError(f'training_forward: {type(model).__name__} is not implemented (PtTransformerEarlyFusionIterative only)')
     if model.sfonly:
         raise NotImplementedError('training_forward: opt.model.sfonly is not implemented: the training branch of the reference '
                                   '(model.py:606-612) never reads it')
-    shared = front_end == 'shared' or bool(model.scat)
+    shared = front_end == 'shared' or bool(model.scat) or selected
     rates = model._train_dropout_rates()                            # None without enable_dropout(); refuses what has no kernel
+    if rates is not None and rates.cdrop > 0.0 and selected:
+        raise ValueError("training_forward: opt.model.vid_net.cdrop > 0 needs expert='dense' with front_end='dense': a per-sample "
+                         "channel mask cannot share the expert product between the queries of a video")
     if rates is not None and rates.cdrop > 0.0 and shared:
         raise ValueError("training_forward: opt.model.vid_net.cdrop > 0 needs front_end='dense' on a model without scat: a per-sample "
                          "channel mask cannot share the products of vid_map between the queries of a video")
@@ -125,10 +202,16 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     if rates is not None and dropout is not None:
         raise ValueError('training_forward: `dropout` is the refinement stage alone on a model without enable_dropout(); this model\'s '
                          'dropout is enabled and covers it')
-    if not vid.is_cuda:
+    if selected:
+        if shallow.size(0) > MAX_SELECTED_VIDEOS:
+            raise ValueError(f"training_forward: expert='selected' takes at most {MAX_SELECTED_VIDEOS} videos per forward (got "
+                             f'{shallow.size(0)}): split the step into micro-batches (TrainStep.step takes a list of them)')
+        if vid is None and expert_fn is None and vid_rows is None:
+            raise ValueError("training_forward: expert='selected' without `vid` needs expert_fn or vid_rows")
+    if not (shallow if selected else vid).is_cuda:
         raise RuntimeError('the training forward runs on the MI355X only: move the inputs to the GPU')
     lib, st = _lib.lib(), _lib.current_stream()
-    bs, D, T = vid.shape
+    bs, D, T = shallow.shape if selected else vid.shape
     sizes = [1] * bs if text_size is None else [int(k) for k in text_size]
     nq = sum(sizes)
     if len(sizes) != bs or min(sizes) < 1 or tokens.size(0) != nq or text_cls.size(0) != nq:
@@ -137,25 +220,26 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
     # include/decafnet_hip_front_half.h); the dense front end builds an fp32 (B', T, Cin) tensor anyway and keeps its upcast
     half = False
     if shared and model.half_features:
-        modeling._check_feature_dtypes(vid, shallow)
-        half = vid.dtype == torch.float16
+        if vid is not None:
+            modeling._check_feature_dtypes(vid, shallow)
+        half = shallow.dtype == torch.float16
     model.last_train_feature_dtype = torch.float16 if half else torch.float32
     if shared and not half:
-        vid, shallow = vid.float(), shallow.float()
+        vid, shallow = (None if vid is None else vid.float()), shallow.float()
     gates, masks, correls, q = [], [], [], 0
     for b, k in enumerate(sizes):                                   # one video and its k queries per call
         sh, cls = (shallow[b] if half else shallow[b].float()).contiguous(), text_cls[q:q + k].float().contiguous()
         vm = vid_masks[b].reshape(-1).to(torch.bool).contiguous()
-        correl = torch.empty(k, T, device=vid.device)
+        correl = torch.empty(k, T, device=shallow.device)
         sidekick = 'dcf_op_sidekick_h' if half else 'dcf_op_sidekick'
         _lib.check(getattr(lib, sidekick)(_lib.ptr(sh), _lib.ptr(cls), _lib.ptr(correl), D, T, k, int(model.norm), st), sidekick)
-        gate, mo = torch.empty(k, T, device=vid.device), torch.empty(k, T, dtype=torch.bool, device=vid.device)
+        gate, mo = torch.empty(k, T, device=shallow.device), torch.empty(k, T, dtype=torch.bool, device=shallow.device)
         _lib.check(lib.dcf_op_gate(_lib.ptr(correl), _lib.ptr(vm), _lib.ptr(gate), _lib.ptr(mo), T, k, model.sn, float(model.sratio),
                                    int(model.msf), st), 'dcf_op_gate')
         gates.append(gate), masks.append(mo), correls.append(correl)
         q += k
     gate, mask = torch.cat(gates), torch.cat(masks)
-    kv_size = torch.tensor(sizes, device=vid.device)
+    kv_size = torch.tensor(sizes, device=shallow.device)
     vid_drop = fus_drop = text_drop = None
     if rates is not None:                                           # one key per forward
         seed = (model._next_dropout_seed() if dropout_seed is None else int(dropout_seed)) & ((1 << 64) - 1)
@@ -165,7 +249,10 @@ def training_forward(model, vid, shallow, vid_masks, tokens, text_cls, token_mas
         text_drop = A.DropSpec(seed, 0, rates.text_net.proj, rates.text_net.path, attn_p=rates.text_net.attn)
         if rates.refine > 0.0:
             dropout = (seed, rates.refine, 0)
-    if shared:                                                      # the products once per video: nothing is repeated or transposed
+    if selected:                                                    # the expert half on the rows of the selected clips alone
+        vid_map, mask = _selected_front(model, vid, shallow.contiguous(), vid_masks, gate, mask, torch.cat(correls), sizes, half, expert_fn,
+                                        selection, vid_rows)
+    elif shared:                                                    # the products once per video: nothing is repeated or transposed
         vid_map = A.gated_vid_map(vid, shallow if model.msf else None, gate, mask, torch.cat(correls) if model.scat else None, sizes,
                                   model.vid_map.conv.weight, model.vid_map.conv.bias)
     else:
@@ -199,11 +286,22 @@ class TrainStep:
     ``optim.StepGuard`` (``self.guard``), armed around forward, backward and update; a step whose gradients are not all finite is
     skipped on the GPU (module docstring).  ``False`` -- the default -- launches exactly what it launched before the option existed.
     ``device_count=True``: Adam's step counts live on the GPU and advance on applied steps only (module docstring); the scheduler,
-    ``itr`` and the loss-norm update still follow attempts.  ``False`` -- the default -- changes nothing."""
+    ``itr`` and the loss-norm update still follow attempts.  ``False`` -- the default -- changes nothing.
+    ``expert``: 'dense' or 'selected', and ``expert_fn``, handed to ``training_forward``: with 'selected' vid_map runs on the expert
+    features of the clips the gates keep -- from ``expert_fn(b, clips)`` per video of a micro-batch if given (the batch's 'vid' may then
+    be None), else gathered from the batch's dense 'vid', which is what ``fit`` on a ``data.TrainLoader`` does.  'dense' -- the default
+    -- launches exactly what it launched before the option existed.  Like ``front_end`` it is a property of the step, not of the
+    checkpoint: ``state()`` / ``load_state()`` carry neither, and a checkpoint moves freely between the settings."""
 
-    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1, front_end='dense', skip_nonfinite=False, device_count=False):
+    def __init__(self, model, opt, world_size=1, itrs_per_epoch=1, front_end='dense', skip_nonfinite=False, device_count=False,
+                 expert='dense', expert_fn=None):
         if front_end not in FRONT_ENDS:
             raise ValueError(f'TrainStep: front_end = {front_end!r} (one of {FRONT_ENDS})')
+        if expert not in EXPERTS:
+            raise ValueError(f'TrainStep: expert = {expert!r} (one of {EXPERTS})')
+        if expert_fn is not None and expert != 'selected':
+            raise ValueError("TrainStep: expert_fn belongs to expert='selected'")
+        self.expert, self.expert_fn = expert, expert_fn
         if not isinstance(skip_nonfinite, bool):
             raise ValueError(f'TrainStep: skip_nonfinite = {skip_nonfinite!r} (True or False)')
         if not isinstance(device_count, bool):
@@ -253,7 +351,8 @@ class TrainStep:
         self.optimizer.zero_grad(set_to_none=True)
         sums = {}
         for i, (mb, tg) in enumerate(zip(batches, targets)):
-            out = training_forward(self.model, *(mb.get(k) for k in _BATCH_KEYS), front_end=self.front_end)
+            extra = {} if self.expert == 'dense' else {'expert': self.expert, 'expert_fn': self.expert_fn}
+            out = training_forward(self.model, *(mb.get(k) for k in _BATCH_KEYS), front_end=self.front_end, **extra)
             d = self.objective(out, tg)
             self._backward(d['total'], i == len(batches) - 1)
             for k, v in d.items():
@@ -780,18 +879,19 @@ class DataParallelTrainStep(TrainStep):
     was launched before the option existed.
 
     ``device_count=True``: as in ``TrainStep``; every rank keeps its own counts, which agree as long as the verdicts do.
+    ``expert`` / ``expert_fn``: as in ``TrainStep``; every rank selects the clips of its own micro-batches.
 
     Backends: nccl (RCCL), one GPU per rank; gloo stages every bucket through the host and is a flow check for a one-GPU box."""
 
     def __init__(self, model, opt, itrs_per_epoch=1, process_group=None, bucket_bytes=D.DEFAULT_BUCKET_BYTES, front_end='dense',
-                 skip_nonfinite=False, device_count=False, agree_skips=False):
+                 skip_nonfinite=False, device_count=False, agree_skips=False, expert='dense', expert_fn=None):
         if not isinstance(agree_skips, bool):
             raise ValueError(f'DataParallelTrainStep: agree_skips = {agree_skips!r} (True or False)')
         self.agree_skips = agree_skips
         self.group = process_group
         self.world, self._backend = D._group_info(process_group)
         super().__init__(model, opt, world_size=self.world, itrs_per_epoch=itrs_per_epoch, front_end=front_end,
-                         skip_nonfinite=skip_nonfinite, device_count=device_count)
+                         skip_nonfinite=skip_nonfinite, device_count=device_count, expert=expert, expert_fn=expert_fn)
         D.broadcast_module(model, 0, process_group)
         D.broadcast_module(self.ema.module, 0, process_group)
         self.reducer = D.GradReducer(self._params, process_group, bucket_bytes)
