@@ -817,24 +817,70 @@ int dcf_forward_eval_gated(dcf_model* m, const float* vid, const float* shallow_
 }
 
 namespace dcf {
-static int forward_selected(dcf_model* m, const char* who, const float* rows, int32_t n_rows, const int32_t* pos, const float* shallow,
-                            const uint8_t* vid_mask, int64_t T, int32_t nq, const float* const* text, const uint8_t* const* text_mask,
-                            const int32_t* text_len, const float* gate, float* logits_out, float* offsets_out, uint8_t* masks_out,
-                            hipStream_t st) {
+// The selected-clip forward of `nvid` videos.  row_first = nullptr is the one-video form (nvid = 1, the rows are [0, n_rows)): forward()
+// takes that path on `nvid == 1 || fc.sel_first`, so the one-video entry points never hand a row_first over.
+static int forward_selected(dcf_model* m, int nvid, const float* rows, const int32_t* row_first, int32_t n_rows, const int32_t* pos,
+                            const float* const* shallow, const uint8_t* const* vid_mask, int64_t T, const int32_t* nq_per_video, int nq,
+                            const float* const* text, const uint8_t* const* text_mask, const int32_t* text_len, const float* gate,
+                            const float* correl, float* logits_out, float* offsets_out, uint8_t* masks_out, hipStream_t st) {
   VideoSet vs;
-  vs.nvid = 1; vs.vid[0] = nullptr; vs.shallow[0] = shallow; vs.mask[0] = vid_mask; vs.text_cls[0] = nullptr; vs.nq[0] = nq;
+  vs.nvid = nvid;
+  for (int v = 0; v < nvid; ++v) {
+    vs.vid[v] = nullptr; vs.shallow[v] = shallow[v]; vs.mask[v] = vid_mask[v]; vs.text_cls[v] = nullptr; vs.nq[v] = nq_per_video[v];
+  }
   ForwardCall fc{text, text_mask, text_len, gate, logits_out, offsets_out, masks_out};
-  fc.sel_rows = rows; fc.sel_pos = pos; fc.sel_n = n_rows;
+  fc.sel_rows = rows; fc.sel_pos = pos; fc.sel_n = n_rows; fc.sel_first = row_first; fc.sel_correl = correl;
   return forward_maybe_graph(m, vs, (int)T, nq, fc, st);
 }
-// the refusals of the selected-clip forward that need no workspace: before any launch, and before the half form's upcast
-static int selected_checks(const dcf_model* m, const char* who, int32_t n_rows, int64_t T) {
+// The refusals of the selected-clip forwards that need no workspace: before any launch, and before the half forms' upcast.  row_first =
+// nullptr is the one-video form, which refuses scat and bounds n_rows; the several-video form wants correl exactly with scat and bounds
+// every video's rows.  *nq_out = the queries of all videos.
+static int selected_checks(const dcf_model* m, const char* who, int nvid, const int32_t* row_first, int32_t n_rows, int64_t T,
+                           const int32_t* nq_per_video, const float* correl, int* nq_out) {
   DCF_CHECK(T >= 1 && T < (1ll << 24), "%s: T out of range", who);
   DCF_CHECK(m->finalized, "%s: model not finalized", who);
-  DCF_CHECK(!m->cfg.scat, "%s: opt.model.scat needs the sidekick scores, which this forward is not handed (as dcf_forward_eval_gated)", who);
+  if (row_first) DCF_CHECK(nvid >= 1 && nvid <= DCF_MAX_VIDEOS, "%s: 1 .. %d videos per call (got %d)", who, DCF_MAX_VIDEOS, nvid);
+  else DCF_CHECK(!m->cfg.scat, "%s: opt.model.scat needs the sidekick scores, which this forward is not handed (as dcf_forward_eval_gated)", who);
   DCF_CHECK(m->vid_w1, "%s: opt.model.sfonly reads no expert features: there is nothing to select", who);
   DCF_CHECK(vid_stride_of(m->cfg) == 1, "%s: vid_net.stride = %d: the externally gated forward takes vid_net.stride = 1", who, vid_stride_of(m->cfg));
-  DCF_CHECK(n_rows >= 1 && n_rows <= T, "%s: n_rows=%d must lie in [1, T=%lld]", who, (int)n_rows, (long long)T);
+  int nq = 0;
+  if (!row_first) {
+    DCF_CHECK(n_rows >= 1 && n_rows <= T, "%s: n_rows=%d must lie in [1, T=%lld]", who, (int)n_rows, (long long)T);
+    nq = nq_per_video[0];
+  } else {
+    DCF_CHECK(!m->cfg.scat == !correl, "%s: correl (the sidekick scores of dcf_select_videos) is required with opt.model.scat and must be "
+                                       "null without it", who);
+    for (int v = 0; v < nvid; ++v) {
+      DCF_CHECK(nq_per_video[v] >= 1 && nq + nq_per_video[v] <= DCF_MAX_VIDEOS * 64, "%s: bad query count of video %d", who, v);
+      nq += nq_per_video[v];
+    }
+    const int Bmax = std::min(nq, m->cfg.max_batch > 0 ? m->cfg.max_batch : 8);
+    DCF_CHECK(nvid == 1 || Bmax <= 16, "%s: several videos per forward need max_batch <= 16 (got %d)", who, Bmax);
+    DCF_CHECK(row_first[0] == 0, "%s: row_first[0] = %d, not 0", who, (int)row_first[0]);
+    for (int v = 0; v < nvid; ++v) {
+      const int64_t n = (int64_t)row_first[v + 1] - row_first[v];
+      DCF_CHECK(n >= 1 && n <= T, "%s: video %d has %lld rows: every video needs 1 .. T = %lld", who, v, (long long)n, (long long)T);
+    }
+  }
+  *nq_out = nq;
+  return 0;
+}
+// The half forms: the packed rows and every video's shallow features upcast once into the engine's half workspace (exact: every binary16
+// value is an fp32 value), then the fp32 form: the same numbers as fp32 operands of the same values give.  Layout: the rows, then the
+// videos' shallow features, each piece rounded up to 256 bytes.
+static int upcast_selected_h(dcf_model* m, int nvid, const uint16_t* vid_rows, int64_t n_rows, const uint16_t* const* shallow_vid, int64_t T,
+                             hipStream_t st, const float** rows32, const float** sh32) {
+  const int D = m->cfg.D;
+  const size_t rows_b = ((size_t)n_rows * D * sizeof(float) + 255) & ~(size_t)255;
+  const size_t sh_b = ((size_t)D * T * sizeof(float) + 255) & ~(size_t)255;
+  if (grow_half_ws(m, rows_b + sh_b * nvid, st)) return -1;
+  if (launch_half_to_f32(vid_rows, reinterpret_cast<float*>(m->half_ws), n_rows * D, st)) return -1;
+  *rows32 = reinterpret_cast<const float*>(m->half_ws);
+  for (int v = 0; v < nvid; ++v) {
+    float* d = reinterpret_cast<float*>(m->half_ws + rows_b + sh_b * v);
+    if (launch_half_to_f32(shallow_vid[v], d, (int64_t)D * T, st)) return -1;
+    sh32[v] = d;
+  }
   return 0;
 }
 }  // namespace dcf
@@ -848,9 +894,10 @@ int dcf_forward_eval_selected(dcf_model* m, const float* vid_rows, int32_t n_row
   const char* who = "dcf_forward_eval_selected";
   DCF_CHECK(m && vid_rows && pos && shallow_vid && vid_mask && text && text_len && gate && logits_out && offsets_out && masks_out,
             "%s: null argument", who);
-  if (dcf::selected_checks(m, who, n_rows, T)) return -1;
-  return dcf::forward_selected(m, who, vid_rows, n_rows, pos, shallow_vid, vid_mask, T, nq, text, text_mask, text_len, gate, logits_out,
-                               offsets_out, masks_out, (hipStream_t)stream);
+  int nq_all = 0;
+  if (dcf::selected_checks(m, who, 1, nullptr, n_rows, T, &nq, nullptr, &nq_all)) return -1;
+  return dcf::forward_selected(m, 1, vid_rows, nullptr, n_rows, pos, &shallow_vid, &vid_mask, T, &nq, nq, text, text_mask, text_len, gate,
+                               nullptr, logits_out, offsets_out, masks_out, (hipStream_t)stream);
 }
 
 int dcf_forward_eval_selected_h(dcf_model* m, const uint16_t* vid_rows, int32_t n_rows, const int32_t* pos, const uint16_t* shallow_vid,
@@ -860,64 +907,13 @@ int dcf_forward_eval_selected_h(dcf_model* m, const uint16_t* vid_rows, int32_t 
   const char* who = "dcf_forward_eval_selected_h";
   DCF_CHECK(m && vid_rows && pos && shallow_vid && vid_mask && text && text_len && gate && logits_out && offsets_out && masks_out,
             "%s: null argument", who);
-  if (dcf::selected_checks(m, who, n_rows, T)) return -1;
-  // the compact rows and the shallow features upcast once into the engine's half workspace (exact: every binary16 value is an fp32
-  // value), then the fp32 form: the same numbers as fp32 operands of the same values give
-  hipStream_t st = (hipStream_t)stream;
-  const int D = m->cfg.D;
-  const size_t rows_b = ((size_t)n_rows * D * sizeof(float) + 255) & ~(size_t)255;
-  const size_t sh_b = ((size_t)D * T * sizeof(float) + 255) & ~(size_t)255;
-  if (dcf::grow_half_ws(m, rows_b + sh_b, st)) return -1;
-  float* rows32 = reinterpret_cast<float*>(m->half_ws);
-  float* sh32 = reinterpret_cast<float*>(m->half_ws + rows_b);
-  if (dcf::launch_half_to_f32(vid_rows, rows32, (int64_t)n_rows * D, st)) return -1;
-  if (dcf::launch_half_to_f32(shallow_vid, sh32, (int64_t)D * T, st)) return -1;
-  return dcf::forward_selected(m, who, rows32, n_rows, pos, sh32, vid_mask, T, nq, text, text_mask, text_len, gate, logits_out, offsets_out,
-                               masks_out, st);
+  int nq_all = 0;
+  if (dcf::selected_checks(m, who, 1, nullptr, n_rows, T, &nq, nullptr, &nq_all)) return -1;
+  const float *rows32, *sh32;
+  if (dcf::upcast_selected_h(m, 1, vid_rows, n_rows, &shallow_vid, T, (hipStream_t)stream, &rows32, &sh32)) return -1;
+  return dcf::forward_selected(m, 1, rows32, nullptr, n_rows, pos, &sh32, &vid_mask, T, &nq, nq, text, text_mask, text_len, gate, nullptr,
+                               logits_out, offsets_out, masks_out, (hipStream_t)stream);
 }
-
-namespace dcf {
-// the refusals of the several-video selected forward that need no workspace: before any launch, and before the half form's upcast;
-// *nq_out = the queries of all videos
-static int videos_selected_checks(const dcf_model* m, const char* who, int nvid, const int32_t* row_first, int64_t T,
-                                  const int32_t* nq_per_video, const float* correl, int* nq_out) {
-  DCF_CHECK(T >= 1 && T < (1ll << 24), "%s: T out of range", who);
-  DCF_CHECK(m->finalized, "%s: model not finalized", who);
-  DCF_CHECK(nvid >= 1 && nvid <= DCF_MAX_VIDEOS, "%s: 1 .. %d videos per call (got %d)", who, DCF_MAX_VIDEOS, nvid);
-  DCF_CHECK(m->vid_w1, "%s: opt.model.sfonly reads no expert features: there is nothing to select", who);
-  DCF_CHECK(vid_stride_of(m->cfg) == 1, "%s: vid_net.stride = %d: the externally gated forward takes vid_net.stride = 1", who, vid_stride_of(m->cfg));
-  DCF_CHECK(!m->cfg.scat == !correl, "%s: correl (the sidekick scores of dcf_select_videos) is required with opt.model.scat and must be "
-                                     "null without it", who);
-  int nq = 0;
-  for (int v = 0; v < nvid; ++v) {
-    DCF_CHECK(nq_per_video[v] >= 1 && nq + nq_per_video[v] <= DCF_MAX_VIDEOS * 64, "%s: bad query count of video %d", who, v);
-    nq += nq_per_video[v];
-  }
-  const int Bmax = std::min(nq, m->cfg.max_batch > 0 ? m->cfg.max_batch : 8);
-  DCF_CHECK(nvid == 1 || Bmax <= 16, "%s: several videos per forward need max_batch <= 16 (got %d)", who, Bmax);
-  DCF_CHECK(row_first[0] == 0, "%s: row_first[0] = %d, not 0", who, (int)row_first[0]);
-  for (int v = 0; v < nvid; ++v) {
-    const int64_t n = (int64_t)row_first[v + 1] - row_first[v];
-    DCF_CHECK(n >= 1 && n <= T, "%s: video %d has %lld rows: every video needs 1 .. T = %lld", who, v, (long long)n, (long long)T);
-  }
-  *nq_out = nq;
-  return 0;
-}
-static int forward_videos_selected(dcf_model* m, int nvid, const float* rows, const int32_t* row_first, const int32_t* pos,
-                                   const float* const* shallow, const uint8_t* const* vid_mask, int64_t T, const int32_t* nq_per_video,
-                                   int nq, const float* const* text, const uint8_t* const* text_mask, const int32_t* text_len,
-                                   const float* gate, const float* correl, float* logits_out, float* offsets_out, uint8_t* masks_out,
-                                   hipStream_t st) {
-  VideoSet vs;
-  vs.nvid = nvid;
-  for (int v = 0; v < nvid; ++v) {
-    vs.vid[v] = nullptr; vs.shallow[v] = shallow[v]; vs.mask[v] = vid_mask[v]; vs.text_cls[v] = nullptr; vs.nq[v] = nq_per_video[v];
-  }
-  ForwardCall fc{text, text_mask, text_len, gate, logits_out, offsets_out, masks_out};
-  fc.sel_rows = rows; fc.sel_pos = pos; fc.sel_n = row_first[nvid]; fc.sel_first = row_first; fc.sel_correl = correl;
-  return forward_maybe_graph(m, vs, (int)T, nq, fc, st);
-}
-}  // namespace dcf
 
 int dcf_forward_eval_videos_selected(dcf_model* m, int32_t nvid, const float* vid_rows, const int32_t* row_first, const int32_t* pos,
                                      const float* const* shallow_vid, const uint8_t* const* vid_mask, int64_t T,
@@ -928,10 +924,10 @@ int dcf_forward_eval_videos_selected(dcf_model* m, int32_t nvid, const float* vi
   DCF_CHECK(m && vid_rows && row_first && pos && shallow_vid && vid_mask && nq_per_video && text && text_len && gate && logits_out &&
                 offsets_out && masks_out, "%s: null argument", who);
   int nq = 0;
-  if (dcf::videos_selected_checks(m, who, nvid, row_first, T, nq_per_video, correl, &nq)) return -1;
+  if (dcf::selected_checks(m, who, nvid, row_first, 0, T, nq_per_video, correl, &nq)) return -1;
   for (int v = 0; v < nvid; ++v) DCF_CHECK(shallow_vid[v] && vid_mask[v], "%s: video %d is incomplete", who, v);
-  return dcf::forward_videos_selected(m, nvid, vid_rows, row_first, pos, shallow_vid, vid_mask, T, nq_per_video, nq, text, text_mask,
-                                      text_len, gate, correl, logits_out, offsets_out, masks_out, (hipStream_t)stream);
+  return dcf::forward_selected(m, nvid, vid_rows, row_first, row_first[nvid], pos, shallow_vid, vid_mask, T, nq_per_video, nq, text,
+                               text_mask, text_len, gate, correl, logits_out, offsets_out, masks_out, (hipStream_t)stream);
 }
 
 int dcf_forward_eval_videos_selected_h(dcf_model* m, int32_t nvid, const uint16_t* vid_rows, const int32_t* row_first,
@@ -943,25 +939,12 @@ int dcf_forward_eval_videos_selected_h(dcf_model* m, int32_t nvid, const uint16_
   DCF_CHECK(m && vid_rows && row_first && pos && shallow_vid && vid_mask && nq_per_video && text && text_len && gate && logits_out &&
                 offsets_out && masks_out, "%s: null argument", who);
   int nq = 0;
-  if (dcf::videos_selected_checks(m, who, nvid, row_first, T, nq_per_video, correl, &nq)) return -1;
+  if (dcf::selected_checks(m, who, nvid, row_first, 0, T, nq_per_video, correl, &nq)) return -1;
   for (int v = 0; v < nvid; ++v) DCF_CHECK(shallow_vid[v] && vid_mask[v], "%s: video %d is incomplete", who, v);
-  // the packed rows and every video's shallow features upcast once into the engine's half workspace (exact), then the fp32 form
-  hipStream_t st = (hipStream_t)stream;
-  const int D = m->cfg.D;
-  const int64_t n_rows = row_first[nvid];
-  const size_t rows_b = ((size_t)n_rows * D * sizeof(float) + 255) & ~(size_t)255;
-  const size_t sh_b = ((size_t)D * T * sizeof(float) + 255) & ~(size_t)255;
-  if (dcf::grow_half_ws(m, rows_b + sh_b * nvid, st)) return -1;
-  float* rows32 = reinterpret_cast<float*>(m->half_ws);
-  const float* sh32[dcf::DCF_MAX_VIDEOS];
-  if (dcf::launch_half_to_f32(vid_rows, rows32, n_rows * D, st)) return -1;
-  for (int v = 0; v < nvid; ++v) {
-    float* d = reinterpret_cast<float*>(m->half_ws + rows_b + sh_b * v);
-    if (dcf::launch_half_to_f32(shallow_vid[v], d, (int64_t)D * T, st)) return -1;
-    sh32[v] = d;
-  }
-  return dcf::forward_videos_selected(m, nvid, rows32, row_first, pos, sh32, vid_mask, T, nq_per_video, nq, text, text_mask, text_len, gate,
-                                      correl, logits_out, offsets_out, masks_out, st);
+  const float *rows32, *sh32[dcf::DCF_MAX_VIDEOS];
+  if (dcf::upcast_selected_h(m, nvid, vid_rows, row_first[nvid], shallow_vid, T, (hipStream_t)stream, &rows32, sh32)) return -1;
+  return dcf::forward_selected(m, nvid, rows32, row_first, row_first[nvid], pos, sh32, vid_mask, T, nq_per_video, nq, text, text_mask,
+                               text_len, gate, correl, logits_out, offsets_out, masks_out, (hipStream_t)stream);
 }
 
 int dcf_graph_active(const dcf_model* m) { return m ? m->last_launch : 0; }

@@ -444,6 +444,17 @@ class GroundingEvaluator:
         self.outputs = out
         return model_._last_flat, T
 
+    def _expert_rows(self, data, clips_host, count, half):
+        """``expert_fn``'s rows for the ``count`` clips ``clips_host`` of one video, checked and in the type the forward takes (half: the
+        shallow features are float16), on whatever device ``expert_fn`` left them"""
+        rows = self.expert_fn(data, clips_host)
+        if not torch.is_tensor(rows) or rows.dim() != 2 or rows.size(0) != count:
+            raise ValueError(f'expert_fn returned {tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__} for {count} clips: '
+                             f'one row of D features per clip is expected')
+        if self.feature_dtype is not None:
+            return self._to_half(rows, 'the expert rows', data.get('clip_id', '?') if isinstance(data, dict) else '?')
+        return rows if half else rows.float()
+
     def _forward_selected(self, data, model_, args):
         """the two-call pattern on one forward window: select_clips -> the rows of the selected clips -> forward_selected"""
         if isinstance(data, dict) and data.get('bank') is not None:
@@ -453,14 +464,7 @@ class GroundingEvaluator:
         if self.expert_fn is None:
             rows = model_.gather_clip_rows(window, sel)
         else:
-            rows = self.expert_fn(data, sel.clips_host())
-            if not torch.is_tensor(rows) or rows.dim() != 2 or rows.size(0) != sel.count:
-                raise ValueError(f'expert_fn returned {tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__} for {sel.count} clips: '
-                                 f'one row of D features per clip is expected')
-            if self.feature_dtype is not None:
-                rows = self._to_half(rows, 'the expert rows', data.get('clip_id', '?') if isinstance(data, dict) else '?')
-            elif shallow_window.dtype != torch.float16:
-                rows = rows.float()
+            rows = self._expert_rows(data, sel.clips_host(), sel.count, shallow_window.dtype == torch.float16)
             rows = rows.to(shallow_window.device, non_blocking=True)
         self.last_selection = sel
         return model_.forward_selected(rows, sel, shallow_window, mask, texts, tmasks)
@@ -481,15 +485,7 @@ class GroundingEvaluator:
             half = videos[0][1].dtype == torch.float16
             parts = []
             for v, (data, _, _, _) in enumerate(pending):
-                r = self.expert_fn(data, batch.clips_host(v))
-                if not torch.is_tensor(r) or r.dim() != 2 or r.size(0) != batch.counts[v]:
-                    raise ValueError(f'expert_fn returned {tuple(r.shape) if torch.is_tensor(r) else type(r).__name__} for {batch.counts[v]} '
-                                     f'clips: one row of D features per clip is expected')
-                if self.feature_dtype is not None:
-                    r = self._to_half(r, 'the expert rows', data.get('clip_id', '?') if isinstance(data, dict) else '?')
-                elif not half:
-                    r = r.float()
-                parts.append(r)
+                parts.append(self._expert_rows(data, batch.clips_host(v), batch.counts[v], half))
             dev = videos[0][1].device
             if any(r.is_cuda for r in parts):
                 rows = torch.cat([r.to(dev, non_blocking=True) for r in parts])

@@ -413,11 +413,7 @@ def _encode_text(model, tokens, token_masks):
     worker_v2.py:953)."""
     if not tokens.is_cuda:
         raise RuntimeError('encode_text runs on the MI355X only: move the tokens to the GPU')
-    if model._engine is None:
-        model._engine = _Engine(model._config())
-    model._raise_if_flagged()
-    eng = model._engine
-    eng.bind(model)
+    eng = model._engine_ready()
     tn = model.text_net
     bs, ct, lq = tokens.shape
     assert ct == tn.in_dim, (ct, tn.in_dim)
@@ -455,6 +451,31 @@ def _check_feature_dtypes(vid, shallow):
     if (vid.dtype == torch.float16) != (shallow.dtype == torch.float16):
         raise ValueError(f'vid is {vid.dtype} and shallow_vid is {shallow.dtype}: float16 clip features come as a pair '
                          f'(cast one of them, or set model.half_features = False and pass both as fp32)')
+
+
+def _same_dtype_videos(what, tensors):
+    if len({x.dtype == torch.float16 for x in tensors}) != 1:
+        raise ValueError(f'{what}: the videos of one call are all float16 or none of them is')
+
+
+def _text_table(text, text_masks):
+    """The engine's query tables for a flat list of encoded queries: text[q] (TE, Lk), text_masks[q] of Lk elements.  Returns
+    (tptr, mptr, tlen, keep); keep holds what the pointers point at -- the inputs themselves where they are contiguous fp32 / bool."""
+    nq = len(text)
+    tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
+    keep = []
+    for q in range(nq):
+        t = text[q].contiguous().float()
+        m = text_masks[q].reshape(-1).to(torch.bool).contiguous()
+        assert t.dim() == 2 and m.numel() == t.size(1)
+        keep += [t, m]
+        tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
+    return tptr, mptr, tlen, keep
+
+
+# what _video_tables returns: c_void_p tables over the videos (vid / cls: None where not asked for), the int32 table of query counts, the
+# (TE, Lk) texts and their masks of all videos in video order, and keep: per video [shallow, mask, vid?, cls?], what the tables point at
+_VideoTables = namedtuple('_VideoTables', 'vid shallow mask cls nqs text text_masks keep')
 
 
 class Selection:
@@ -694,14 +715,6 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         Lk = Lq + use_bkgd_token.  Runs TextTransformer.forward (text_net.py:158-188) on the GPU (dcf_text_encode)."""
         return _encode_text(self, tokens, token_masks)
 
-    def _feature_pair(self, vid, shallow, half_ok=True):
-        """(vid, shallow, half) contiguous for the engine: float16 tensors themselves (no copy of a contiguous tensor) where the pair is
-        float16 and ``half_features`` is on, fp32 otherwise.  One of the two in float16 and the other not is refused."""
-        _check_feature_dtypes(vid, shallow)
-        if half_ok and self.half_features and vid.dtype == torch.float16:
-            return vid.contiguous(), shallow.contiguous(), True
-        return vid.contiguous().float(), shallow.contiguous().float(), False
-
     def forward(self, vid, shallow_vid, vid_masks, text, text_cls, text_masks, text_size=None, mv_data=None, eval=False):
         if not eval:
             return self._drop_forward(vid, shallow_vid, vid_masks, text, text_cls, text_masks, text_size, mv_data, eval)
@@ -737,46 +750,28 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         assert text.size(0) == nq and text_cls.size(0) == nq, (text.shape, text_cls.shape, sizes)
         enc, enc_mask = self.encode_text(text, text_masks.reshape(nq, 1, -1))  # (nq, TE, Lk), (nq, 1, Lk)
         dev = vid.device
-        eng = self._engine
+        eng = self._engine                           # encode_text has created and bound it, and looked at the numerics flag
         lib = eng.lib
-        keep = []
-        vptr, sptr, mptr_v, cptr = ((ctypes.c_void_p * bs)() for _ in range(4))
-        nqs = (ctypes.c_int32 * bs)()
-        tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
-        q = 0
-        for b in range(bs):
-            vc, sc = vid[b].contiguous().float(), shallow_vid[b].contiguous().float()
-            mc = vid_masks[b].reshape(-1).to(torch.bool).contiguous()
-            cc = text_cls[q:q + sizes[b]].contiguous().float()
-            assert sc.shape == vc.shape == (self.D, T) and mc.numel() == T and cc.shape == (sizes[b], self.D)
-            keep += [vc, sc, mc, cc]
-            vptr[b], sptr[b], mptr_v[b], cptr[b], nqs[b] = vc.data_ptr(), sc.data_ptr(), mc.data_ptr(), cc.data_ptr(), sizes[b]
-            for i in range(q, q + sizes[b]):
-                t = enc[i].contiguous().float()
-                m = enc_mask[i].reshape(-1).to(torch.bool).contiguous()
-                keep += [t, m]
-                tptr[i], mptr[i], tlen[i] = t.data_ptr(), m.data_ptr(), t.size(1)
-            q += sizes[b]
-        pe = None
-        if self.vid_net.use_abs_pe:
-            Tp = T // self.vid_net.stride            # the pyramid (and its position encoding) starts behind the strided convolutions
-            pe = self._position_encoding(Tp, dev)
-            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), Tp), 'dcf_model_set_pe')
+        first = [0]
+        for k in sizes:
+            first.append(first[-1] + k)
+        tb = self._video_tables([(vid[b:b + 1], shallow_vid[b:b + 1], vid_masks[b], None, text_cls[first[b]:first[b + 1]], None)
+                                 for b in range(bs)], False, text=False)
+        tptr, mptr, tlen, tkeep = _text_table(enc, enc_mask)
+        pe = self._install_pe(eng, T, dev)
         S = lib.dcf_points_per_query(eng.handle, T)
-        logits2 = torch.empty(nq, S, device=dev, dtype=torch.float32)
-        offsets = torch.empty(nq, S, 2, device=dev, dtype=torch.float32)
-        masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
-        sizes_l = [(T // self.vid_net.stride) >> l for l in range(self.vid_net.arch[2])]
+        logits2, offsets, masks = flat = self._alloc_outputs(nq, S, dev, False)
+        keep = tb.keep + tkeep + [pe, enc, enc_mask]
+        sizes_l = self._level_sizes(T)
         if self.MODEL_KIND != 0:
             # PtTransformer (model.py:110-161) / PtTransformerEarlyFusion (model.py:300-373): one classification head, no refinement
             # branch -- the training forward at p = 0 computes, per (video, query) row, exactly what the evaluation forward computes
             # (the gate, vid_map, fusion, encoder and heads of model.py:83-147 / :320-362 do not depend on `eval`), so it runs the
             # evaluation engine over the (video, query) rows and returns the reference's three tuples
-            _lib.check(lib.dcf_forward_eval_videos(eng.handle, bs, vptr, sptr, mptr_v, T, nqs, tptr, mptr, tlen, cptr, _lib.ptr(logits2),
-                                                   _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()), 'dcf_forward_eval_videos')
-            self._last_inputs = (keep, pe, enc, enc_mask)
-            self._last_flat = (logits2, offsets, masks)
-            self._probe_numerics()
+            _lib.check(lib.dcf_forward_eval_videos(eng.handle, bs, tb.vid, tb.shallow, tb.mask, T, tb.nqs, tptr, mptr, tlen, tb.cls,
+                                                   _lib.ptr(logits2), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()),
+                       'dcf_forward_eval_videos')
+            self._finish(keep, flat, None)
             return tuple(logits2.split(sizes_l, 1)), tuple(offsets.split(sizes_l, 1)), tuple(masks.split(sizes_l, 1))
         logits1 = torch.empty(nq, S, device=dev, dtype=torch.float32)
         seed = 0
@@ -785,12 +780,10 @@ class PtTransformerEarlyFusionIterative(nn.Module):
             self.last_dropout_seed = seed
         sseed = seed - (1 << 64) if seed >= 1 << 63 else seed          # the key's 64 bits as the ABI's int64
         _lib.check(lib.dcf_model_set_dropout(eng.handle, *(rates or (0.0,) * 5), sseed), 'dcf_model_set_dropout')
-        _lib.check(lib.dcf_forward_train_videos(eng.handle, bs, vptr, sptr, mptr_v, T, nqs, tptr, mptr, tlen, cptr, _lib.ptr(logits1),
-                                                _lib.ptr(logits2), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()),
-                   'dcf_forward_train_videos')
-        self._last_inputs = (keep, pe, enc, enc_mask)
-        self._last_flat = (logits2, offsets, masks)
-        self._probe_numerics()
+        _lib.check(lib.dcf_forward_train_videos(eng.handle, bs, tb.vid, tb.shallow, tb.mask, T, tb.nqs, tptr, mptr, tlen, tb.cls,
+                                                _lib.ptr(logits1), _lib.ptr(logits2), _lib.ptr(offsets), _lib.ptr(masks),
+                                                _lib.current_stream()), 'dcf_forward_train_videos')
+        self._finish(keep, flat, None)
         return (tuple(logits1.split(sizes_l, 1)), tuple(logits2.split(sizes_l, 1)), tuple(offsets.split(sizes_l, 1)),
                 tuple(masks.split(sizes_l, 1)))
 
@@ -923,6 +916,95 @@ class PtTransformerEarlyFusionIterative(nn.Module):
             eng.pe_cache = {T: pe[:, :T].t().contiguous().to(device)}
         return eng.pe_cache[T]
 
+    # -- marshalling of a forward, in the order a route calls them ("adding a forward entry point") ---------------------
+    def _engine_ready(self, check_flag=True):
+        """the engine, created if absent and bound to the current parameters; check_flag: raise what an earlier forward flagged"""
+        if self._engine is None:
+            self._engine = _Engine(self._config())
+        if check_flag:
+            self._raise_if_flagged()
+        self._engine.bind(self)
+        return self._engine
+
+    def _video_tables(self, videos, half, vid=True, cls=True, text=True):
+        """The per-video tables of a call as a ``_VideoTables``.  ``videos``: tuples ``(vid (1, D, T), shallow_vid (1, D, T), vid_masks (T
+        elements), text, text_cls (nq, D), text_masks)`` as ``forward_videos`` takes them, of one length T; ``vid`` / ``text_cls`` / ``text``
+        and ``text_masks`` are read only where asked for.  The features go as float16 (half) or fp32, the masks as bool, each contiguous: a
+        tensor that is so already goes as itself, no copy.  nqs counts ``text_cls`` rows, or the texts where cls is not asked for."""
+        nv, T = len(videos), videos[0][1].size(-1)
+        vptr, sptr, mptr, cptr = ((ctypes.c_void_p * nv)() for _ in range(4))
+        nqs = (ctypes.c_int32 * nv)()
+        keep, flat_text, flat_masks = [], [], []
+        for v, video in enumerate(videos):
+            assert video[1].dim() == 3 and video[1].size(0) == 1, video[1].size()
+            sc = video[1][0].contiguous() if half else video[1][0].contiguous().float()
+            mc = video[2].reshape(-1).to(torch.bool).contiguous()
+            assert sc.shape == (self.D, T) and mc.numel() == T, 'videos of one call share the padded length'
+            keep += [sc, mc]
+            sptr[v], mptr[v] = sc.data_ptr(), mc.data_ptr()
+            if vid:
+                assert video[0].dim() == 3 and video[0].size(0) == 1, video[0].size()
+                vc = video[0][0].contiguous() if half else video[0][0].contiguous().float()
+                assert vc.shape == sc.shape, 'videos of one call share the padded length'
+                keep.append(vc)
+                vptr[v] = vc.data_ptr()
+            if cls:
+                cc = video[4].contiguous().float()
+                assert cc.dim() == 2 and cc.size(1) == self.D and cc.size(0) >= 1, cc.shape
+                keep.append(cc)
+                cptr[v], nqs[v] = cc.data_ptr(), cc.size(0)
+            if text:
+                t, tm = video[3], video[5]
+                if not isinstance(t, (tuple, list)):
+                    t, tm = (t,), (tm,)
+                assert not cls or len(t) == nqs[v], (len(t), nqs[v])
+                nqs[v] = len(t)
+                flat_text += [x[0] for x in t]                               # (TE, Lk)
+                flat_masks += list(tm)
+        return _VideoTables(vptr if vid else None, sptr, mptr, cptr if cls else None, nqs, flat_text, flat_masks, keep)
+
+    def _level_sizes(self, T):
+        Tp = T // self.vid_net.stride               # the pyramid (and its position encoding) starts behind the strided convolutions
+        return [Tp >> l for l in range(self.vid_net.arch[2])]
+
+    def _install_pe(self, eng, T, dev, pe_tokens=None):
+        """dcf_model_set_pe for a forward on T clips: the model's own encoding, or the caller's slice ``pe_tokens`` of a longer video's.
+        Returns the tensor the engine now points at (None without use_abs_pe)."""
+        if not self.vid_net.use_abs_pe:
+            return None
+        Tp = self._level_sizes(T)[0]
+        pe = self._position_encoding(Tp, dev) if pe_tokens is None else pe_tokens.contiguous().float()
+        assert pe.shape == (Tp, self.E)
+        _lib.check(eng.lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), Tp), 'dcf_model_set_pe')
+        return pe
+
+    def _alloc_outputs(self, nq, S, dev, reuse):
+        """(logits (nq, S), offsets (nq, S, 2), masks (nq, S) bool): fresh, or with ``reuse`` the ones of the last call of this shape"""
+        okey = (nq, S, dev)
+        if reuse and okey in self._out_cache:
+            return self._out_cache[okey]
+        flat = (torch.empty(nq, S, device=dev, dtype=torch.float32), torch.empty(nq, S, 2, device=dev, dtype=torch.float32),
+                torch.empty(nq, S, device=dev, dtype=torch.bool))
+        if reuse:
+            self._out_cache = {okey: flat}
+        return flat
+
+    def _finish(self, keep, flat, half):
+        """After the engine call.  ``_last_inputs`` is ONE flat list of every tensor the engine borrowed (entries may be None): it keeps
+        them alive until the stream has consumed them, and nothing reads its order.  half (None: not an eval forward): what
+        ``last_feature_dtype`` reports."""
+        self._last_inputs = keep
+        self._last_flat = flat
+        if half is not None:
+            self.last_feature_dtype = torch.float16 if half else torch.float32
+        self._probe_numerics()
+
+    def _per_query_levels(self, flat, T, q0, q1):
+        """(logits, offsets, masks) of queries q0 .. q1 - 1 as the reference nests them: per query a tuple over the levels of (1, T_l) /
+        (1, T_l, 2) / (1, T_l) views of the flat buffers"""
+        sizes = self._level_sizes(T)
+        return tuple([tuple(x.unsqueeze(0) for x in buf[q].split(sizes)) for q in range(q0, q1)] for buf in flat)
+
     def forward_window(self, vid, shallow_vid, vid_masks, text, text_masks, gate, pe_tokens=None):
         """Extension used by T-sharding (dist.py): the eval forward on a window of a longer video with an
         externally selected 0/1 clip ``gate`` (NQ, T) and the window's slice ``pe_tokens`` (T, E) of the whole
@@ -1022,48 +1104,22 @@ class PtTransformerEarlyFusionIterative(nn.Module):
             raise ValueError(f'forward_selected: the selection is for {selection.nq} queries on {selection.T} clips, the call has {nq} '
                              f'on {T}')
         dev = shallow_vid.device
-        if self._engine is None:
-            self._engine = _Engine(self._config())
-        self._raise_if_flagged()
-        eng = self._engine
-        eng.bind(self)
+        eng = self._engine_ready()
         lib = eng.lib
         half = self.half_features and vid_rows.dtype == torch.float16
         rows_c = vid_rows.contiguous() if half else vid_rows.contiguous().float()
-        sh_c = shallow_vid[0].contiguous() if half else shallow_vid[0].contiguous().float()
-        mask_c = vid_masks.reshape(-1).to(torch.bool).contiguous()
+        tb = self._video_tables([(None, shallow_vid, vid_masks, text, None, text_masks)], half, vid=False, cls=False)
         gate_c, pos_c = selection.gate.contiguous().float(), selection.pos.contiguous()
-        assert mask_c.numel() == T and sh_c.shape == (self.D, T) and pos_c.dtype == torch.int32
-        keep = []
-        tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
-        for q in range(nq):
-            t = text[q][0].contiguous().float()                              # (TE, Lk)
-            m = text_masks[q].reshape(-1).to(torch.bool).contiguous()
-            assert t.dim() == 2 and m.numel() == t.size(1)
-            keep += [t, m]
-            tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
-        pe = None
-        if self.vid_net.use_abs_pe:
-            pe = self._position_encoding(T, dev) if pe_tokens is None else pe_tokens.contiguous().float()
-            assert pe.shape == (T, self.E)
-            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), T), 'dcf_model_set_pe')
-        S = lib.dcf_points_per_query(eng.handle, T)
-        logits = torch.empty(nq, S, device=dev, dtype=torch.float32)
-        offsets = torch.empty(nq, S, 2, device=dev, dtype=torch.float32)
-        masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
+        assert pos_c.dtype == torch.int32
+        tptr, mptr, tlen, tkeep = _text_table(tb.text, tb.text_masks)
+        pe = self._install_pe(eng, T, dev, pe_tokens)
+        logits, offsets, masks = flat = self._alloc_outputs(nq, lib.dcf_points_per_query(eng.handle, T), dev, False)
         fn, what = (lib.dcf_forward_eval_selected_h, 'dcf_forward_eval_selected_h') if half else \
                    (lib.dcf_forward_eval_selected, 'dcf_forward_eval_selected')
-        _lib.check(fn(eng.handle, _lib.ptr(rows_c), n, _lib.ptr(pos_c), _lib.ptr(sh_c), _lib.ptr(mask_c), T, nq, tptr, mptr, tlen,
+        _lib.check(fn(eng.handle, _lib.ptr(rows_c), n, _lib.ptr(pos_c), tb.shallow[0], tb.mask[0], T, nq, tptr, mptr, tlen,
                       _lib.ptr(gate_c), _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()), what)
-        self.last_feature_dtype = torch.float16 if half else torch.float32
-        self._last_inputs = (rows_c, sh_c, mask_c, gate_c, pos_c, keep, pe)
-        self._last_flat = (logits, offsets, masks)
-        self._probe_numerics()
-        sizes = [T >> l for l in range(self.vid_net.arch[2])]
-        lg = [tuple(x.unsqueeze(0) for x in logits[q].split(sizes)) for q in range(nq)]
-        of = [tuple(x.unsqueeze(0) for x in offsets[q].split(sizes)) for q in range(nq)]
-        mk = [tuple(x.unsqueeze(0) for x in masks[q].split(sizes)) for q in range(nq)]
-        return lg, of, mk
+        self._finish(tb.keep + tkeep + [rows_c, gate_c, pos_c, pe], flat, half)
+        return self._per_query_levels(flat, T, 0, nq)
 
     # -- selected-clip inference on several videos per forward (include/decafnet_hip_select_videos.h) ------------------------------
     def _selected_videos_refusals(self, what, nvid, lengths):
@@ -1085,39 +1141,24 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         and ONE device-to-host read, of the videos' counts.  Returns a ``SelectionBatch``; a ``scat`` model's carries the scores."""
         nv = len(videos)
         self._selected_videos_refusals('select_clips_videos', nv, [video[1].size(-1) for video in videos])
-        if len({video[1].dtype == torch.float16 for video in videos}) != 1:
-            raise ValueError('select_clips_videos: the videos of one call are all float16 or none of them is')
+        _same_dtype_videos('select_clips_videos', [video[1] for video in videos])
         if not videos[0][1].is_cuda:
             raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
         dev = videos[0][1].device
-        if self._engine is None:
-            self._engine = _Engine(self._config())
-        eng = self._engine
-        eng.bind(self)
+        eng = self._engine_ready(check_flag=False)  # no forward: what an earlier one flagged is raised by the next forward
         lib = eng.lib
         T = videos[0][1].size(-1)
         half = self.half_features and videos[0][1].dtype == torch.float16
-        keep = []
-        sptr, mptr, cptr = ((ctypes.c_void_p * nv)() for _ in range(3))
-        nqs = (ctypes.c_int32 * nv)()
-        for v, video in enumerate(videos):
-            shallow, vmask, text_cls = video[1], video[2], video[4]
-            assert shallow.dim() == 3 and shallow.size(0) == 1, shallow.size()
-            sc = shallow[0].contiguous() if half else shallow[0].contiguous().float()
-            mc = vmask.reshape(-1).to(torch.bool).contiguous()
-            cc = text_cls.contiguous().float()
-            assert sc.shape == (self.D, T) and mc.numel() == T and cc.dim() == 2 and cc.size(1) == self.D and cc.size(0) >= 1
-            keep += [sc, mc, cc]
-            sptr[v], mptr[v], cptr[v], nqs[v] = sc.data_ptr(), mc.data_ptr(), cc.data_ptr(), cc.size(0)
-        NQ = sum(nqs)
+        tb = self._video_tables(videos, half, vid=False, text=False)
+        NQ = sum(tb.nqs)
         gate = torch.empty(NQ, T, device=dev, dtype=torch.float32)
         scores = torch.empty(NQ, T, device=dev, dtype=torch.float32) if self.scat else None
         lists = torch.empty(2 * nv * T + nv, device=dev, dtype=torch.int32)          # clips, pos and counts: one allocation
         clips, pos, counts = lists[:nv * T].view(nv, T), lists[nv * T:2 * nv * T].view(nv, T), lists[2 * nv * T:]
         fn, what = (lib.dcf_select_videos_h, 'dcf_select_videos_h') if half else (lib.dcf_select_videos, 'dcf_select_videos')
-        _lib.check(fn(eng.handle, nv, sptr, mptr, T, nqs, cptr, _lib.ptr(gate), _lib.ptr(scores) if scores is not None else None,
-                      _lib.ptr(clips), _lib.ptr(pos), _lib.ptr(counts), _lib.current_stream()), what)
-        return SelectionBatch(gate, pos, clips, scores, counts.cpu().tolist(), list(nqs))
+        _lib.check(fn(eng.handle, nv, tb.shallow, tb.mask, T, tb.nqs, tb.cls, _lib.ptr(gate), _lib.ptr(scores), _lib.ptr(clips),
+                      _lib.ptr(pos), _lib.ptr(counts), _lib.current_stream()), what)
+        return SelectionBatch(gate, pos, clips, scores, counts.cpu().tolist(), list(tb.nqs))
 
     def gather_clip_rows_videos(self, vids, batch):
         """The packed rows ``forward_videos_selected`` takes, made from dense features: ``vids`` a sequence of (1, D, T) tensors, all
@@ -1126,8 +1167,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         nv = len(vids)
         if nv != batch.nvid:
             raise ValueError(f'gather_clip_rows_videos: {nv} feature tensors for a selection of {batch.nvid} videos')
-        if len({x.dtype == torch.float16 for x in vids}) != 1:
-            raise ValueError('gather_clip_rows_videos: the videos of one call are all float16 or none of them is')
+        _same_dtype_videos('gather_clip_rows_videos', vids)
         if not vids[0].is_cuda:
             raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
         lib = _lib.lib()
@@ -1174,66 +1214,26 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         T = videos[0][1].size(-1)
         if batch.T != T:
             raise ValueError(f'forward_videos_selected: the selection is on {batch.T} clips, the call has {T}')
-        if self._engine is None:
-            self._engine = _Engine(self._config())
-        self._raise_if_flagged()
-        eng = self._engine
-        eng.bind(self)
+        eng = self._engine_ready()
         lib = eng.lib
         half = self.half_features and vid_rows.dtype == torch.float16
         rows_c = vid_rows.contiguous() if half else vid_rows.contiguous().float()
-        keep = [rows_c]
-        sptr, mptr_v = (ctypes.c_void_p * nv)(), (ctypes.c_void_p * nv)()
-        nqs = (ctypes.c_int32 * nv)(*batch.nqs)
-        flat_text, flat_masks = [], []
-        for v, video in enumerate(videos):
-            shallow, vmask, text, tmasks = video[1], video[2], video[3], video[5]
-            sc = shallow[0].contiguous() if half else shallow[0].contiguous().float()
-            mc = vmask.reshape(-1).to(torch.bool).contiguous()
-            if not isinstance(text, (tuple, list)):
-                text, tmasks = (text,), (tmasks,)
-            assert sc.shape == (self.D, T) and mc.numel() == T
-            keep += [sc, mc]
-            sptr[v], mptr_v[v] = sc.data_ptr(), mc.data_ptr()
-            flat_text += list(text)
-            flat_masks += list(tmasks)
-        nq = len(flat_text)
-        tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
-        for q in range(nq):
-            t = flat_text[q][0].contiguous().float()
-            m = flat_masks[q].reshape(-1).to(torch.bool).contiguous()
-            assert t.dim() == 2 and m.numel() == t.size(1)
-            keep += [t, m]
-            tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
+        tb = self._video_tables(videos, half, vid=False, cls=False)
+        nq = len(tb.text)
+        tptr, mptr, tlen, tkeep = _text_table(tb.text, tb.text_masks)
         gate_c, pos_c = batch.gate.contiguous().float(), batch.pos.contiguous()
         scores_c = batch.scores.contiguous().float() if self.scat else None
         assert gate_c.shape == (nq, T) and pos_c.shape == (nv, T) and pos_c.dtype == torch.int32
-        pe = None
-        if self.vid_net.use_abs_pe:
-            pe = self._position_encoding(T, dev)
-            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), T), 'dcf_model_set_pe')
-        S = lib.dcf_points_per_query(eng.handle, T)
-        logits = torch.empty(nq, S, device=dev, dtype=torch.float32)
-        offsets = torch.empty(nq, S, 2, device=dev, dtype=torch.float32)
-        masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
+        pe = self._install_pe(eng, T, dev)
+        logits, offsets, masks = flat = self._alloc_outputs(nq, lib.dcf_points_per_query(eng.handle, T), dev, False)
         first = (ctypes.c_int32 * (nv + 1))(*batch.row_first)
         fn, what = (lib.dcf_forward_eval_videos_selected_h, 'dcf_forward_eval_videos_selected_h') if half else \
                    (lib.dcf_forward_eval_videos_selected, 'dcf_forward_eval_videos_selected')
-        _lib.check(fn(eng.handle, nv, _lib.ptr(rows_c), first, _lib.ptr(pos_c), sptr, mptr_v, T, nqs, tptr, mptr, tlen, _lib.ptr(gate_c),
-                      _lib.ptr(scores_c) if scores_c is not None else None, _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks),
-                      _lib.current_stream()), what)
-        self.last_feature_dtype = torch.float16 if half else torch.float32
-        self._last_inputs = (keep, gate_c, pos_c, scores_c, pe)
-        self._last_flat = (logits, offsets, masks)
-        self._probe_numerics()
-        sizes = [T >> l for l in range(self.vid_net.arch[2])]
-        out, q = [], 0
-        for n in batch.nqs:
-            out.append(([tuple(x.unsqueeze(0) for x in logits[i].split(sizes)) for i in range(q, q + n)],
-                        [tuple(x.unsqueeze(0) for x in offsets[i].split(sizes)) for i in range(q, q + n)],
-                        [tuple(x.unsqueeze(0) for x in masks[i].split(sizes)) for i in range(q, q + n)]))
-            q += n
-        return out
+        _lib.check(fn(eng.handle, nv, _lib.ptr(rows_c), first, _lib.ptr(pos_c), tb.shallow, tb.mask, T, tb.nqs, tptr, mptr, tlen,
+                      _lib.ptr(gate_c), _lib.ptr(scores_c), _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()),
+                   what)
+        self._finish(tb.keep + tkeep + [rows_c, gate_c, pos_c, scores_c, pe], flat, half)
+        return [self._per_query_levels(flat, T, batch.q_first[v], batch.q_first[v + 1]) for v in range(nv)]
 
     # -- one long video cut at pyramid level k (dist.hybrid_forward; dcf_hybrid_phase1 / 2 / 3) --------------------------------
     def hybrid_phase1(self, vid_w, shallow_w, mask_w, text, text_masks, gate_w, k, Tc, pe_tokens=None):
@@ -1241,34 +1241,18 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         pe_tokens: (Tn, E) the window's slice of the video's position encoding; Tc: level-k rows of the coarse window the later phases
         will use).  Returns the window's level-k features (NQ, Tn >> k, E)."""
         dev = vid_w.device
-        if self._engine is None:
-            self._engine = _Engine(self._config())
-        self._raise_if_flagged()
-        eng = self._engine
-        eng.bind(self)
-        lib = eng.lib
+        eng = self._engine_ready()
         Tn = vid_w.size(-1)
-        vid_c, sh_c = vid_w.contiguous().float(), shallow_w.contiguous().float()
-        mask_c = mask_w.reshape(-1).to(torch.bool).contiguous()
         nq = len(text)
+        tb = self._video_tables([(vid_w[None], shallow_w[None], mask_w, text, None, text_masks)], False, cls=False)
         gate_c = gate_w.contiguous().float()
-        assert vid_c.shape == sh_c.shape == (self.D, Tn) and mask_c.numel() == Tn and gate_c.shape == (nq, Tn)
-        keep = []
-        tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
-        for q in range(nq):
-            t = text[q][0].contiguous().float()
-            m = text_masks[q].reshape(-1).to(torch.bool).contiguous()
-            keep += [t, m]
-            tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
-        pe = None
-        if self.vid_net.use_abs_pe:
-            pe = pe_tokens.contiguous().float()
-            assert pe.shape == (Tn, self.E)
-            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), Tn), 'dcf_model_set_pe')
+        assert gate_c.shape == (nq, Tn)
+        tptr, mptr, tlen, tkeep = _text_table(tb.text, tb.text_masks)
+        pe = self._install_pe(eng, Tn, dev, pe_tokens)
         featk = torch.empty(nq, Tn >> k, self.E, device=dev, dtype=torch.float32)
-        _lib.check(lib.dcf_hybrid_phase1(eng.handle, k, _lib.ptr(vid_c), _lib.ptr(sh_c), _lib.ptr(mask_c), Tn, Tc, nq, tptr, mptr, tlen,
-                                         _lib.ptr(gate_c), _lib.ptr(featk), _lib.current_stream()), 'dcf_hybrid_phase1')
-        self._last_inputs = (vid_c, sh_c, mask_c, gate_c, keep, pe)
+        _lib.check(eng.lib.dcf_hybrid_phase1(eng.handle, k, tb.vid[0], tb.shallow[0], tb.mask[0], Tn, Tc, nq, tptr, mptr, tlen,
+                                             _lib.ptr(gate_c), _lib.ptr(featk), _lib.current_stream()), 'dcf_hybrid_phase1')
+        self._last_inputs = tb.keep + tkeep + [gate_c, pe]          # phases 2 and 3 append theirs; phase 3 ends with the numerics probe
         self._hybrid = (k, Tn, Tc, nq)
         return featk
 
@@ -1283,7 +1267,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         refk = torch.empty(nq, Tn >> k, 32, device=f.device, dtype=torch.float32)
         _lib.check(lib.dcf_hybrid_phase2(eng.handle, _lib.ptr(f), _lib.ptr(mk), int(off_k), _lib.ptr(refk), _lib.current_stream()),
                    'dcf_hybrid_phase2')
-        self._last_inputs = self._last_inputs + (f, mk)
+        self._last_inputs = self._last_inputs + [f, mk]
         return refk
 
     def hybrid_phase3(self, refk_c):
@@ -1302,7 +1286,7 @@ class PtTransformerEarlyFusionIterative(nn.Module):
                       torch.empty(nq, max(Sc, 1), device=dev, dtype=torch.bool))
         _lib.check(lib.dcf_hybrid_phase3(eng.handle, _lib.ptr(r), _lib.ptr(ln), _lib.ptr(on), _lib.ptr(mn), _lib.ptr(lc), _lib.ptr(oc),
                                          _lib.ptr(mc), _lib.current_stream()), 'dcf_hybrid_phase3')
-        self._last_inputs = self._last_inputs + (r,)
+        self._last_inputs = self._last_inputs + [r]
         self._probe_numerics()
         return (ln, on, mn), (lc[:, :Sc], oc[:, :Sc], mc[:, :Sc])
 
@@ -1320,73 +1304,27 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         assert len(videos) >= 1
         for video in videos:
             _check_feature_dtypes(video[0], video[1])
-        if len({video[0].dtype == torch.float16 for video in videos}) != 1:
-            raise ValueError('forward_videos: the videos of one call are all float16 or none of them is')
+        _same_dtype_videos('forward_videos', [video[0] for video in videos])
         if not videos[0][0].is_cuda:
             raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
         dev = videos[0][0].device
-        if self._engine is None:
-            self._engine = _Engine(self._config())
-        self._raise_if_flagged()
-        eng = self._engine
-        eng.bind(self)
+        eng = self._engine_ready()
         lib = eng.lib
         T = videos[0][0].size(-1)
         nv = len(videos)
-        keep = []
-        vptr, sptr, mptr_v, cptr = ((ctypes.c_void_p * nv)() for _ in range(4))
-        nqs = (ctypes.c_int32 * nv)()
-        flat_text, flat_masks = [], []
-        for v, (vid, shallow, vmask, text, text_cls, tmasks) in enumerate(videos):
-            assert vid.size(0) == 1 and vid.size(-1) == T, 'videos of one call share the padded length'
-            vc, sc, half = self._feature_pair(vid[0], shallow[0])
-            mc = vmask.reshape(-1).to(torch.bool).contiguous()
-            if not isinstance(text, (tuple, list)):
-                text, tmasks = (text,), (tmasks,)
-            cc = text_cls.contiguous().float()
-            assert sc.shape == vc.shape == (self.D, T) and mc.numel() == T and cc.shape == (len(text), self.D)
-            keep += [vc, sc, mc, cc]
-            vptr[v], sptr[v], mptr_v[v], cptr[v], nqs[v] = vc.data_ptr(), sc.data_ptr(), mc.data_ptr(), cc.data_ptr(), len(text)
-            flat_text += list(text)
-            flat_masks += list(tmasks)
-        nq = len(flat_text)
-        tptr, mptr, tlen = (ctypes.c_void_p * nq)(), (ctypes.c_void_p * nq)(), (ctypes.c_int32 * nq)()
-        for q in range(nq):
-            t = flat_text[q][0].contiguous().float()
-            m = flat_masks[q].reshape(-1).to(torch.bool).contiguous()
-            assert t.dim() == 2 and m.numel() == t.size(1)
-            keep += [t, m]
-            tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
-        pe = None
-        if self.vid_net.use_abs_pe:
-            Tp = T // self.vid_net.stride            # the pyramid (and its position encoding) starts behind the strided convolutions
-            pe = self._position_encoding(Tp, dev)
-            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), Tp), 'dcf_model_set_pe')
-        S = lib.dcf_points_per_query(eng.handle, T)
-        okey = (nq, S, dev)
-        if self.reuse_output_buffers and okey in self._out_cache:
-            logits, offsets, masks = self._out_cache[okey]
-        else:
-            logits = torch.empty(nq, S, device=dev, dtype=torch.float32)
-            offsets = torch.empty(nq, S, 2, device=dev, dtype=torch.float32)
-            masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
-            if self.reuse_output_buffers:
-                self._out_cache = {okey: (logits, offsets, masks)}
+        half = self.half_features and videos[0][0].dtype == torch.float16
+        tb = self._video_tables(videos, half)
+        nq = len(tb.text)
+        tptr, mptr, tlen, tkeep = _text_table(tb.text, tb.text_masks)
+        pe = self._install_pe(eng, T, dev)
+        logits, offsets, masks = flat = self._alloc_outputs(nq, lib.dcf_points_per_query(eng.handle, T), dev, self.reuse_output_buffers)
         fn, what = (lib.dcf_forward_eval_videos_h, 'dcf_forward_eval_videos_h') if half else (lib.dcf_forward_eval_videos, 'dcf_forward_eval_videos')
-        _lib.check(fn(eng.handle, nv, vptr, sptr, mptr_v, T, nqs, tptr, mptr, tlen, cptr, _lib.ptr(logits),
+        _lib.check(fn(eng.handle, nv, tb.vid, tb.shallow, tb.mask, T, tb.nqs, tptr, mptr, tlen, tb.cls, _lib.ptr(logits),
                       _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()), what)
-        self.last_feature_dtype = torch.float16 if half else torch.float32
-        self._last_inputs = (keep, pe)
-        self._last_flat = (logits, offsets, masks)
-        self._probe_numerics()
-        L = self.vid_net.arch[2]
-        sizes = [(T // self.vid_net.stride) >> l for l in range(L)]
+        self._finish(tb.keep + tkeep + [pe], flat, half)
         out, q = [], 0
-        for v in range(nv):
-            n = nqs[v]
-            out.append(([tuple(x.unsqueeze(0) for x in logits[i].split(sizes)) for i in range(q, q + n)],
-                        [tuple(x.unsqueeze(0) for x in offsets[i].split(sizes)) for i in range(q, q + n)],
-                        [tuple(x.unsqueeze(0) for x in masks[i].split(sizes)) for i in range(q, q + n)]))
+        for n in tb.nqs:
+            out.append(self._per_query_levels(flat, T, q, q + n))
             q += n
         return out
 
@@ -1398,67 +1336,28 @@ class PtTransformerEarlyFusionIterative(nn.Module):
         if not vid.is_cuda:
             raise RuntimeError('the grounding forward runs on the MI355X only: move the inputs to the GPU')
         dev = vid.device
-        if self._engine is None:
-            self._engine = _Engine(self._config())
-        self._raise_if_flagged()
-        eng = self._engine
-        eng.bind(self)
+        eng = self._engine_ready()
         lib = eng.lib
         T = vid.size(-1)
-        vid_c, sh_c, half = self._feature_pair(vid[0], shallow_vid[0], half_ok=gate is None)
-        mask_c = vid_masks.reshape(-1).to(torch.bool).contiguous()
-        assert mask_c.numel() == T and sh_c.shape == vid_c.shape == (self.D, T)
-        if not isinstance(text, (tuple, list)):
-            text, text_masks = (text,), (text_masks,)
-        nq = len(text)
+        half = gate is None and self.half_features and vid.dtype == torch.float16
+        tb = self._video_tables([(vid, shallow_vid, vid_masks, text, text_cls, text_masks)], half, cls=gate is None)
+        nq = len(tb.text)
         if gate is None:
-            cls_c = text_cls.contiguous().float()
-            assert cls_c.shape == (nq, self.D), (cls_c.shape, nq, self.D)
+            cls_p = tb.cls[0]
         else:
-            cls_c = gate.contiguous().float()
-            assert cls_c.shape == (nq, T), (cls_c.shape, nq, T)
-        keep = []
-        tptr = (ctypes.c_void_p * nq)()
-        mptr = (ctypes.c_void_p * nq)()
-        tlen = (ctypes.c_int32 * nq)()
-        for q in range(nq):
-            t = text[q][0].contiguous().float()                              # (TE, Lk)
-            m = text_masks[q].reshape(-1).to(torch.bool).contiguous()
-            assert t.dim() == 2 and m.numel() == t.size(1)
-            keep += [t, m]
-            tptr[q], mptr[q], tlen[q] = t.data_ptr(), m.data_ptr(), t.size(1)
-        if self.vid_net.use_abs_pe:
-            Tp = T // self.vid_net.stride
-            pe = self._position_encoding(Tp, dev) if pe_tokens is None else pe_tokens.contiguous().float()
-            assert pe.shape == (Tp, self.E)
-            _lib.check(lib.dcf_model_set_pe(eng.handle, _lib.ptr(pe), Tp), 'dcf_model_set_pe')
-        else:
-            pe = None
-        S = lib.dcf_points_per_query(eng.handle, T)
-        okey = (nq, S, dev)
-        if self.reuse_output_buffers and okey in self._out_cache:
-            logits, offsets, masks = self._out_cache[okey]
-        else:
-            logits = torch.empty(nq, S, device=dev, dtype=torch.float32)
-            offsets = torch.empty(nq, S, 2, device=dev, dtype=torch.float32)
-            masks = torch.empty(nq, S, device=dev, dtype=torch.bool)
-            if self.reuse_output_buffers:
-                self._out_cache = {okey: (logits, offsets, masks)}
-        fn = lib.dcf_forward_eval_h if half else lib.dcf_forward_eval if gate is None else lib.dcf_forward_eval_gated
-        _lib.check(fn(eng.handle, _lib.ptr(vid_c), _lib.ptr(sh_c), _lib.ptr(mask_c), T, nq, tptr, mptr, tlen,
-                      _lib.ptr(cls_c), _lib.ptr(logits), _lib.ptr(offsets), _lib.ptr(masks), _lib.current_stream()),
-                   'dcf_forward_eval_h' if half else 'dcf_forward_eval')
-        self.last_feature_dtype = torch.float16 if half else torch.float32
-        # keep the borrowed inputs alive until the stream has consumed them
-        self._last_inputs = (vid_c, sh_c, mask_c, cls_c, keep, pe)
-        self._last_flat = (logits, offsets, masks)
-        self._probe_numerics()
-        L = self.vid_net.arch[2]
-        sizes = [(T // self.vid_net.stride) >> l for l in range(L)]
-        lg = [tuple(x.unsqueeze(0) for x in logits[q].split(sizes)) for q in range(nq)]
-        of = [tuple(x.unsqueeze(0) for x in offsets[q].split(sizes)) for q in range(nq)]
-        mk = [tuple(x.unsqueeze(0) for x in masks[q].split(sizes)) for q in range(nq)]
-        return lg, of, mk
+            gate_c = gate.contiguous().float()
+            assert gate_c.shape == (nq, T), (gate_c.shape, nq, T)
+            tb.keep.append(gate_c)
+            cls_p = _lib.ptr(gate_c)
+        tptr, mptr, tlen, tkeep = _text_table(tb.text, tb.text_masks)
+        pe = self._install_pe(eng, T, dev, pe_tokens)
+        logits, offsets, masks = flat = self._alloc_outputs(nq, lib.dcf_points_per_query(eng.handle, T), dev, self.reuse_output_buffers)
+        fn, what = (lib.dcf_forward_eval_h, 'dcf_forward_eval_h') if half else (lib.dcf_forward_eval, 'dcf_forward_eval') if gate is None else \
+                   (lib.dcf_forward_eval_gated, 'dcf_forward_eval_gated')
+        _lib.check(fn(eng.handle, tb.vid[0], tb.shallow[0], tb.mask[0], T, nq, tptr, mptr, tlen, cls_p, _lib.ptr(logits), _lib.ptr(offsets),
+                      _lib.ptr(masks), _lib.current_stream()), what)
+        self._finish(tb.keep + tkeep + [pe], flat, half)
+        return self._per_query_levels(flat, T, 0, nq)
 
 
 class PtTransformer(PtTransformerEarlyFusionIterative):
